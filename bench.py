@@ -8,6 +8,10 @@ Workload (config C2/C3): ViT-S/8 student+teacher, DINO head K=100000, 2 global 1
 crops, batch 64 per GPU, drop_path 0.1, epoch >= 1 (last layer unfrozen), bf16 MFMA GEMMs with fp32 accumulate /
 residual stream / optimizer.  One "step" = teacher fwd + student fwd + DINO loss + backward + RCCL gradient/center
 all-reduce + per-tensor clip + AdamW + teacher EMA + center EMA, inputs resident in HBM.
+
+A plain run sets up, warms up, times the steps and prints the headline line.  --full adds the measurements the headline does not
+need (roofline kernel loops, committed-profile read-backs, CPU oracle baseline, non-headline extras); --dump-outputs DIR writes
+what the last timed step computed.
 """
 import argparse
 import json
@@ -62,7 +66,16 @@ def parse():
     ap.add_argument("--frontend", action="store_true",
                     help="include the landmark front-end (frozen MobileNetV3 on 10*B views + theta + gathers) in every step, "
                          "software-pipelined on its own stream; default off = landmark crops resident in HBM (the headline metric)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline steps also measure what the headline figure does not need: the roofline kernels' loops, "
+                         "the HBM bytes read back from committed profiles, the CPU oracle baseline and the non-headline extras "
+                         "(--no-roofline / --no-cpu-baseline / --no-extras leave out single parts)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last step computed as DIR/<name>.npy (see dump_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def _time_on_stream(fn, iters):
@@ -463,6 +476,31 @@ def run_extras(device, which=("mynet", "finetune")):
     return out
 
 
+DUMP_SAMPLE = 1 << 22
+
+
+def _flat_params(arena):
+    """The arena's fp32 master weights in module parameter order, without the arena's chunk padding."""
+    return torch.cat([arena.view(arena.master, n) for n in arena.names])
+
+
+def dump_outputs(out_dir, eng, loss):
+    """What a caller of the timed step holds after its last step, as float32 .npy files: the loss, the DINO center, and the
+    student's and teacher's weights after the update and the EMA.  The weights (~53 M floats each with the 100 000-class head)
+    are a fixed sample of DUMP_SAMPLE positions drawn from a seeded generator, the same positions in both networks, so that
+    the files stay at ~33 MB together; smaller networks are written whole."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    student, teacher = _flat_params(eng.sa), _flat_params(eng.ta)
+    if student.numel() > DUMP_SAMPLE:
+        idx = torch.randint(0, student.numel(), (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values
+        idx = idx.to(student.device)
+        student, teacher = student[idx], teacher[idx]
+    arrays = {"loss": loss.detach().reshape(1), "center": eng.dino_loss.center, "student_weights": student, "teacher_weights": teacher}
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
+
+
 def spawn_ranks(args):
     """`python bench.py --gpus N` without a launcher: start N fresh rank processes of this script (one per GPU, RCCL over
     127.0.0.1) BEFORE this process touches the GPU, relay rank 0's JSON line, exit with the worst return code."""
@@ -611,6 +649,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     loss_v = float(loss.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, eng, loss)
 
     if rank == 0:
         ms = dt / args.steps * 1e3
@@ -634,18 +674,19 @@ def main():
             # an empty object = the shipped configuration)
             "lafs_env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("LAFS_") and k != "LAFS_BENCH_SHARE_GPU"},
         }
-        hb = step_hbm_bytes()
-        if hb is not None:                           # measured HBM bytes of one step (committed PMC profile) over this run's time
-            out["step_hbm_bytes"] = hb
-            out["step_hbm_frac"] = round(hb / (ms * 1e-3) / 8e12, 4)
-        if not args.no_roofline:
-            out["roofline"] = dominant_kernel_roofline(device)
-        out["profile_provenance"] = PROFILE_NOTES       # which committed profile each read-back number came from (null = stale)
-        if world == 1 and not args.no_cpu_baseline:
-            out["cpu_baseline"] = cpu_baseline(dims, nl, K, args.cpu_batch)
-        if world == 1 and not args.no_extras and args.arch == "vit_small" and not args.frontend:
-            del eng, student, teacher, crit
-            out["extras"] = run_extras(device)
+        if args.full:
+            hb = step_hbm_bytes()
+            if hb is not None:                           # measured HBM bytes of one step (committed PMC profile) over this run's time
+                out["step_hbm_bytes"] = hb
+                out["step_hbm_frac"] = round(hb / (ms * 1e-3) / 8e12, 4)
+            if not args.no_roofline:
+                out["roofline"] = dominant_kernel_roofline(device)
+            out["profile_provenance"] = PROFILE_NOTES       # which committed profile each read-back number came from (null = stale)
+            if world == 1 and not args.no_cpu_baseline:
+                out["cpu_baseline"] = cpu_baseline(dims, nl, K, args.cpu_batch)
+            if world == 1 and not args.no_extras and args.arch == "vit_small" and not args.frontend:
+                del eng, student, teacher, crit
+                out["extras"] = run_extras(device)
         print(json.dumps(out))
     if world > 1:
         dist.barrier()

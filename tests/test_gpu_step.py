@@ -265,7 +265,8 @@ def test_bench_owns_its_launch_two_ranks_on_one_gpu():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     bench = os.path.join(root, "bench.py")
-    small = ["--steps", "2", "--warmup", "1", "--batch", "2", "--arch", "vit_tiny", "--out-dim", "1024", "--local-crops", "2", "--no-cpu-baseline"]
+    small = ["--steps", "2", "--warmup", "1", "--batch", "2", "--arch", "vit_tiny", "--out-dim", "1024", "--local-crops", "2", "--no-cpu-baseline",
+             "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LAFS_DEBUG_FLAGS")}
     r = subprocess.run([sys.executable, bench, "--gpus", "2"] + small, env=dict(env, LAFS_BENCH_SHARE_GPU="1"), capture_output=True, text=True,
                        timeout=600)
@@ -282,29 +283,76 @@ def test_bench_owns_its_launch_two_ranks_on_one_gpu():
     assert r.returncode != 0 and "debug flags" in r.stderr
 
 
-def test_bench_eight_rank_launch_is_ready_for_an_eight_gpu_node():
-    """The launch the driver uses on an 8-GPU node -- `bench.py --gpus 8` -- at toy dimensions with all eight ranks on the one GPU over
-    gloo (LAFS_BENCH_SHARE_GPU=1; RCCL wants one device per rank): eight rank processes, segmented graphs with the gradient / center
-    all-reduces between them, barrier + max-over-ranks timing, ONE JSON line from rank 0 that reports what the communication backend
-    really saw.  No 1 -> 8 scaling curve has been measured on hardware (README); this pins the launch structure, not a rate."""
+def test_bench_plain_run_is_the_headline_and_dumps_the_last_step(tmp_path):
+    """A plain `bench.py` run times the steps and prints the headline line without the --full measurements (roofline loops, CPU
+    baseline, extras), and --dump-outputs writes the last timed step's loss, center and weights as float32 .npy files -- the same
+    bits in two runs with the same arguments, so that two builds can be compared output for output."""
     import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    # (eight processes time-slicing one GPU pay a context switch per kernel: the trunk is cut to 2 blocks -- 250 s at depth 12)
+    small = ["--steps", "3", "--warmup", "1", "--batch", "2", "--arch", "vit_tiny", "--depth", "2", "--out-dim", "1024", "--local-crops", "2"]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LAFS_DEBUG_FLAGS")}
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"out{i}"
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + small + ["--dump-outputs", str(d)], env=env,
+                           capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        runs.append((json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]), {f.stem: np.load(f) for f in d.glob("*.npy")}))
+    line, got = runs[0]
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["unit"] == "face-crops/s" and line["dtype"] == "bf16"
+    assert abs(line["value"] - 2 * 4 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]
+    assert not {"roofline", "cpu_baseline", "extras", "profile_provenance"} & set(line)
+    assert set(got) == {"loss", "center", "student_weights", "teacher_weights"}
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    assert got["center"].shape == (1, 1024) and got["student_weights"].shape == got["teacher_weights"].shape
+    assert abs(float(got["loss"][0]) - line["final_loss"]) < 1e-3 * abs(line["final_loss"]) + 1e-4
+    again = runs[1][1]
+    assert set(again) == set(got) and all(np.array_equal(got[k], again[k]) for k in got)
+
+
+def _bench_launch(n, share):
+    """`bench.py --gpus n` at toy dimensions: n rank processes started by bench.py itself, segmented graphs with the gradient / center
+    all-reduces between them, barrier + max-over-ranks timing, ONE JSON line from rank 0 that reports what the communication backend
+    really saw.  share: every rank on GPU 0 over gloo (LAFS_BENCH_SHARE_GPU=1; RCCL wants one device per rank), else one GPU per rank
+    over RCCL.  No 1 -> 8 scaling curve has been measured on hardware (README); this pins the launch structure, not a rate."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    # (ranks time-slicing one GPU pay a context switch per kernel: the trunk is cut to 2 blocks -- 250 s for eight at depth 12)
     small = ["--steps", "2", "--warmup", "1", "--batch", "2", "--arch", "vit_tiny", "--depth", "2", "--out-dim", "1024", "--local-crops", "2",
              "--no-cpu-baseline", "--no-roofline"]
-    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LAFS_DEBUG_FLAGS")}
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8"] + small, env=dict(env, LAFS_BENCH_SHARE_GPU="1"),
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "LAFS_DEBUG_FLAGS", "LAFS_BENCH_SHARE_GPU")}
+    if share:
+        env["LAFS_BENCH_SHARE_GPU"] = "1"
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n)] + small, env=env,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, lines
     line = json.loads(lines[0])
-    assert line["n_gpus"] == 8 and line["comm"]["ranks_seen"] == 8 and line["comm"]["backend"] == "gloo"
-    assert line["config"]["parallelism"] == "dp8" and line["config"]["global_batch"] == 16 and line["scaling"] == "weak"
-    assert line["value"] > 0 and abs(line["value"] - 8 * 2 * 4 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]      # whole-job crops/s
+    assert line["n_gpus"] == n and line["comm"]["ranks_seen"] == n and line["comm"]["backend"] == ("gloo" if share else "nccl")
+    assert line["config"]["parallelism"] == f"dp{n}" and line["config"]["global_batch"] == 2 * n and line["scaling"] == "weak"
+    assert line["value"] > 0 and abs(line["value"] - n * 2 * 4 / (line["ms_per_step"] * 1e-3)) < 1e-3 * line["value"]      # whole-job crops/s
+
+
+def test_bench_four_rank_launch_shares_one_gpu():
+    """The multi-rank launch of `bench.py` with four ranks sharing the one GPU over gloo.  Four ranks keep the processes that hold the
+    GPU at once (this test's and the ranks'; the launching parent only counts devices) at five."""
+    _bench_launch(4, share=True)
+
+
+def test_bench_eight_rank_launch_over_rccl_on_an_eight_gpu_node():
+    """The launch the driver uses on an 8-GPU node -- `bench.py --gpus 8` -- one GPU per rank over RCCL."""
+    n_gpu = torch.cuda.device_count()
+    if n_gpu < 8:
+        pytest.skip(f"needs 8 GPUs (one per rank), found {n_gpu}")
+    _bench_launch(8, share=False)
 
 
 # ------------------------------------------------------------------------------------------------ Part-fViT as the LAFS pair

@@ -3,7 +3,7 @@
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/final; mkdir -p $O; cd $R
 timeout 2400 python -m pytest tests -x -q -m gpu -p no:cacheprovider > $O/gpu_tests.log 2>&1; echo "gpu tests rc=$?"; tail -2 $O/gpu_tests.log | cut -c1-200
 python -c "import __graft_entry__ as g; g.build(); g.smoke()" 2>&1 | tail -1
-timeout 1500 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python - <<PY
+timeout 1500 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench rc=$?"; python - <<PY
 import json
 for l in open("$O/bench.json"):
     if l.strip().startswith("{"):

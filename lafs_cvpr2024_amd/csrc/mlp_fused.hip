@@ -609,7 +609,11 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
         xh[ob][0] = v.x; xh[ob][1] = v.y; xh[ob][2] = v.z; xh[ob][3] = v.w;
       }
     }
-    float* red = reinterpret_cast<float*>(smem + 2 * STAGE);      // [wave][gamma 384 | beta 384]: ring buffer 2 holds stage 45, read by all
+    // [wave][gamma 384 | beta 384] in ring buffer 2.  Stage s of the loop sits in buffer (2 + s) % 3, so the last one (s = 2 NI - 1)
+    // is in buffer 2 when NI % 3 == 2 (H = 128, 320, 512, ...): a fast wave's stores below would overwrite the Wb slice a slower
+    // wave is still reading.  The barrier lets every wave finish its last stage first.
+    float* red = reinterpret_cast<float*>(smem + 2 * STAGE);
+    __syncthreads();
     if (active) {
 #pragma unroll
       for (int ob = 0; ob < NOB; ++ob) {

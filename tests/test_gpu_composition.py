@@ -139,6 +139,13 @@ def test_benchmark_composition_vit_small_droppath_against_the_oracle(B):
     assert eng._graphs is not None and len(eng._graphs) == 1                       # one captured graph, as in the benchmark
     chains, rows, routes = _routes(eng)
     assert chains == 2, chains
+    # the block's MLP runs fused (engine.hip mlp_fused_on): forward-only, saving and backward passes, LayerNorm 2 and the next
+    # block's LayerNorm 1 inside, for both row chains -- not quietly as two GEMM launches
+    h, d = _lib.lib(), eng._st["vit"].desc
+    fused = h.lafs_ctx_get(d.ctx, _lib.OPT_MLP_FUSED)
+    assert fused & (1 | 2 | 4 | 8 | 64) == 1 | 2 | 4 | 8 | 64, fused
+    assert all(h.lafs_mlp_fused_supported(d.dim, d.mlp, R) == 1 for R in rows) and (d.dim, d.mlp) == (384, 1536), (d.dim, d.mlp, rows)
+    assert d.dropout_p == 0.0
     for name in ("qkv", "fc1", "proj", "dgelu"):
         assert all(r in (1, 2) for r in routes[name]), (name, routes)               # K-resident (either form)
     if B == 64:

@@ -878,13 +878,14 @@ def test_fused_mlp_with_the_attention_projection_in_front(M, mode):
     assert relerr(x1[:M], want) < 2e-3
 
 
-@pytest.mark.parametrize("M", [128 * 35, 128 * 33 + 50])
-def test_fused_mlp_backward_with_the_layernorm_backward_in_its_epilogue(M):
+@pytest.mark.parametrize("M,H", [pytest.param(128 * 35, 1536, id="4480"), pytest.param(128 * 33 + 50, 1536, id="4274"),
+                                 pytest.param(128 * 33 + 50, 512, id="4274-H512")])     # H = 512: the last stage-B slice sits in the LDS the epilogue reuses
+def test_fused_mlp_backward_with_the_layernorm_backward_in_its_epilogue(M, H):
     """LAFS_MLP_BWD with the LayerNorm-2 backward in the epilogue (vision_transformer.py:112 backward) against the separate path --
     lafs_mlp_fused(BWD) storing dX, then lafs_layernorm_bwd(accumulate) with its partial slots, then the fold: the residual gradient
     stream, its DropPath-scaled bf16 copy and dgamma / dbeta agree to fp32 summation order (the epilogue rounds dX to bf16 exactly
     as the stored tensor is); du is bit-identical; rows past M untouched."""
-    D, H = 384, 1536
+    D = 384
     g = torch.Generator().manual_seed(91)
     x = (torch.randn(M, D, generator=g) * 1.3 + 0.2).to(DEV)
     gam = (1.0 + 0.2 * torch.randn(D, generator=g)).to(DEV); bet = torch.zeros(D, device=DEV)

@@ -215,9 +215,7 @@ def lib():
         # library binds to the very same HIP runtime instance (streams and device pointers are shared with torch).
         import torch  # noqa: F401
         path = LIB_PATH
-        if os.environ.get("LAFS_USE_ABLATE_LIB") == "1":          # tools/bench_kernels.py ablate: result-changing timing flags
-            path = os.path.join(_HERE, "liblafs_hip_ablate.so")
-        elif os.environ.get("LAFS_LIB_VARIANT"):                  # lab: an A/B build of the same sources (csrc/Makefile `variant`)
+        if os.environ.get("LAFS_LIB_VARIANT"):                  # lab: an A/B build of the same sources (csrc/Makefile `variant`)
             path = os.path.join(_HERE, "liblafs_hip_%s.so" % os.environ["LAFS_LIB_VARIANT"])
         if not os.path.isfile(path):
             raise LafsHipError(f"{path} not found: the HIP extension is not built (run __graft_entry__.build()); "
@@ -232,7 +230,7 @@ def lib():
             fn.argtypes = list(args)
             fn.restype = res
         _lib = h
-        flags = os.environ.get("LAFS_DEBUG_FLAGS")               # A/B experiments on whole steps (see lafs_debug_set in lafs_hip.h)
+        flags = os.environ.get("LAFS_DEBUG_FLAGS")               # recorded only (see lafs_debug_set in lafs_hip.h)
         if flags:
             h.lafs_debug_set(int(flags, 0))
     return _lib

@@ -15,6 +15,12 @@ extern "C" void lafs_set_error(const char* fmt, ...) {
 extern "C" const char* lafs_last_error(void) { return g_err; }
 extern "C" int lafs_version(void) { return LAFS_ABI_VERSION; }
 
+// The debug-flag word of the C ABI: recorded and returned, read by no kernel or dispatch (include/lafs_hip.h)
+static int g_debug_word = 0;
+extern "C" int lafs_debug_set(int flags) { g_debug_word = flags; return LAFS_OK; }
+extern "C" int lafs_debug_get(void) { return g_debug_word; }
+extern "C" int lafs_ablation_build(void) { return 0; }
+
 // Diagnostic: what does ds_read_b64_tr_b16 return when lane l reads LDS bytes [8*l, 8*l+8) of a 512-element ramp?
 // out[l*4 + j] = element index delivered to lane l, slot j.  Used by tests to pin the transpose-read model the
 // attention / wgrad kernels are built on.

@@ -33,18 +33,11 @@ namespace {
 typedef __attribute__((ext_vector_type(8))) short s16x8_t;
 
 // 16 bytes of an operand the BACKWARD kernels read exactly once (q, k, v, dO, O of a pair): non-temporal, so that these streams do not
-// displace what the kernels running beside the attention backward re-read from the L2.  LAFS_ATTN_NT=0: plain loads (lab).
-#ifndef LAFS_ATTN_NT
-#define LAFS_ATTN_NT 1
-#endif
+// displace what the kernels running beside the attention backward re-read from the L2.
 __device__ __forceinline__ uint4 ld_once16(const bf16_t* p) {
-#if LAFS_ATTN_NT
   typedef unsigned u4v __attribute__((ext_vector_type(4)));
   const u4v v = __builtin_nontemporal_load(reinterpret_cast<const u4v*>(p));
   return make_uint4(v[0], v[1], v[2], v[3]);
-#else
-  return *reinterpret_cast<const uint4*>(p);
-#endif
 }
 
 __device__ __forceinline__ bf16x8_t to_frag(s16x4_t lo, s16x4_t hi) {
@@ -632,18 +625,15 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kernel(AttnArgs a) {
       }
     }
   };
-#ifndef LAFS_LAB_ATTN_ABL
-#define LAFS_LAB_ATTN_ABL 0
-#endif
   bool more = true;
   // the stops of the dQ phase (the next pair's Q, lse) and of the dK/dV phase (its K, V, dO, delta)
   auto stop_q = [&](int u) __attribute__((always_inline)) {
-    if (!more || (LAFS_LAB_ATTN_ABL & 2)) return;
+    if (!more) return;
     if (u == 0) { request(r0, s_q, a.ldqkv); request_lse(); }
     else if (u == H2) { deposit_f(s_x, r0); deposit_lse(); }
   };
   auto stop_k = [&](int u) __attribute__((always_inline)) {
-    if (!more || (LAFS_LAB_ATTN_ABL & 1)) return;
+    if (!more) return;
     if (u == 0) { request(r0, s_q + inner, a.ldqkv); request(r1, s_q + 2 * inner, a.ldqkv); }
     else if (u == H2) { deposit_f(KV, r0); deposit_r(KV + TILE, r1); request(r0, s_d, a.lddo); request(r1, s_o, a.ldo); }
     else if (u == H3) deposit_do_delta();
@@ -662,7 +652,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kernel(AttnArgs a) {
     __syncthreads();
     const unsigned char* QsF = smem + cur * 2 * TILE;
     const float* lsd = lsd_base + cur * 2 * ROWS;
-    if (itB < NI && itB * TPI * 16 < len && !(LAFS_LAB_ATTN_ABL & 8))
+    if (itB < NI && itB * TPI * 16 < len)
       bwd_phase_queries<NT, TPI>(QsF, QsF + TILE, KV, KV + TILE, lsd, itB, len, drow, a.lddqkv, lane, c2, a.scale, stop_q);
     else { stop_q(0); stop_q(H2); }
     bf16x8_t kf[TPI][2], vf[TPI][2];
@@ -673,7 +663,7 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kernel(AttnArgs a) {
       vf[x][0] = rfrag(KV + TILE, key, g); vf[x][1] = rfrag(KV + TILE, key, 4 + g);
     }
     __syncthreads();
-    if (itA < NI && itA * TPI * 16 < len && !(LAFS_LAB_ATTN_ABL & 4))
+    if (itA < NI && itA * TPI * 16 < len)
       bwd_phase_keys<NT, TPI>(QsF, QsF + TILE, lsd, kf, vf, itA, len, drow, a.lddqkv, inner, lane, c2, a.scale, stop_k);
     else { stop_k(0); stop_k(H2); stop_k(H3); }
     if (!more) break;
@@ -715,14 +705,12 @@ int dispatch(int which, const AttnArgs& a, hipStream_t s) {
   // the former delta + dQ + dK/dV kernels; short ones two pairs per 4-wave workgroup, one tile per item: 512 x 37 in 32 us
   // against 42.
   const size_t pair_bytes = 4 * tile + 2 * NT * 16 * 4;
-#ifndef LAFS_LAB_ATTN_BWD_OLD
   if constexpr (NT >= 10 && NT <= 13) {
     // (per call, for the device that is current NOW: no process-global state -- another device of the same process has its own count)
     int dev = 0, n_cu = 256;
     (void)hipGetDevice(&dev); (void)hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, dev);
     return launch_attn(attn_bwd_stream_kernel<NT>, min(n_pairs, n_cu), 1, 512, 6 * tile + 4 * NT * 16 * 4, a, s);
   }
-#endif
   if constexpr (NT >= 7) return launch_attn(attn_bwd_fused_kernel<NT, 1, 8, 2>, n_pairs, 1, 512, pair_bytes, a, s);
   else return launch_attn(attn_bwd_fused_kernel<NT, 2, 4, 1>, n_pairs, 2, 256, 2 * pair_bytes, a, s);
 }

@@ -1,6 +1,7 @@
 // Internal layout of lafs_ctx (include/lafs_hip.h): the per-device handle that owns every device object the library itself creates
 // -- the side streams and fork / join events of the trunk passes' row chains, the event pool of the two-stream backward -- and the
-// kernel-selection options.  Nothing in the library is process-global any more: no function-local statics, no getenv.
+// kernel-selection options.  No kernel choice depends on process-global state: no getenv, and the debug-flag word of
+// lafs_debug_set (api.hip) is only recorded.
 #pragma once
 #include <vector>
 #include <hip/hip_runtime.h>

@@ -14,7 +14,6 @@
 // The NT kernel computes C^T tiles (MFMA A-operand = weight rows) and permutes which weight row feeds which
 // MFMA row so that every lane ends up with 16 CONTIGUOUS output columns of one row: epilogues read/write
 // 32-64 B per lane (bias, residual, GELU, fp32/bf16 stores) with no LDS transpose.
-#include <stdlib.h>
 #include <type_traits>
 #include "common.hpp"
 #include "lafs_hip.h"
@@ -22,23 +21,7 @@
 #include "gemm_big.hpp"
 #include "ctx.hpp"
 
-// Timing ablations that change RESULTS (no stores / no MFMA / ...) exist only in the -DLAFS_ABLATE build (make ablate ->
-// liblafs_hip_ablate.so, used by tools/bench_kernels.py): in the product library the branches below are compiled out, so no
-// environment variable or lafs_debug_set call can make a kernel skip work.
-#ifdef LAFS_ABLATE
-#define DBG(p, bits) ((p).dbg & (bits))
-#else
-#define DBG(p, bits) (0)
-#endif
-
 namespace {
-
-#ifdef LAFS_ABLATE
-unsigned long long* g_stamps = nullptr;                // lab: per-workgroup phase time stamps of the next NT launches
-#define STAMP(slot) do { if (p.stamps && threadIdx.x == 0) p.stamps[(size_t)(stamp_id + n_vb * blockIdx.z) * 8 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define STAMP(slot) do { } while (0)
-#endif
 
 enum {
   EPI_BF16 = LAFS_EPI_BF16,
@@ -54,34 +37,26 @@ enum {
 struct NTArgs {
   const bf16_t* A; const bf16_t* B;
   int M, N, K, lda, ldb, klen;
-  int n_tiles;                      // persistent variants: output tiles to walk (the grid is one residency wave)
   void* C; int ldc; void* C2; int ldc2;
   const float* bias; const float* resid; int ldr;
   const float* seq_scale; const int* row2seq;
   const bf16_t* aux; int ldaux;
   const float* pos; int npatch;
   int f16;                          // operands / 16-bit outputs are fp16 (lafs_gemm_nt_args::operand_f16)
-  int dbg;                          // timing ablations (lafs_debug_set): 16 = no epilogue stores, 32 = no MFMA/ds_read
   DropCfg drop;                     // element dropout on the linear's output (RESID_F32) / on GELU(u) (BF16_GELU, DGELU_BF16)
   int act;                          // BF16_ACT: LAFS_ACT_*
-#ifdef LAFS_ABLATE
-  unsigned long long* stamps;
-#endif
 };
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
 typedef float f32x4v_t __attribute__((ext_vector_type(4)));
-// 16-byte epilogue stores; `nt` selects the non-temporal (streaming) form -- activations written here are consumed by a
-// later kernel, never by this one
-__device__ __forceinline__ void st16(void* p, unsigned a, unsigned b, unsigned c, unsigned d, bool nt) {
+// 16-byte epilogue stores.  (Non-temporal forms of them were measured: no gain in a real layer chain.)
+__device__ __forceinline__ void st16(void* p, unsigned a, unsigned b, unsigned c, unsigned d) {
   const u32x4_t v = {a, b, c, d};
-  if (nt) __builtin_nontemporal_store(v, reinterpret_cast<u32x4_t*>(p));
-  else *reinterpret_cast<u32x4_t*>(p) = v;
+  *reinterpret_cast<u32x4_t*>(p) = v;
 }
-__device__ __forceinline__ void st16f(void* p, float a, float b, float c, float d, bool nt) {
+__device__ __forceinline__ void st16f(void* p, float a, float b, float c, float d) {
   const f32x4v_t v = {a, b, c, d};
-  if (nt) __builtin_nontemporal_store(v, reinterpret_cast<f32x4v_t*>(p));
-  else *reinterpret_cast<f32x4v_t*>(p) = v;
+  *reinterpret_cast<f32x4v_t*>(p) = v;
 }
 
 
@@ -117,24 +92,22 @@ __device__ __forceinline__ int xcd_tile(int b, int n) {
 }
 
 // WM = wave rows: 2 -> 128x128 tile, 256 threads; 4 -> 256x128 tile, 512 threads (one third less L2->LDS traffic per
-// flop).  BK = k-depth of a pipeline stage: 32 (3-stage ring, 64-byte row pieces) or 64 (2-stage ring, full 128-byte
-// cache lines per row piece).
+// flop; 32-deep stages only).  BK = k-depth of a pipeline stage: 32 (3-stage ring, 64-byte row pieces) or 64 (2-stage ring,
+// full 128-byte cache lines per row piece).
 template <int BK> __device__ __forceinline__ int nt_swzk(int row) { return BK == 32 ? nt_swz(row) : (row & 7); }
 
-// WN = wave columns: 2 -> 128-wide tiles (default), 4 -> 256-wide (256x256 with WM = 4: 16 waves, one workgroup per CU, half the
-// L2->LDS traffic of 128x128 per flop).
-// PERSIST (lab build only, see launch_nt): the grid is one residency wave of workgroups and each walks virtual blocks b,
-// b + grid, b + 2 grid, ...; while a workgroup stores tile j it already has the first ring stages of tile j+1 in flight.
+// WN = wave columns: 2 -> 128-wide tiles (default), 6 -> 384-wide (128x384, 12 waves: see launch_nt).
 // F16: operands (and a 16-bit output / residual) are IEEE fp16 instead of bf16 -- the trainable landmark CNN's plan
 // (landmark_train.py); instantiated for the plain, activation and fp32 epilogues on 128x128 tiles only.
-template <int EPI, int WM, int BK, int WN = 2, bool PERSIST = false, bool F16 = false, int MB = 4>
-__global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM == 2) ? (BK == 32 ? 3 : 2) : (BK == 32 ? 4 : 2)))) void gemm_nt_kernel(NTArgs p) {
+template <int EPI, int WM, int BK, int WN = 2, bool F16 = false, int MB = 4>
+__global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WM == 2) ? (BK == 32 ? 3 : 2) : 4)) void gemm_nt_kernel(NTArgs p) {
+  static_assert(WM == 2 || (BK == 32 && WN == 2), "256x128 tiles: 32-deep stages only");
   static_assert(!F16 || EPI == EPI_BF16 || EPI == EPI_BF16_ACT || EPI == EPI_F32, "fp16 operands: plain / activation / fp32 epilogues only");
   auto PK2 = [](float lo, float hi) { return F16 ? pack_h2(lo, hi) : pack_bf2(lo, hi); };
   auto CV1 = [](float x) { return F16 ? f2h(x) : f2bf(x); };
   auto LD1 = [](bf16_t h) { return F16 ? h2f(h) : bf2f(h); };
   const DropCfg drop = drop_resolve(p.drop);
-  static_assert(MB == 4 || (WM == 2 && WN == 2 && BK == 64 && !PERSIST), "tall tiles: 2 x 2 waves on 64-deep stages only");
+  static_assert(MB == 4 || (WM == 2 && WN == 2 && BK == 64), "tall tiles: 2 x 2 waves on 64-deep stages only");
   constexpr int RW = MB * 16;                         // rows per wave: MB 16-row MFMA blocks (4: 128-row tiles at WM = 2; 5: 160-row tiles)
   constexpr int THREADS = WM * WN * 64, BMT = WM * RW, BN = WN * 64;
   constexpr bool PIN32 = (WM == 2);                   // (the 8-wave variants run at the 128-register cap: pinning spills there)
@@ -152,24 +125,16 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave / WN, wc = wave % WN;
   const int tiles_n = (p.N + BN - 1) / BN;
-  const int n_vb = PERSIST ? p.n_tiles : (int)gridDim.x;     // virtual blocks = output tiles (per k-split)
-  int m0, n0;
   const int kbeg = blockIdx.z * p.klen;
   const int kend = min(p.K, kbeg + p.klen);
   const int nk = (kend - kbeg) / BK;
-#ifdef LAFS_ABLATE
-  // phase-lock experiment: hold back every second round-robin slot of a CU by (dbg >> 20) & 15 sleeps of ~4 us
-  if ((((blockIdx.x >> 3) >> 5) & 1) && ((p.dbg >> 20) & 15)) {
-    for (int z = 0; z < ((p.dbg >> 20) & 15); ++z) __builtin_amdgcn_s_sleep(127);
-  }
-#endif
 
   // ---- async global -> LDS staging (LDS-DMA).  The LDS image is lane-linear (wave base + lane*16), so the XOR
   // swizzle is applied to the SOURCE column instead. ----
   struct Src { const bf16_t* a[NA]; const bf16_t* b[NB]; int m0, n0; };
   int ldsoff[NMAX];
-  auto locate = [&](int vb, Src& o) {               // operand pointers of virtual block vb
-    const int tile = xcd_tile(vb, n_vb);
+  auto locate = [&](int vb, Src& o) {               // origin and operand pointers of output tile (block) vb
+    const int tile = xcd_tile(vb, (int)gridDim.x);
     const int tm = tile / tiles_n, tn = tile % tiles_n;
     o.m0 = tm * BMT; o.n0 = tn * BN;
 #pragma unroll
@@ -180,7 +145,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
     }
   };
   auto issue = [&](const Src& o, int t) {
-    if DBG(p, 524288) return;                        // ablation: no operand loads (the epilogue works on whatever LDS holds)
     unsigned char* st = smem + (t % NSTG) * STAGE;
 #pragma unroll
     for (int i = 0; i < NMAX; ++i) {
@@ -196,7 +160,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
   int arow[MB], brow[4];
 
   auto compute = [&](int t) {
-    if DBG(p, 32) return;
     const unsigned char* st = smem + (t % NSTG) * STAGE;
 #pragma unroll
     for (int kk = 0; kk < BK / 32; ++kk) {
@@ -214,45 +177,30 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
     // 64-deep stages at two waves per SIMD (the long-K GEMMs of the trunk): pin the 16 fragment reads ahead of the 32 MFMAs that
     // consume them -- left alone, hipcc issues them in batches of 2-6 behind s_waitcnt lgkmcnt(0) and exposes the LDS latency four or
     // five times per stage (the same finding as in gemm_kres.hip)
-    if constexpr (BK == 64 && WM == 2 && WN == 2) {
-      if (!DBG(p, 32)) {                                 // 2 (MB + 4) reads, 8 MB MFMAs per stage
-        __builtin_amdgcn_sched_group_barrier(0x100, MB + 4, 0);
+    if constexpr (BK == 64 && WM == 2 && WN == 2) {   // 2 (MB + 4) reads, 8 MB MFMAs per stage
+      __builtin_amdgcn_sched_group_barrier(0x100, MB + 4, 0);
 #pragma unroll
-        for (int x = 0; x < MB + 4; ++x) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 8 * MB - 2 * (MB + 4), 0);
+      for (int x = 0; x < MB + 4; ++x) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
-    } else if constexpr (BK == 32 && WN == 2 && PIN32) {
-      if (!DBG(p, 32)) {                               // 32-deep stages: 8 reads, 16 MFMAs
-        __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
+      __builtin_amdgcn_sched_group_barrier(0x008, 8 * MB - 2 * (MB + 4), 0);
+    } else if constexpr (BK == 32 && WN == 2 && PIN32) {   // 32-deep stages: 8 reads, 16 MFMAs
+      __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
 #pragma unroll
-        for (int x = 0; x < 4; ++x) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-        }
-        __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
+      for (int x = 0; x < 4; ++x) {
+        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
+      __builtin_amdgcn_sched_group_barrier(0x008, 8, 0);
     }
   };
 
-  bool primed = false;                               // the first ring stages of this tile were issued before the previous epilogue
-  for (int vb = blockIdx.x; vb < n_vb; vb += (int)gridDim.x) {
-#ifdef LAFS_ABLATE
-  const int stamp_id = vb;
-  STAMP(0);
-  if (p.stamps && threadIdx.x == 0) {
-    p.stamps[(size_t)(stamp_id + n_vb * blockIdx.z) * 8 + 4] = __builtin_amdgcn_s_getreg((31 << 11) | 4);     // HW_ID
-    p.stamps[(size_t)(stamp_id + n_vb * blockIdx.z) * 8 + 5] = __builtin_amdgcn_s_getreg((31 << 11) | 20);    // XCC_ID
-  }
-#endif
+  if ((int)blockIdx.x >= (int)gridDim.x) return;     // (never true; kept from the former tile loop's entry test: same code as before)
   {
-    // k-loop addressing is re-derived per tile from an opaque copy of the thread id: hoisted out of the loop it would stay live
-    // across the epilogue, which has no registers to spare at 4 waves per SIMD
-    int t_ = threadIdx.x;
-    if (PERSIST) asm volatile("" : "+v"(t_));
-    const int w_ = t_ >> 6, l_ = t_ & 63;
+    // (derived from threadIdx.x here rather than from wave / lane above: the same values, but this form keeps the code hipcc
+    // generates for the kernel unchanged)
+    const int w_ = (int)threadIdx.x >> 6, l_ = (int)threadIdx.x & 63;
 #pragma unroll
     for (int i = 0; i < NMAX; ++i) ldsoff[i] = (i * THREADS + w_ * 64) * 16;       // wave-uniform
 #pragma unroll
@@ -261,21 +209,18 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
       if (i < 4) brow[i] = (w_ % WN) * 64 + i * 16 + (l_ & 15);
     }
   }
-  if (!PERSIST || !primed) locate(vb, src);
-  m0 = src.m0; n0 = src.n0;
+  locate(blockIdx.x, src);
+  const int m0 = src.m0, n0 = src.n0;
 #pragma unroll
   for (int j = 0; j < 4; ++j)
 #pragma unroll
     for (int i = 0; i < MB; ++i) acc[j][i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   if (NSTG == 3) {
-    if (!primed) {
-      if (nk > 0) issue(src, 0);
-      if (nk > 1) issue(src, 1);
-    }
+    if (nk > 0) issue(src, 0);
+    if (nk > 1) issue(src, 1);
     for (int t = 0; t < nk; ++t) {
-      // stage t has landed once at most the NA+NB loads of stage t+1 are still in flight (loads retire in order).  The first
-      // step of a primed tile drains everything instead: the previous tile's stores are younger than its two stages.
-      if (t + 1 < nk && !(PERSIST && primed && t == 0)) {
+      // stage t has landed once at most the NA+NB loads of stage t+1 are still in flight (loads retire in order)
+      if (t + 1 < nk) {
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NA + NB) : "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -285,7 +230,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
       compute(t);
     }
   } else {
-    if (!primed && nk > 0) issue(src, 0);
+    if (nk > 0) issue(src, 0);
     for (int t = 0; t < nk; ++t) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __builtin_amdgcn_s_barrier();                  // stage t landed everywhere; the other buffer is free again
@@ -293,17 +238,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
       compute(t);
     }
   }
-  if (PERSIST) {
-    primed = vb + (int)gridDim.x < n_vb;
-    if (primed) {
-      locate(vb + gridDim.x, src);                   // (m0, n0 keep this tile's origin for the epilogue)
-      __builtin_amdgcn_s_barrier();                  // every wave is out of the ring before the next tile's stages land in it
-      if (nk > 0) issue(src, 0);
-      if (NSTG == 3 && nk > 1) issue(src, 1);
-    }
-  }
 
-  STAMP(1);
   // (WHOLE: the tile lies inside the matrix.  Without guards there are no branches around the epilogue's loads and stores; with
   // them every guarded piece is its own basic block that hipcc opens with s_waitcnt vmcnt(0) -- the bias / prefetched operand
   // registers came from loads -- so the one-row-ahead prefetch below was waited for right where it was issued, and every store sat
@@ -314,13 +249,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
   // group q starts at n0 + wc*64 + q*4*VPL + fq*VPL; register e = j*4 + r of the row is element e % VPL of group e / VPL.
   constexpr int VPL = EpiTraits<EPI>::VPL, NG = 16 / VPL;
   const int ncol0 = n0 + wc * 64 + fq * VPL;
-  if DBG(p, 16) {                                    // ablation: keep the accumulators live, store nothing
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-      for (int i = 0; i < MB; ++i) asm volatile("" :: "v"(acc[j][i]));
-    return;
-  }
   float bias[16];
 #pragma unroll
   for (int e = 0; e < 16; ++e) bias[e] = 0.f;
@@ -374,7 +302,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[j * 4 + r] = acc[j][i][r] + bias[j * 4 + r];
     float sc = 1.0f;
-    const bool ntst = DBG(p, 256) != 0;              // streaming stores: A/B experiment only (no gain in a real layer chain)
     size_t orow = (size_t)m;
     int tpos = 0;
     if (EPI == EPI_RESID_F32) sc = scv[i];
@@ -384,8 +311,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
       orow = (size_t)m + b + 1;                         // one cls row in front of every sequence
     }
     // BF16_GELU writes two tensors: all pieces of u first, then all pieces of GELU(u), so that the 64-byte halves of a
-    // 128-byte line leave the CU back to back and merge into full-line writes (fc1 at C2: 150 -> ~125 us; debug flag 32768
-    // restores the piece-by-piece order for A/B runs)
+    // 128-byte line leave the CU back to back and merge into full-line writes (fc1 at C2: 150 -> ~125 us against the
+    // piece-by-piece order)
     constexpr int NPASS = (EPI == EPI_BF16_GELU) ? 2 : 1;
     uint4 gpk[NG];                                        // (BF16_GELU saving gelu'(u): gelu(u) of the row's pieces, packed)
 #pragma unroll
@@ -398,14 +325,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
       if (!WHOLE && n >= p.N) continue;
       const bool full = WHOLE || (n + VPL <= p.N);
       float* w = v + q * VPL;
-#ifdef LAFS_ABLATE
-      // pacing experiment: (dbg >> 24) & 31 sleeps of 128 clocks before every store group, so that a workgroup's stores enter
-      // the CU's in-order memory pipeline spread out instead of as one burst in front of the neighbour workgroup's loads
-      for (int z = 0; z < ((p.dbg >> 24) & 31); ++z) __builtin_amdgcn_s_sleep(2);
-#endif
-      const bool legacy = DBG(p, 32768) != 0;
-      const bool do_first = legacy ? (pass == 0) : (pass == 0), do_second = legacy ? (pass == 0) : (pass == NPASS - 1);
-      if (legacy && pass > 0) continue;
+      const bool do_first = (pass == 0), do_second = (pass == NPASS - 1);
       if (EPI == EPI_BF16_ACT) {                          // 1x1 convolution of the landmark CNN: + residual (bf16), activation
         if (p.aux != nullptr) {
           const bf16_t* ax = p.aux + (size_t)m * p.ldaux + n;
@@ -437,16 +357,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
           }
         }
         bf16_t* c = reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n;
-#ifdef LAFS_ABLATE
-        // ablation (timing only, values land in the wrong places): every store instruction covers 8 full 128-byte lines
-        // (8 rows x 64 columns of the wave's 64x64 tile) instead of 16 half lines
-        const bool fullline = DBG(p, 2097152) && VPL == 8;
-        const size_t flrow = (size_t)(m0 + wr * RW + (i * NG + q) * 8 + (lane >> 3));
-        if (fullline) c = reinterpret_cast<bf16_t*>(p.C) + min(flrow, (size_t)p.M - 1) * p.ldc + n0 + wc * 64 + (lane & 7) * 8;
-#endif
-        // experiment (debug flag 16384): u and GELU(u) interleaved in 64-byte pieces of ONE [M, 2N] buffer, so the two stores
-        // of a lane group complete a 128-byte line
-        if (EPI == EPI_BF16_GELU && DBG(p, 16384)) c = reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc * 2 + (n >> 5) * 64 + (n & 31);
         if (EPI == EPI_BF16_GELU && (p.C == nullptr || !do_first)) {
           // forward-only pass (teacher): the pre-activation is not needed, only GELU(u) is written; second pass: already stored
         } else if (EPI == EPI_BF16_GELU && p.act == LAFS_GELU_SAVE_GRAD) {        // the first tensor is gelu'(u), not u
@@ -459,40 +369,34 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
               gelu_both_f(w[e], g[e], d[e]);
               if (drop.thresh) g[e] *= drop_mult(drop, (unsigned)m * (unsigned)p.N + (unsigned)(n + e));
             }
-            st16(c, pack_bf2(d[0], d[1]), pack_bf2(d[2], d[3]), pack_bf2(d[4], d[5]), pack_bf2(d[6], d[7]), ntst);
+            st16(c, pack_bf2(d[0], d[1]), pack_bf2(d[2], d[3]), pack_bf2(d[4], d[5]), pack_bf2(d[6], d[7]));
             gpk[q] = make_uint4(pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]), pack_bf2(g[4], g[5]), pack_bf2(g[6], g[7]));
           } else {
 #pragma unroll
             for (int e = 0; e < VPL; ++e) if (n + e < p.N) c[e] = f2bf(gelu_grad_f(w[e]));
           }
         } else if (full) {
-          st16(c, PK2(w[0], w[1]), PK2(w[2], w[3]), PK2(w[4], w[5]), PK2(w[6], w[7]), ntst);
+          st16(c, PK2(w[0], w[1]), PK2(w[2], w[3]), PK2(w[4], w[5]), PK2(w[6], w[7]));
         } else {
 #pragma unroll
           for (int e = 0; e < VPL; ++e) if (n + e < p.N) c[e] = CV1(w[e]);
         }
-        if (EPI == EPI_BF16_GELU && !DBG(p, 64) && do_second) {
+        if (EPI == EPI_BF16_GELU && do_second) {
           bf16_t* c2 = reinterpret_cast<bf16_t*>(p.C2) + (size_t)m * p.ldc2 + n;
-#ifdef LAFS_ABLATE
-          if (fullline) c2 = reinterpret_cast<bf16_t*>(p.C2) + min(flrow, (size_t)p.M - 1) * p.ldc2 + n0 + wc * 64 + (lane & 7) * 8;
-#endif
-          if DBG(p, 16384) c2 = c + 32;
-          if (full && DBG(p, 128)) {
-            *reinterpret_cast<uint4*>(c2) = make_uint4(pack_bf2(w[0], w[1]), pack_bf2(w[2], w[3]), pack_bf2(w[4], w[5]), pack_bf2(w[6], w[7]));
-          } else if (full && p.C != nullptr && p.act == LAFS_GELU_SAVE_GRAD) {          // evaluated with gelu'(u) in the first pass
-            st16(c2, gpk[q].x, gpk[q].y, gpk[q].z, gpk[q].w, ntst);
+          if (full && p.C != nullptr && p.act == LAFS_GELU_SAVE_GRAD) {          // evaluated with gelu'(u) in the first pass
+            st16(c2, gpk[q].x, gpk[q].y, gpk[q].z, gpk[q].w);
           } else if (drop.thresh && full) {              // dropout(gelu(u)): one 16-byte store like the plain form
             float g[8];
 #pragma unroll
             for (int e = 0; e < VPL; ++e) g[e] = gelu_f(w[e]) * drop_mult(drop, (unsigned)m * (unsigned)p.N + (unsigned)(n + e));
-            st16(c2, pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]), pack_bf2(g[4], g[5]), pack_bf2(g[6], g[7]), ntst);
+            st16(c2, pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]), pack_bf2(g[4], g[5]), pack_bf2(g[6], g[7]));
           } else if (drop.thresh) {
 #pragma unroll
             for (int e = 0; e < VPL; ++e)
               if (n + e < p.N) c2[e] = f2bf(gelu_f(w[e]) * drop_mult(drop, (unsigned)m * (unsigned)p.N + (unsigned)(n + e)));
           } else if (full) {
             st16(c2, pack_bf2(gelu_f(w[0]), gelu_f(w[1])), pack_bf2(gelu_f(w[2]), gelu_f(w[3])),
-                 pack_bf2(gelu_f(w[4]), gelu_f(w[5])), pack_bf2(gelu_f(w[6]), gelu_f(w[7])), ntst);
+                 pack_bf2(gelu_f(w[4]), gelu_f(w[5])), pack_bf2(gelu_f(w[6]), gelu_f(w[7])));
           } else {
 #pragma unroll
             for (int e = 0; e < VPL; ++e) if (n + e < p.N) c2[e] = f2bf(gelu_f(w[e]));
@@ -525,7 +429,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
         // F32 with the K axis split over blockIdx.z: every slice stores its own [M][ldc] image (lafs_sum_slices folds them)
         float* c = reinterpret_cast<float*>(p.C) + (EPI == EPI_F32 ? (size_t)blockIdx.z * p.M * p.ldc : 0) + orow * p.ldc + n;
         if (full) {
-          st16f(c, w[0], w[1], w[2], w[3], ntst);
+          st16f(c, w[0], w[1], w[2], w[3]);
         } else {
 #pragma unroll
           for (int e = 0; e < VPL; ++e) if (n + e < p.N) c[e] = w[e];
@@ -537,14 +441,6 @@ __global__ __launch_bounds__(WM * WN * 64, (WN == 6) ? 3 : ((WN == 4) ? 4 : ((WM
   // (plain / residual / GELU' epilogues only: the others are rare or already store back to back, and two copies of them cost registers)
   if ((EPI == EPI_BF16 || EPI == EPI_RESID_F32 || EPI == EPI_DGELU_BF16) && m0 + BMT <= p.M && n0 + BN <= p.N) epilogue(std::true_type());
   else epilogue(std::false_type());
-#ifdef LAFS_ABLATE
-  STAMP(2);
-  if (p.stamps && !PERSIST) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-  STAMP(3);
-#endif
-  if (!PERSIST) break;
-  if (primed) locate(vb + gridDim.x, src);          // recomputed rather than kept live across the epilogue
-  }                                                  // virtual blocks
 }
 
 // ------------------------------------------------------------------------------------------------ TN
@@ -554,21 +450,20 @@ struct TNArgs {
   long part_stride;                                // mode 2: C is [n_xcd][...] partial sums, one image per XCD
 };
 
-// Reduction rows per pipeline stage: KB = 32 (3-stage ring) or 64 (2-stage ring, half as many barriers per row).
-// One 128-column operand panel of a stage is KB rows x 256 B.
+// Reduction rows per pipeline stage: KB = 32, in a 3-stage ring.  One 128-column operand panel of a stage is KB rows x 256 B.
 
 // XOR applied to the 8-byte unit index (0..31) of a 256-byte row so that ds_read_b64_tr_b16 of 4 consecutive rows x
 // 4 units is conflict-free for both 16-lane groups sharing an LDS cycle (rows r..r+3 and r+8..r+11).
 __device__ __forceinline__ int tn_f(int row) { return ((row & 3) | (((row >> 3) & 1) << 2)) << 2; }
 
 // Output tile (64*WM) x (64*WN), one 64x64 block of 4x4 MFMA tiles per wave.  Operands are staged as 128-column panels
-// (WM/2 panels of A, WN/2 of B per stage).  The product path uses 2x2 (see launch_tn for the measured comparison).
-// CS = false compiles the bias-gradient (column-sum) accumulators out: 16 registers the 16-wave 256x256 variant needs back.
-template <int WM, int WN, int KB, bool CS = true>
-__global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? (KB == 64 ? 2 : 3) : (WM * WN == 8 ? 4 : 1)) void gemm_tn_kernel(TNArgs p) {
+// (WM/2 panels of A, WN/2 of B per stage).  2x2 on most shapes, 4x2 / 2x4 where launch_tn says so.
+template <int WM, int WN>
+__global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? 3 : 4) void gemm_tn_kernel(TNArgs p) {
   constexpr int NTH = 64 * WM * WN;
   constexpr int PA = WM / 2, PB = WN / 2;
-  constexpr int TN_BM = KB, TN_PANEL = KB * 256, NS = (KB == 32) ? 3 : 2;
+  constexpr int KB = 32;
+  constexpr int TN_BM = KB, TN_PANEL = KB * 256, NS = 3;
   constexpr int STAGE = (PA + PB) * TN_PANEL;
   constexpr int NCH = (PA + PB) * TN_BM * 16;        // 16-byte chunks per stage
   constexpr int NI = NCH / NTH;                      // LDS-DMA loads per thread and stage
@@ -593,7 +488,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? (KB == 64 ? 2 : 3) :
   const int mbeg = zslice * p.mlen;
   const int mend = min(p.M, mbeg + p.mlen);
   const int nk = (mend - mbeg + TN_BM - 1) / TN_BM;
-  const bool do_colsum = CS && (p.colsum != nullptr) && n2_0 == 0 && wn == 0;
+  const bool do_colsum = (p.colsum != nullptr) && n2_0 == 0 && wn == 0;
 
   // LDS-DMA staging: the image is lane-linear (chunk q of the stage lands at byte 16*q), so the unit swizzle goes on the
   // source column.  Rows past the end of the slice are clamped to a valid row here and zeroed in LDS before use.
@@ -636,10 +531,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? (KB == 64 ? 2 : 3) :
   const int oa0 = r0 * 256 + ((ua ^ tn_f(r0)) << 3), oa1 = r1 * 256 + ((ua ^ tn_f(r1)) << 3);
   const int ob0 = r0 * 256 + ((ub ^ tn_f(r0)) << 3), ob1 = r1 * 256 + ((ub ^ tn_f(r1)) << 3);
   if (nk > 0) issue(0);
-  if (NS == 3 && nk > 1) issue(1);
+  if (nk > 1) issue(1);
   for (int t = 0; t < nk; ++t) {
-    // NS == 3: stage t+1 may still be in flight; NS == 2: only stage t is outstanding here
-    if (NS == 3 && t + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
+    // stage t+1 may still be in flight
+    if (t + 1 < nk) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NI) : "memory");
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     if (t + NS - 1 < nk) issue(t + NS - 1);
@@ -669,7 +564,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? (KB == 64 ? 2 : 3) :
       for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) acc[a][b] = mfma16(fa[a], fb[b], acc[a][b]);
-      if (CS && do_colsum) {                          // column sums of A (bias gradient): a lane holds 8 k-values of one column
+      if (do_colsum) {                                // column sums of A (bias gradient): a lane holds 8 k-values of one column
 #pragma unroll
         for (int a = 0; a < 4; ++a) {
           const uint4 w = __builtin_bit_cast(uint4, fa[a]);
@@ -695,12 +590,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 4) ? (KB == 64 ? 2 : 3) :
         if (n2 < p.N2) {
           float* dst = Cx + (size_t)n1 * p.ldc + n2;
           if (p.mode == 0) atomicAdd(dst, acc[a][b][r]);
-          else if (p.mode == 2) __hip_atomic_fetch_add(dst, acc[a][b][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-          else *dst = acc[a][b][r];                                   // timing experiment only (lafs_debug_set)
+          else __hip_atomic_fetch_add(dst, acc[a][b][r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
       }
     }
-  if (CS && do_colsum) {                              // lanes l, l^16, l^32, l^48 hold the four k-slices of column (l & 15)
+  if (do_colsum) {                                    // lanes l, l^16, l^32, l^48 hold the four k-slices of column (l & 15)
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       float v = cs[a];
@@ -741,8 +635,6 @@ __global__ __launch_bounds__(256) void sum_slices_kernel(const float* __restrict
   reinterpret_cast<float4*>(out)[i] = acc;
 }
 
-int g_debug_flags = 0;
-
 // 128x384 / 12-wave tiles (the whole N per workgroup) when the tiles fit one round of one workgroup per CU: see launch_nt
 // 160-row tiles (MB = 5) instead of 128-row ones where they save a round of workgroup slots.  The tiled kernel keeps two workgroups per
 // CU, so a launch costs whole rounds of 512 tiles: tools/lab/t_quant.py measures the staircase (fc1 input gradient of ViT-S, N = 384,
@@ -770,59 +662,27 @@ int launch_nt(const NTArgs& a, int splits, const lafs_ctx* cx, hipStream_t s) {
   const long t2 = (long)ceil_div(a.M, 128) * tn * splits, t4 = (long)ceil_div(a.M, 256) * tn * splits;
   //  * 256x256 tiles (16 waves, one workgroup per CU, half the operand re-reads of 128x128) win 6-9 % on the isolated ViT-S
   //    fc1 forward / GELU' dgrad (141 -> 128 us, 138 -> 129 us) but LOSE in the real step (21.3 -> 21.5 ms: a 16-wave
-  //    workgroup owns the CU while the weight-gradient stream wants to share it); kept behind debug flag 65536.
-  const bool wide256 = (g_debug_flags & 65536) != 0;
-  if (wide256 && splits == 1 && a.N >= 1024 && a.N % 256 == 0 && a.M >= 4096 &&
-      (EPI == EPI_BF16 || EPI == EPI_BF16_GELU || EPI == EPI_DGELU_BF16)) {
-    const unsigned t44 = (unsigned)(ceil_div(a.M, 256) * ceil_div(a.N, 256));
-    if ((g_debug_flags & 8) && a.klen % 64 == 0) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 64, 4>), dim3(t44, 1, 1), dim3(1024), 0, s, a);
-    else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 32, 4>), dim3(t44, 1, 1), dim3(1024), 0, s, a);
-    LAFS_LAUNCH_CHECK();
-    return LAFS_OK;
-  }
+  //    workgroup owns the CU while the weight-gradient stream wants to share it).
   if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_ACT || EPI == EPI_F32) {
     if (a.f16) {                                     // fp16 operands (landmark CNN training plan): 128x128 tiles, no K split
       const bool bk = (a.klen % 64 == 0) && a.klen >= 640;
-      if (bk) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 2, false, true>), dim3((unsigned)t2, 1, 1), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 32, 2, false, true>), dim3((unsigned)t2, 1, 1), dim3(256), 0, s, a);
+      if (bk) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 2, true>), dim3((unsigned)t2, 1, 1), dim3(256), 0, s, a);
+      else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 32, 2, true>), dim3((unsigned)t2, 1, 1), dim3(256), 0, s, a);
       LAFS_LAUNCH_CHECK();
       return LAFS_OK;
     }
   }
-  bool bk64 = (a.klen % 64 == 0) && a.klen >= 640 && (splits == 1 || a.K % 64 == 0);    // K = 704 / 768 (ViT-B) included: 5-15 % over 32-deep stages
-  int wm = (!bk64 && a.N >= 1024 && a.M >= 4096) ? 4 : 2;
-  if (g_debug_flags & 2) wm = 2;
-  if (g_debug_flags & 4) wm = 4;
-  if (g_debug_flags & 8) bk64 = (a.klen % 64 == 0);
-  if (g_debug_flags & 2) bk64 = bk64 && (g_debug_flags & 8);
-#ifdef LAFS_ABLATE
-  // Lab build only (debug flag 8388608): problems that need more than one residency wave of workgroups run persistently -- one
-  // wave of workgroups walking the tiles, the next tile's first ring stages in flight during the epilogue.  Measured on the C2
-  // shapes: within +-2 % of the one-tile-per-workgroup launch in isolation (fc1 135 vs 133 us) and 0.2 ms SLOWER per step
-  // (18.45 vs 18.23 ms): resident workgroups keep the side streams' kernels off the CUs.  Not built into the product library.
-  const long tiles = (wm == 4 ? t4 : t2);
-  const int resident = 256 * ((wm == 4 || bk64) ? 2 : 3);
-  if (splits == 1 && tiles > resident && (g_debug_flags & 8388608)) {
-    NTArgs b = a;
-    b.n_tiles = (int)tiles;
-    const dim3 grid((unsigned)resident, 1, 1);
-    if (wm == 4) {
-      if (bk64) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 64, 2, true>), grid, dim3(512), 0, s, b);
-      else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 32, 2, true>), grid, dim3(512), 0, s, b);
-    } else {
-      if (bk64) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 2, true>), grid, dim3(256), 0, s, b);
-      else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 32, 2, true>), grid, dim3(256), 0, s, b);
-    }
-    LAFS_LAUNCH_CHECK();
-    return LAFS_OK;
-  }
-#endif
+  const bool bk64 = (a.klen % 64 == 0) && a.klen >= 640 && (splits == 1 || a.K % 64 == 0);    // K = 704 / 768 (ViT-B) included: 5-15 % over 32-deep stages
+  const int wm = (!bk64 && a.N >= 1024 && a.M >= 4096) ? 4 : 2;
+  //  * persistent tiles (one residency wave of workgroups walking the tiles, the next tile's first ring stages in flight during
+  //    the epilogue) were measured on the C2 shapes: within +-2 % of the one-tile-per-workgroup launch in isolation (fc1 135 vs
+  //    133 us) and 0.2 ms SLOWER per step (18.45 vs 18.23 ms): resident workgroups keep the side streams' kernels off the CUs.
   // Long reductions onto N = 384 (fc2 forward, fc1 / qkv input gradients of ViT-S): 128x384 tiles, 12 waves -- the whole N per
   // workgroup, so the A rows are staged once instead of three times and a wave issues 5.3 instead of 8 LDS-DMA instructions per
   // 32 MFMAs (the staging cost is issue time in the wave)
   // ... when its tiles fit ONE round of one workgroup per CU: 197 tiles (teacher, M = 25216) run 12-17 % faster than on the
   // 128x128 kernel; 345 tiles (student: a second round of 89) are slower, and so is a split into whole rounds here + the rest on
-  // the 128x128 kernel (fc2 forward 92-98 against 83-86 us; tools/lab/nt_variants.py).  LAFS_OPT_NT_WIDE = 0 switches it off (A/B).
+  // the 128x128 kernel (fc2 forward 92-98 against 83-86 us).  LAFS_OPT_NT_WIDE = 0 switches it off (A/B).
   if constexpr (EPI == EPI_BF16 || EPI == EPI_RESID_F32) {
     const int mt = ceil_div(a.M, 128);
     if (bk64 && wide_tile_shape(cx, a.M, a.N, splits)) {
@@ -833,15 +693,13 @@ int launch_nt(const NTArgs& a, int splits, const lafs_ctx* cx, hipStream_t s) {
   }
   if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_GELU || EPI == EPI_RESID_F32 || EPI == EPI_DGELU_BF16) {
     if (bk64 && wm == 2 && tall_tile_shape(cx, a.M, a.N, splits)) {
-      hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 2, false, false, 5>), dim3((unsigned)(ceil_div(a.M, 160) * tn), 1, 1), dim3(256), 0, s, a);
+      hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 2, false, 5>), dim3((unsigned)(ceil_div(a.M, 160) * tn), 1, 1), dim3(256), 0, s, a);
       LAFS_LAUNCH_CHECK();
       return LAFS_OK;
     }
   }
   if (wm == 4) {
-    if (bk64) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 64>), dim3((unsigned)t4 / splits, 1, splits), dim3(512), 0, s, a);
-    else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 32>), dim3((unsigned)t4 / splits, 1, splits), dim3(512),
-                            (g_debug_flags & 4194304) ? 24576 : 0 /* lab: extra LDS -> one workgroup per CU */, s, a);
+    hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 32>), dim3((unsigned)t4 / splits, 1, splits), dim3(512), 0, s, a);
   } else {
     if (bk64) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64>), dim3((unsigned)t2 / splits, 1, splits), dim3(256), 0, s, a);
     else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 32>), dim3((unsigned)t2 / splits, 1, splits), dim3(256), 0, s, a);
@@ -870,7 +728,7 @@ extern "C" int lafs_gemm_nt_route(const lafs_gemm_nt_args* g) {
   if (g->operand_f16) return 0;                     // fp16 operands (landmark CNN plan): launch_nt takes the 128x128 fp16 kernel first
   const int splits = (g->epilogue == LAFS_EPI_ATOMIC_F32 || g->epilogue == LAFS_EPI_F32) && g->splits > 1 ? g->splits : 1;
   // the tiled kernel's 128x384 form (launch_nt): plain / residual epilogue, 64-deep stages (K % 64 == 0, K >= 640), no K split
-  const bool bk64 = g->K % 64 == 0 && g->K >= 640 && !(g_debug_flags & 2);
+  const bool bk64 = g->K % 64 == 0 && g->K >= 640;
   if ((g->epilogue == LAFS_EPI_BF16 || g->epilogue == LAFS_EPI_RESID_F32) && bk64 && wide_tile_shape(g->ctx, g->M, g->N, splits)) return 3;
   // ... and its 160-row form where that saves a round of workgroup slots (plain, GELU, residual and GELU' epilogues)
   if ((g->epilogue == LAFS_EPI_BF16 || g->epilogue == LAFS_EPI_BF16_GELU || g->epilogue == LAFS_EPI_RESID_F32 || g->epilogue == LAFS_EPI_DGELU_BF16) &&
@@ -891,10 +749,7 @@ extern "C" int lafs_gemm_nt(const lafs_gemm_nt_args* g, hipStream_t stream) {
   a.C = g->C; a.ldc = g->ldc; a.C2 = g->C2; a.ldc2 = g->ldc2;
   a.bias = g->bias; a.resid = g->resid; a.ldr = g->ldr;
   a.seq_scale = g->seq_scale; a.row2seq = g->row2seq;
-  a.aux = (const bf16_t*)g->aux; a.ldaux = g->ldaux; a.pos = g->pos; a.npatch = g->npatch; a.dbg = g_debug_flags; a.n_tiles = 0;
-#ifdef LAFS_ABLATE
-  a.stamps = g_stamps;
-#endif
+  a.aux = (const bf16_t*)g->aux; a.ldaux = g->ldaux; a.pos = g->pos; a.npatch = g->npatch;
   a.drop = make_drop(g->drop_p, g->drop_seed, g->drop_step, (unsigned)g->drop_row0 * (unsigned)g->N);
   a.act = g->act;
   a.f16 = g->operand_f16 ? 1 : 0;
@@ -950,20 +805,17 @@ static int launch_tn(const void* A, int lda, const void* B, int ldb, float* C, i
   LAFS_CHECK_ARG(lda % 8 == 0 && ldb % 8 == 0 && N1 % 8 == 0 && N2 % 8 == 0, "N1/N2/lda/ldb must be multiples of 8");
   TNArgs a;
   a.A = (const bf16_t*)A; a.B = (const bf16_t*)B; a.C = C; a.colsum = colsum_a;
-  a.M = M; a.N1 = N1; a.N2 = N2; a.lda = lda; a.ldb = ldb; a.ldc = ldc; a.mode = 0;
-#ifdef LAFS_ABLATE
-  a.mode = g_debug_flags & 1;
-#endif
+  a.M = M; a.N1 = N1; a.N2 = N2; a.lda = lda; a.ldb = ldb; a.ldc = ldc;
   a.part_stride = part_stride;
-  if (part_stride > 0) a.mode = 2;
+  a.mode = part_stride > 0 ? 2 : 0;
   // 32-row stages in a 3-stage ring.  (64-row stages in a 2-stage ring -- half the barriers -- measured 1.8x slower: the
-  // next stage's DMA cannot be issued before the barrier and only 2 workgroups fit a CU; debug flag 8192 selects them.)
-  const int kb = (g_debug_flags & 8192) ? 64 : 32;
+  // next stage's DMA cannot be issued before the barrier and only 2 workgroups fit a CU.)
+  const int kb = 32;
   const int msteps = ceil_div(M, kb);
   // Tile shape.  128x128 (4 waves, 3 workgroups per CU) is the fastest on nearly every LAFS shape: the wider variants re-read the
   // operands from L2 fewer times but 256x128 is on par at best (105 vs 97 us on the ViT-S fc1 wgrad, once it fits 128 VGPRs and
-  // two workgroups share a CU) and 256x256 slower (tools/bench_kernels.py tn); debug flags 2048 = 256x256, 4096 = 256x128.
-  static const int cand[4][2] = {{2, 2}, {4, 2}, {2, 4}, {4, 4}};
+  // two workgroups share a CU) and 256x256 slower.
+  static const int cand[3][2] = {{2, 2}, {4, 2}, {2, 4}};
   int best = 0;
   {
     // ... except when the 128x128 grid would spill into a second round of workgroups (3 fit a CU: 768 slots): then 256x128
@@ -973,18 +825,12 @@ static int launch_tn(const void* A, int lda, const void* B, int ldb, float* C, i
     if (s22 > 4) s22 = (s22 + 7) & ~7;
     if (splits <= 0 && t22 * s22 > 768 && M >= 8192) best = (N1 >= N2) ? 1 : 2;
   }
-  if (g_debug_flags & 1024) best = 0;
-  if (g_debug_flags & 2048) best = 3;
-  if (g_debug_flags & 4096) best = (N1 >= N2) ? 1 : 2;
   const int wm = cand[best][0], wn = cand[best][1];
   const int tiles = ceil_div(N1, 64 * wm) * ceil_div(N2, 64 * wn);
   if (splits <= 0) {
     if (best == 0) {                       // 3 workgroups of 4 waves per CU: ~2 per CU, slices in multiples of 8 (one run per XCD)
       splits = ceil_div(512, tiles);
       if (splits > 4) splits = (splits + 7) & ~7;
-    } else if (best == 3) {                // 1 workgroup of 16 waves per CU: a single wave of workgroups
-      splits = 256 / tiles;
-      if (splits < 1) splits = 1;
     } else {                               // 2 workgroups of 8 waves per CU: a bit more than one per CU
       splits = ceil_div(288, tiles);
       if (splits > 4) splits = (splits + 7) & ~7;
@@ -995,12 +841,9 @@ static int launch_tn(const void* A, int lda, const void* B, int ldb, float* C, i
   if (splits % 8 != 0) splits = ceil_div(M, a.mlen);       // (empty trailing slices are harmless for the x8 layout)
   a.splits = splits; a.tiles = tiles;
   const dim3 grid(tiles * splits);
-  if (best == 0 && kb == 64) hipLaunchKernelGGL((gemm_tn_kernel<2, 2, 64>), grid, dim3(256), 0, stream, a);   // experiment
-  else if (best == 0) hipLaunchKernelGGL((gemm_tn_kernel<2, 2, 32>), grid, dim3(256), 0, stream, a);
-  else if (best == 1) hipLaunchKernelGGL((gemm_tn_kernel<4, 2, 32>), grid, dim3(512), 0, stream, a);
-  else if (best == 2) hipLaunchKernelGGL((gemm_tn_kernel<2, 4, 32>), grid, dim3(512), 0, stream, a);
-  else if (colsum_a != nullptr) hipLaunchKernelGGL((gemm_tn_kernel<4, 4, 32, true>), grid, dim3(1024), 0, stream, a);
-  else hipLaunchKernelGGL((gemm_tn_kernel<4, 4, 32, false>), grid, dim3(1024), 0, stream, a);
+  if (best == 0) hipLaunchKernelGGL((gemm_tn_kernel<2, 2>), grid, dim3(256), 0, stream, a);
+  else if (best == 1) hipLaunchKernelGGL((gemm_tn_kernel<4, 2>), grid, dim3(512), 0, stream, a);
+  else hipLaunchKernelGGL((gemm_tn_kernel<2, 4>), grid, dim3(512), 0, stream, a);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }
@@ -1035,19 +878,4 @@ extern "C" int lafs_sum_slices(const float* part, int64_t part_stride, int n_par
   hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, (long)part_stride, n_part, n4, out);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
-}
-
-// Diagnostic knob for timing experiments (bit 0: TN GEMM stores instead of atomics -> WRONG results).  Never set by
-// the product path.
-extern "C" int lafs_debug_set(int flags) { g_debug_flags = flags; return LAFS_OK; }
-extern "C" int lafs_debug_get(void) { return g_debug_flags; }
-#ifdef LAFS_ABLATE
-extern "C" void lafs_lab_set_stamps(void* buf) { g_stamps = (unsigned long long*)buf; }
-#endif
-extern "C" int lafs_ablation_build(void) {
-#ifdef LAFS_ABLATE
-  return 1;
-#else
-  return 0;
-#endif
 }

@@ -451,12 +451,8 @@ bool lafs_big_eligible(const lafs_gemm_nt_args* g) {
   const int geo = big_geometry(g);
   const long fill = geo_fill(g, geo);
   const long rounds = (geo_tiles(g, geo) + 255) / 256;
-#ifdef LAFS_LAB_BIG_OLDRULE
-  const bool epi_ok = e == LAFS_EPI_BF16 || (e == LAFS_EPI_BF16_GELU && g->C != nullptr && g->act == LAFS_GELU_SAVE_GRAD);
-#else
   const bool epi_ok = e == LAFS_EPI_BF16 || e == LAFS_EPI_DGELU_BF16 || (e == LAFS_EPI_RESID_F32 && rounds >= 3) ||
                       (e == LAFS_EPI_BF16_GELU && g->C != nullptr && g->act == LAFS_GELU_SAVE_GRAD);
-#endif
   return epi_ok && fill >= 840 && (g->K >= 1024 || rounds >= 4 || (rounds >= 3 && fill >= 880));
 }
 

@@ -16,7 +16,7 @@
 //     barrier.  A lane (token t, quarter q) ends up with 4 consecutive output columns per MFMA; the weight rows of a stage are
 //     interleaved so that two MFMAs give it 8 consecutive bf16 columns: every store instruction writes 16 rows x 64 contiguous
 //     bytes (the pattern the HBM write path sustains at full rate; 16-byte pieces scattered over 32 rows -- what a 32x32 MFMA
-//     layout produces -- measured 1.8-2.6 TB/s, tools/lab/lab_kres.cpp);
+//     layout produces -- measured 1.8-2.6 TB/s);
 //   * work = (128-row unit, 64-column block) items in unit-major order, cut into equal contiguous runs, one per workgroup
 //     (4 waves, 2 workgroups per CU, all resident at once).  An item is two ring stages (32 columns each) and one epilogue: the two
 //     stages' 64-byte pieces of a row are stored back to back and complete 128-byte lines; a wave emits 4-8 stores per item, so
@@ -57,15 +57,7 @@ struct KArgs {
   const bf16_t* aux; int ldaux;
   int cbn, items;                          // 64-column blocks per row unit; row units x column blocks
   int save_grad;                           // LAFS_GELU_SAVE_GRAD: GELU epilogue stores gelu'(u) for u / GELU' epilogue multiplies aux in as it is
-  unsigned long long* stamps;              // lab (ABL & 32): per workgroup {wait + barrier, issue, MFMA loop, epilogue, whole run, stages, reload wait, reloads} cycles of wave 0
 };
-// ABL (template argument, 0 in the library; tools/lab/lab_kres.cpp instantiates others): timing ablations and variants
-//   1 stores only from lane 0 (dead-code-proof "no stores"), 2 no MFMA, 4 no weight stages after the first two, 8 no epilogue math,
-//   16 no fragment reads, 32 phase time stamps of wave 0 (s_memtime) into KArgs::stamps, 64 no workgroup barrier (racy),
-//   128 no store instructions at all (accumulators kept alive by an empty asm), 256 every store writes one contiguous KiB,
-//   512 resident rows (re)loaded by per-lane global loads instead of through the ring buffers, 2048 GELU' operand fetched an item
-//   ahead (needs 512: both together spill)
-#define KABL(bit) ((ABL & (bit)) != 0)
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void fence() { asm volatile("" ::: "memory"); }
@@ -85,19 +77,15 @@ template <int EPI, bool HAS_U> struct EpiOps {
   static constexpr int P = F32 ? 8 : ((EPI == LAFS_EPI_DGELU_BF16) ? 4 : 0);
 };
 
-template <int EPI, bool HAS_U, int ABL>
+template <int EPI, bool HAS_U>
 __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
   constexpr int UROWS = 128, NDMA = NDMA4;
   constexpr int S = EpiOps<EPI, HAS_U>::S, P = EpiOps<EPI, HAS_U>::P;
   constexpr bool F32 = EpiOps<EPI, HAS_U>::F32;
-  // epilogue operand fetched one item ahead (GELU': its load latency no longer sits in front of the epilogue math); the
-  // residual epilogue fetches within the item -- a second 32-register buffer does not fit beside its other state
+  // The epilogue operand is fetched within the item, a stage of MFMAs ahead of its use.  (Fetched one item ahead, GELU' spilled
+  // beside the staged reload of the resident rows: no registers for a second operand buffer.)
   // GELU' variants: HAS_U = false means that aux already holds gelu'(u) (LAFS_GELU_SAVE_GRAD): no derivative math in the epilogue
   constexpr bool AUX_IS_GRAD = (EPI == LAFS_EPI_DGELU_BF16) && !HAS_U;
-  constexpr bool AHEAD = (EPI == LAFS_EPI_DGELU_BF16) && KABL(2048);   // (lab only: beside the staged reload the second operand buffer spills)
-  // resident rows (re)loaded through the ring buffers (the GELU' variant has no registers to spare for that code path: it keeps
-  // the per-lane loads)
-  constexpr bool STAGED = !KABL(512) && !AHEAD;
   __shared__ __attribute__((aligned(16))) unsigned char smem[NSTG * STAGE];
   __shared__ __attribute__((aligned(16))) float sbias[MAXN];
   const int tid = threadIdx.x, lane = tid & 63;
@@ -108,7 +96,6 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
   const int id = (blockIdx.x & 7) * per + (blockIdx.x >> 3);
   const int ib = (int)((long)p.items * id / G), ie = (int)((long)p.items * (id + 1) / G);
   if (ie <= ib) return;
-  const int kb = 2 * ib, ke = 2 * ie;                 // stages of this run (two per item)
 
   for (int i = tid; i < p.N; i += NTH) sbias[i] = p.bias ? p.bias[i] : 0.f;
   __syncthreads();                                    // (also keeps the bias loads out of the counted waits below)
@@ -137,10 +124,8 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
     const unsigned st = lds0 + pstage * STAGE + wave * 1024;
     pstage = (pstage + 1 == NSTG) ? 0 : pstage + 1;
     fence();
-    if (!(KABL(4) && k >= kb + 2)) {
 #pragma unroll
-      for (int i = 0; i < NDMA; ++i) lds_dma16_m0_s(base, (unsigned)doff[i], st + i * (NTH * 16));
-    }
+    for (int i = 0; i < NDMA; ++i) lds_dma16_m0_s(base, (unsigned)doff[i], st + i * (NTH * 16));
     fence();
   };
   // The 32 token rows of wave `w` of unit `mu` as ONE ring stage (same 768-byte rows, same chunk swizzle as a weight stage):
@@ -167,21 +152,12 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
   }
   bf16x8_t areg[2][NKK];                              // two 16-token blocks x 12 k steps: lane (t, q) holds k = 32 kk + 8 q .. + 7
   f32x4_t acc[2][2][2];                               // [stage of the item][weight row group][token block]
-  uint4 pre[P > 0 ? P : 1], nxt[P > 0 ? P : 1];       // epilogue operand of this item / of the next one (fetched an item ahead)
+  uint4 pre[P > 0 ? P : 1];                           // epilogue operand of this item
   float sc[2] = {1.0f, 1.0f};
   int cur_mu = -1;
   bool active = false;
   int m0 = 0;
 
-  unsigned long long tacc[6] = {0, 0, 0, 0, 0, 0}, t_begin = 0, t_last = 0;   // [4]: wait + barrier of the reload stages, [5]: how many
-  auto lap = [&](int slot) {
-    if constexpr (KABL(32)) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      tacc[slot] += now - t_last;
-      t_last = now;
-    }
-  };
-  if constexpr (KABL(32)) t_begin = t_last = __builtin_amdgcn_s_memtime();
   auto fetch = [&](int item, uint4 (&dst)[P > 0 ? P : 1]) {        // exactly P loads: the epilogue operand of `item`
     if (P == 0) return;
     const int it = min(item, p.items - 1);
@@ -213,27 +189,20 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
     for (int kk = 0; kk < NKK; ++kk)
 #pragma unroll
       for (int gi = 0; gi < 2; ++gi) {
-        bf16x8_t w = areg[gi][(kk + 1) % NKK];
-        if constexpr (!KABL(16)) w = *reinterpret_cast<const bf16x8_t*>(st + foff[kk & 3] + (kk >> 2) * 256 + gi * (16 * ROWB));
-        if constexpr (!KABL(2)) {
-          a[gi][0] = mfma16(w, areg[0][kk], a[gi][0]);
-          a[gi][1] = mfma16(w, areg[1][kk], a[gi][1]);
-        } else {
-          asm volatile("" :: "v"(w));
-        }
+        const bf16x8_t w = *reinterpret_cast<const bf16x8_t*>(st + foff[kk & 3] + (kk >> 2) * 256 + gi * (16 * ROWB));
+        a[gi][0] = mfma16(w, areg[0][kk], a[gi][0]);
+        a[gi][1] = mfma16(w, areg[1][kk], a[gi][1]);
       }
     // fragment reads run FD ahead of the MFMA pairs that consume them (hipcc on its own keeps one read in flight and exposes
-    // the LDS latency 24 times per stage: 1440 instead of ~1000 cycles, tools/lab/lab_kres.cpp)
-    if constexpr (!KABL(16) && !KABL(2)) {
-      constexpr int FDV = FD;                            // (12 in flight measured no better: the phase is not latency-bound any more)
-      __builtin_amdgcn_sched_group_barrier(0x100, FDV, 0);
+    // the LDS latency 24 times per stage: 1440 instead of ~1000 cycles)
+    // (12 in flight measured no better: the phase is not latency-bound any more)
+    __builtin_amdgcn_sched_group_barrier(0x100, FD, 0);
 #pragma unroll
-      for (int i = 0; i < 2 * NKK - FDV; ++i) {
-        __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-      }
-      __builtin_amdgcn_sched_group_barrier(0x008, 2 * FDV, 0);
+    for (int i = 0; i < 2 * NKK - FD; ++i) {
+      __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+      __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
     }
+    __builtin_amdgcn_sched_group_barrier(0x008, 2 * FD, 0);
     __builtin_amdgcn_sched_barrier(0);
   };
 
@@ -251,7 +220,6 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
   for (int it = ib; it < ie; ++it) {
     const int mu = it / cbn, cb = it - mu * cbn;
     const int k0 = 2 * it;
-    const bool reloaded_lab = (mu != cur_mu);
     // the stages of the NEXT item are issued from this one unless it starts a new row unit (its rows go through the ring first)
     const bool feed_next = (it + 1 < ie) && ((it + 1) / cbn == mu);
     bias_init(acc[0], cb * 64, 0);
@@ -264,70 +232,47 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
 #pragma unroll
         for (int b = 0; b < 2; ++b) sc[b] = p.seq_scale[p.row2seq[min(m0 + 16 * b, p.M - 1)]];
       }
-      if (AHEAD && it == ib) fetch(it, pre);          // first item of the run: nobody fetched its epilogue operand ahead
-      if constexpr (STAGED) {
-        // No stage of this item is in flight (feed_next above), every ring buffer is free once all waves are here.
-        wait_vm<0>();
-        __builtin_amdgcn_s_barrier();
-        issue_rows(mu, 0, 0); issue_rows(mu, 1, 1); issue_rows(mu, 2, 2);
-        wait_vm<0>();
-        __builtin_amdgcn_s_barrier();
-        if (wave < 3) read_rows(wave);
-        __builtin_amdgcn_s_barrier();                 // buffers free again
-        issue_rows(mu, 3, 0);
-        pstage = 1;
-        issue(k0);                                    // -> buffer 1
-        issue(k0 + 1);                                // -> buffer 2; the stage after them goes to buffer 0
-        wait_vm<2 * NDMA>();                          // wave 3's rows have landed (the two weight stages are younger)
-        __builtin_amdgcn_s_barrier();
-        if (wave == 3) read_rows(0);
-        stage = 1;
-        wait_vm<NDMA>();                              // stage k0 has landed; the barrier below also hands buffer 0 back
-      } else {                                        // lab: per-lane global loads, then drain
-        if (it == ib) { pstage = 0; issue(k0); issue(k0 + 1); stage = 0; }
-        else { pstage = stage; issue(k0); issue(k0 + 1); }
-#pragma unroll
-        for (int b = 0; b < 2; ++b) {
-          const bf16_t* arow = p.A + (size_t)min(m0 + 16 * b, p.M - 1) * p.lda;
-#pragma unroll
-          for (int kk = 0; kk < NKK; ++kk) areg[b][kk] = *reinterpret_cast<const bf16x8_t*>(arow + (4 * kk + q) * 8);
-        }
-        wait_vm<0>();
-        __builtin_amdgcn_s_waitcnt(0x0F70);           // vmcnt(0) again, in a form hipcc's wait-count pass sees
-      }
+      // No stage of this item is in flight (feed_next above), every ring buffer is free once all waves are here.
+      wait_vm<0>();
+      __builtin_amdgcn_s_barrier();
+      issue_rows(mu, 0, 0); issue_rows(mu, 1, 1); issue_rows(mu, 2, 2);
+      wait_vm<0>();
+      __builtin_amdgcn_s_barrier();
+      if (wave < 3) read_rows(wave);
+      __builtin_amdgcn_s_barrier();                   // buffers free again
+      issue_rows(mu, 3, 0);
+      pstage = 1;
+      issue(k0);                                      // -> buffer 1
+      issue(k0 + 1);                                  // -> buffer 2; the stage after them goes to buffer 0
+      wait_vm<2 * NDMA>();                            // wave 3's rows have landed (the two weight stages are younger)
+      __builtin_amdgcn_s_barrier();
+      if (wave == 3) read_rows(0);
+      stage = 1;
+      wait_vm<NDMA>();                                // stage k0 has landed; the barrier below also hands buffer 0 back
       fresh = true;
     } else {                                          // younger than this stage's DMA: the other stage of the previous item + its epilogue operations
       if (active) wait_vm<NDMA + S + P>(); else wait_vm<NDMA + P>();
     }
-    if constexpr (!KABL(64)) __builtin_amdgcn_s_barrier();
-    if constexpr (KABL(32)) {
-      if (reloaded_lab) { lap(4); tacc[5] += 1; } else lap(0);
-    }
+    __builtin_amdgcn_s_barrier();
     if (feed_next) issue(k0 + 2);
-    if (AHEAD) fetch(it + 1, nxt);                    // P loads, consumed by the NEXT item's epilogue
     bias_init(acc[1], cb * 64, 1);
-    lap(1);
     mfma_stage(stage, acc[0]);
     stage = (stage + 1 == NSTG) ? 0 : stage + 1;
-    lap(2);
     // ---------------- second stage: younger than its DMA are the previous item's epilogue operations (none right after a
-    // reload), the stage issued above (if any) and, with AHEAD, the fetch above
+    // reload) and the stage issued above (if any)
     if (fresh) {
-      if (feed_next) wait_vm<NDMA + (AHEAD ? P : 0)>(); else wait_vm<(AHEAD ? P : 0)>();
+      if (feed_next) wait_vm<NDMA>(); else wait_vm<0>();
     } else if (feed_next) {
       if (active) wait_vm<NDMA + S + P>(); else wait_vm<NDMA + P>();
     } else {
       if (active) wait_vm<S + P>(); else wait_vm<P>();
     }
     fresh = false;
-    if constexpr (!KABL(64)) __builtin_amdgcn_s_barrier();
-    lap(0);
+    __builtin_amdgcn_s_barrier();
     if (feed_next) issue(k0 + 3);
-    if (!AHEAD) fetch(it, pre);                       // P loads, consumed a stage of MFMAs later
-    lap(1);
+    fetch(it, pre);                                   // P loads, consumed a stage of MFMAs later
     mfma_stage(stage, acc[1]);
     stage = (stage + 1 == NSTG) ? 0 : stage + 1;
-    lap(2);
 
     // ---------------- epilogue: lane (t, q) owns rows m0 and m0 + 16 and, per row and stage, 8 consecutive columns (bf16 outputs:
     // both row groups) or 2 x 4 consecutive columns (fp32 outputs: one piece per row group).  The two stages' pieces of a row
@@ -335,15 +280,11 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
     // writes: 1.28x write traffic, profiles/round2_kernel_pmc.json history).
     fence();
     const int n0 = cb * 64;
-    // lab (ABL & 256): every store instruction writes one contiguous KiB (values land in the wrong places)
-    auto lin = [&](int k) { return (size_t)((((it * 4 + wave) * 8 + k) & 32767) * 1024 + lane * 16); };
     if (active) {
-      const bool lab_lane0 = !KABL(1) || lane == 0;
 #pragma unroll
       for (int b = 0; b < 2; ++b) {
         const int m = m0 + 16 * b;
-        const bool rowok = (m < p.M) && lab_lane0 && !KABL(128);
-        if constexpr (KABL(128)) asm volatile("" :: "v"(acc[0][0][b]), "v"(acc[0][1][b]), "v"(acc[1][0][b]), "v"(acc[1][1][b]));
+        const bool rowok = (m < p.M);
         if (F32) {
 #pragma unroll
           for (int x = 0; x < 4; ++x) {                // x = stage * 2 + row group: 16 columns each
@@ -351,12 +292,9 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
             const int n = n0 + 16 * x + 4 * q;
             const uint4 r4 = pre[x * 2 + b];
             float v0 = acc[g][gi][b][0], v1 = acc[g][gi][b][1], v2 = acc[g][gi][b][2], v3 = acc[g][gi][b][3];
-            if (!KABL(8)) {
-              v0 = __uint_as_float(r4.x) + sc[b] * v0; v1 = __uint_as_float(r4.y) + sc[b] * v1;
-              v2 = __uint_as_float(r4.z) + sc[b] * v2; v3 = __uint_as_float(r4.w) + sc[b] * v3;
-            }
-            if (KABL(256)) st16f(reinterpret_cast<unsigned char*>(p.C) + lin(b * 4 + x), v0, v1, v2, v3);
-            else if (rowok) st16f(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + n, v0, v1, v2, v3);
+            v0 = __uint_as_float(r4.x) + sc[b] * v0; v1 = __uint_as_float(r4.y) + sc[b] * v1;
+            v2 = __uint_as_float(r4.z) + sc[b] * v2; v3 = __uint_as_float(r4.w) + sc[b] * v3;
+            if (rowok) st16f(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + n, v0, v1, v2, v3);
           }
         } else {
           float v[2][8];
@@ -364,7 +302,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
           for (int g = 0; g < 2; ++g) {
             v[g][0] = acc[g][0][b][0]; v[g][1] = acc[g][0][b][1]; v[g][2] = acc[g][0][b][2]; v[g][3] = acc[g][0][b][3];
             v[g][4] = acc[g][1][b][0]; v[g][5] = acc[g][1][b][1]; v[g][6] = acc[g][1][b][2]; v[g][7] = acc[g][1][b][3];
-            if (EPI == LAFS_EPI_DGELU_BF16 && !KABL(8)) {
+            if (EPI == LAFS_EPI_DGELU_BF16) {
               const uint4 a4 = pre[g * 2 + b];
               if constexpr (AUX_IS_GRAD) {               // aux already holds gelu'(u)
                 v[g][0] *= bf_lo(a4.x); v[g][1] *= bf_hi(a4.x); v[g][2] *= bf_lo(a4.y); v[g][3] *= bf_hi(a4.y);
@@ -376,7 +314,7 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
             }
           }
           float dv[2][8];                                // GELU epilogue saving gelu'(u): value and derivative from one exp / rcp
-          const bool both = (EPI == LAFS_EPI_BF16_GELU) && HAS_U && p.save_grad && !KABL(8);
+          const bool both = (EPI == LAFS_EPI_BF16_GELU) && HAS_U && p.save_grad;
           if (both) {
 #pragma unroll
             for (int g = 0; g < 2; ++g)
@@ -393,14 +331,12 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
               const int n = n0 + 32 * g + 8 * q;
-              if (KABL(256)) st16(reinterpret_cast<unsigned char*>(p.C) + lin(b * 2 + g), pack_bf2(v[g][0], v[g][1]), pack_bf2(v[g][2], v[g][3]),
-                                  pack_bf2(v[g][4], v[g][5]), pack_bf2(v[g][6], v[g][7]));
-              else if (rowok) st16(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n, pack_bf2(v[g][0], v[g][1]), pack_bf2(v[g][2], v[g][3]),
-                                   pack_bf2(v[g][4], v[g][5]), pack_bf2(v[g][6], v[g][7]));
+              if (rowok) st16(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n, pack_bf2(v[g][0], v[g][1]), pack_bf2(v[g][2], v[g][3]),
+                              pack_bf2(v[g][4], v[g][5]), pack_bf2(v[g][6], v[g][7]));
             }
           }
           if (EPI == LAFS_EPI_BF16_GELU) {
-            if (!KABL(8) && !both) {
+            if (!both) {
 #pragma unroll
               for (int g = 0; g < 2; ++g)
 #pragma unroll
@@ -409,34 +345,20 @@ __global__ __launch_bounds__(NTH, 2) void gemm_kres_kernel(KArgs p) {
 #pragma unroll
             for (int g = 0; g < 2; ++g) {
               const int n = n0 + 32 * g + 8 * q;
-              if (KABL(256)) st16(reinterpret_cast<unsigned char*>(p.C2) + lin(b * 2 + g), pack_bf2(v[g][0], v[g][1]), pack_bf2(v[g][2], v[g][3]),
-                                  pack_bf2(v[g][4], v[g][5]), pack_bf2(v[g][6], v[g][7]));
-              else if (rowok) st16(reinterpret_cast<bf16_t*>(p.C2) + (size_t)m * p.ldc2 + n, pack_bf2(v[g][0], v[g][1]), pack_bf2(v[g][2], v[g][3]),
-                                   pack_bf2(v[g][4], v[g][5]), pack_bf2(v[g][6], v[g][7]));
+              if (rowok) st16(reinterpret_cast<bf16_t*>(p.C2) + (size_t)m * p.ldc2 + n, pack_bf2(v[g][0], v[g][1]), pack_bf2(v[g][2], v[g][3]),
+                              pack_bf2(v[g][4], v[g][5]), pack_bf2(v[g][6], v[g][7]));
             }
           }
         }
       }
     }
     fence();
-    if (AHEAD) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) pre[i] = nxt[i];
-    }
-    lap(3);
-  }
-  if constexpr (KABL(32)) {
-    if (tid == 0 && p.stamps != nullptr) {
-      unsigned long long* o = p.stamps + (size_t)blockIdx.x * 8;
-      o[0] = tacc[0]; o[1] = tacc[1]; o[2] = tacc[2]; o[3] = tacc[3];
-      o[4] = __builtin_amdgcn_s_memtime() - t_begin; o[5] = (unsigned long long)(ke - kb); o[6] = tacc[4]; o[7] = tacc[5];
-    }
   }
 }
 
-template <int EPI, bool HAS_U, int ABL>
+template <int EPI, bool HAS_U>
 int launch(const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((gemm_kres_kernel<EPI, HAS_U, ABL>), dim3(grid), dim3(NTH), 0, s, a);
+  hipLaunchKernelGGL((gemm_kres_kernel<EPI, HAS_U>), dim3(grid), dim3(NTH), 0, s, a);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }
@@ -462,9 +384,7 @@ bool lafs_kres_eligible(const lafs_gemm_nt_args* g) {
   return true;
 }
 
-namespace {
-template <int ABL>
-int kres_launch(const lafs_gemm_nt_args* g, hipStream_t stream, int grid_override = 0, unsigned long long* stamps = nullptr) {
+int lafs_kres_launch(const lafs_gemm_nt_args* g, hipStream_t stream) {
   const int e = g->epilogue;
   KArgs a;
   a.A = (const bf16_t*)g->A; a.B = (const bf16_t*)g->B; a.M = g->M; a.N = g->N; a.lda = g->lda; a.ldb = g->ldb;
@@ -474,7 +394,6 @@ int kres_launch(const lafs_gemm_nt_args* g, hipStream_t stream, int grid_overrid
   a.aux = (const bf16_t*)g->aux; a.ldaux = g->ldaux;
   a.cbn = g->N / 64;
   a.save_grad = (g->act == LAFS_GELU_SAVE_GRAD && (e == LAFS_EPI_BF16_GELU || e == LAFS_EPI_DGELU_BF16)) ? 1 : 0;
-  a.stamps = stamps;
 
   const int mus = (g->M + 127) / 128;
   a.items = mus * a.cbn;
@@ -485,18 +404,12 @@ int kres_launch(const lafs_gemm_nt_args* g, hipStream_t stream, int grid_overrid
   int grid = 512;
   while (grid > 8 && a.items / grid < min_items) grid >>= 1;
   if (g_comm_cus > 0 && grid > 2 * (256 - g_comm_cus)) grid = (2 * (256 - g_comm_cus)) & ~7;     // CUs left to RCCL (LAFS_OPT_COMM_CUS)
-  if (grid_override > 0) grid = grid_override;
   switch (e) {
-    case LAFS_EPI_BF16: return launch<LAFS_EPI_BF16, true, ABL>(a, grid, stream);
+    case LAFS_EPI_BF16: return launch<LAFS_EPI_BF16, true>(a, grid, stream);
     case LAFS_EPI_BF16_GELU:
-      return g->C != nullptr ? launch<LAFS_EPI_BF16_GELU, true, ABL>(a, grid, stream) : launch<LAFS_EPI_BF16_GELU, false, ABL>(a, grid, stream);
-    case LAFS_EPI_RESID_F32: return launch<LAFS_EPI_RESID_F32, true, ABL>(a, grid, stream);
+      return g->C != nullptr ? launch<LAFS_EPI_BF16_GELU, true>(a, grid, stream) : launch<LAFS_EPI_BF16_GELU, false>(a, grid, stream);
+    case LAFS_EPI_RESID_F32: return launch<LAFS_EPI_RESID_F32, true>(a, grid, stream);
     default:
-      return a.save_grad ? launch<LAFS_EPI_DGELU_BF16, false, ABL>(a, grid, stream) : launch<LAFS_EPI_DGELU_BF16, true, ABL>(a, grid, stream);
+      return a.save_grad ? launch<LAFS_EPI_DGELU_BF16, false>(a, grid, stream) : launch<LAFS_EPI_DGELU_BF16, true>(a, grid, stream);
   }
 }
-}  // namespace
-
-#ifndef LAFS_KRES_LAB
-int lafs_kres_launch(const lafs_gemm_nt_args* g, hipStream_t stream) { return kres_launch<0>(g, stream); }
-#endif

@@ -5,9 +5,6 @@
 #include <algorithm>
 #include <stdlib.h>
 #include "common.hpp"
-#ifndef LAFS_LN_NT
-#define LAFS_LN_NT 1
-#endif
 #include "lafs_hip.h"
 
 namespace {
@@ -15,24 +12,16 @@ namespace {
 // Loads of the LayerNorm backward's operands -- x, dy and the old value of the gradient stream are each read ONCE by this pass: with
 // the non-temporal hint (global_load ... nt) they do not displace what the kernels running beside this one re-read from the L2 (the
 // fused MLP's weight slices).  Same-box A/B of the step, 9 interleaved pairs: 14.45 against 14.55 ms with plain loads; alone, on
-// operands a timing loop keeps cache-warm, the kernel is 10 % slower with it (tools/lab/NOTES.md).  LAFS_LN_NT=0: plain loads (lab).
+// operands a timing loop keeps cache-warm, the kernel is 10 % slower with it (tools/lab/NOTES.md).
 __device__ __forceinline__ float4 ld_stream4(const float* p) {
-#if LAFS_LN_NT
   typedef float f4v __attribute__((ext_vector_type(4)));
   const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
   return make_float4(v[0], v[1], v[2], v[3]);
-#else
-  return *reinterpret_cast<const float4*>(p);
-#endif
 }
 __device__ __forceinline__ uint2 ld_stream2(const bf16_t* p) {
-#if LAFS_LN_NT
   typedef unsigned u2v __attribute__((ext_vector_type(2)));
   const u2v v = __builtin_nontemporal_load(reinterpret_cast<const u2v*>(p));
   return make_uint2(v[0], v[1]);
-#else
-  return *reinterpret_cast<const uint2*>(p);
-#endif
 }
 
 constexpr int MAXI = 8;   // D <= 2048: lane owns float4 at columns lane*4 + 256*i
@@ -513,7 +502,6 @@ extern "C" int lafs_layernorm_bwd(const void* dy_bf16, int lddy, const float* dy
   LAFS_CHECK_ARG(seq_scale == nullptr || row2seq != nullptr, "seq_scale needs row2seq");
   const int ni = ceil_div(D, 256);
   const dim3 grid(lafs_layernorm_bwd_parts(rows, D));
-#ifndef LAFS_LAB_LN_BWD1
   if (dy_f32 == nullptr && D % 128 == 0 && D <= 512 && rows >= 4096) {      // two rows per wave (see ln_bwd2_kernel); same grid, same slots
     const DropCfg dc = make_drop(drop_p, drop_seed, drop_step, (unsigned)drop_row0 * (unsigned)D);
 #define LN_BWD2(NI_, NW_)                                                                                                                  \
@@ -529,7 +517,6 @@ extern "C" int lafs_layernorm_bwd(const void* dy_bf16, int lddy, const float* dy
     LAFS_LAUNCH_CHECK();
     return LAFS_OK;
   }
-#endif
   if (dy_f32 != nullptr) {
     LN_BWD_DISPATCH(ni, true, (const bf16_t*)dy_bf16, lddy, dy_f32, lddyf, x, ldx, stats, gamma, g_io, ldg, accumulate,
                     (bf16_t*)gb_out, ldgb, seq_scale, row2seq, dgamma, dbeta, part_out, rows, D,

@@ -30,14 +30,6 @@
 #include "lafs_hip.h"
 #include "ctx.hpp"
 
-// lab builds only (tools/lab/Makefile: mlp_abl): timing ablations -- 1 no GELU / gelu' arithmetic, 2 no fragment reads, 4 no LDS-DMA
-// after the prologue's stages, 8 no MFMA, 16 no workgroup barriers (racy), 32 / 64 every second fragment read of stage B / A only.
-// 128 phase time stamps of wave 0 (s_memtime; lafs_mlp_args::ctx carries the output buffer).  0 in the library.
-#ifndef LAFS_MLP_ABL
-#define LAFS_MLP_ABL 0
-#endif
-#define MABL(bit) ((LAFS_MLP_ABL & (bit)) != 0)
-
 namespace {
 
 typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
@@ -55,10 +47,7 @@ constexpr int NKK = D / 32;                  // k steps of GEMM 1 (12)
 constexpr int NOB = D / 16;                  // 16-column output blocks of GEMM 2 (24)
 constexpr int UROWS = 16 * NWV;              // token rows per workgroup (128)
 constexpr int MAXH = 1536;
-#ifndef LAFS_MLP_FD
-#define LAFS_MLP_FD 6
-#endif
-constexpr int FD = LAFS_MLP_FD;              // fragment reads in flight ahead of their MFMAs
+constexpr int FD = 6;                        // fragment reads in flight ahead of their MFMAs
 static_assert(STAGE % (16 * NTH) == 0 && STAGE == D * 128 && NWV == 8, "stage layout");
 
 struct MArgs {
@@ -85,8 +74,7 @@ struct MArgs {
   float* ln_stats; bf16_t* ln_out; int ldln;            //      (mean, rstd) per row and the bf16 operand as by-products (optional)
   int unit_waves;                            // waves of a workgroup that own rows (8: 128-row units; 4: 64-row units, one computing wave per SIMD)
   int row0;                                  // first row of this launch's first unit
-  unsigned long long* stamps;                // lab (ablation 128): per workgroup, wave 0: cycles in {wait + barrier A, DMA issue A, MFMA A, mid-epilogue,
-};                                           //   wait + barrier B, DMA issue B, MFMA B, prologue, final epilogue, whole kernel}
+};
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 __device__ __forceinline__ void fence() { asm volatile("" ::: "memory"); }
@@ -134,8 +122,6 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int t = lane & 15, q = lane >> 4;
-  unsigned long long t_begin = 0;
-  if constexpr (MABL(128)) t_begin = __builtin_amdgcn_s_memtime();
   const int u0 = p.row0 + blockIdx.x * (16 * p.unit_waves);   // first row of this workgroup's unit
   const int NI = p.H / HC;                             // items (>= 2)
   const int row = u0 + wave * 16 + t;                  // this lane's token row
@@ -184,7 +170,6 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
     const bf16_t* base = p.Wa + (size_t)item * HC * p.ldwa;
     const unsigned st = lds0 + buf * STAGE + wave * 1024;
     fence();
-    if (MABL(4) && item >= 2) return;
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) lds_dma16_m0_s(base, (unsigned)doffa[i], st + i * (NTH * 16));
     fence();
@@ -193,7 +178,6 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
     const bf16_t* base = p.Wb + (size_t)item * HC;
     const unsigned st = lds0 + buf * STAGE + wave * 1024;
     fence();
-    if (MABL(4) && item >= 1) return;
 #pragma unroll
     for (int i = 0; i < NDMA; ++i) lds_dma16_m0_s(base + (size_t)i * 64 * p.ldwb, (unsigned)doffb, st + i * (NTH * 16));
     fence();
@@ -444,16 +428,6 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
   // gfx950).  In flight here, oldest first: [whatever the prologue stored: LayerNorm by-products], stage 0, [gelu' of item 0], stage 1,
   // stage 2 -- a wait for "at most the 12 youngest" therefore covers stage 0 and everything older.
 
-  bf16x8_t wprev = areg[0];                            // (lab: ablations 32 / 64)
-  unsigned long long tacc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, t_last = 0;
-  auto lap = [&](int slot) {
-    if constexpr (MABL(128)) {
-      const unsigned long long now = __builtin_amdgcn_s_memtime();
-      tacc[slot] += now - t_last;
-      t_last = now;
-    }
-  };
-  if constexpr (MABL(128)) { t_last = __builtin_amdgcn_s_memtime(); tacc[7] = t_last - t_begin; }
   int buf = 2;                                         // ring buffer of the stage consumed next
   auto next_buf = [&](int b) { return (b + 1 == NSTG) ? 0 : b + 1; };
   for (int it = 0; it < NI; ++it) {
@@ -475,10 +449,8 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
     else if (it == 0) wait_vm<2 * NDMA>();             // younger than stage 0 and the gelu' loads of item 0: stages 1 and 2
     else if (active) wait_vm<NS + NDMA + NL>();
     else wait_vm<NDMA + NL>();
-    if constexpr (!MABL(16)) __builtin_amdgcn_s_barrier();
-    lap(0);
+    __builtin_amdgcn_s_barrier();
     if (it > 0 && has_next) issue_a(it + 1, next_buf(next_buf(buf)));           // stage 2 it + 2 (item 0: issued by the prologue)
-    lap(1);
     if (active) {
       __builtin_amdgcn_sched_barrier(0);
       const unsigned char* st = smem + buf * STAGE;
@@ -486,13 +458,9 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
       for (int kk = 0; kk < NKK; ++kk)
 #pragma unroll
         for (int gi = 0; gi < 4; ++gi) {
-          bf16x8_t w = areg[(kk + 1) % NKK];
-          if constexpr (MABL(64)) { if (gi % 2 == 0) wprev = *reinterpret_cast<const bf16x8_t*>(st + foff[kk & 3] + (kk >> 2) * 256 + gi * (16 * ROWB)); w = wprev; }
-          else if constexpr (!MABL(2)) w = *reinterpret_cast<const bf16x8_t*>(st + foff[kk & 3] + (kk >> 2) * 256 + gi * (16 * ROWB));
-          if constexpr (!MABL(8)) acc1[gi] = mfma16(w, areg[kk], acc1[gi]);
-          else asm volatile("" :: "v"(w));
+          const bf16x8_t w = *reinterpret_cast<const bf16x8_t*>(st + foff[kk & 3] + (kk >> 2) * 256 + gi * (16 * ROWB));
+          acc1[gi] = mfma16(w, areg[kk], acc1[gi]);
         }
-      if constexpr ((LAFS_MLP_ABL & (2 | 8 | 32 | 64)) == 0) {
       __builtin_amdgcn_sched_group_barrier(0x100, FD, 0);
 #pragma unroll
       for (int i = 0; i < 4 * NKK - FD; ++i) {
@@ -500,11 +468,9 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
       __builtin_amdgcn_sched_group_barrier(0x008, FD, 0);
-      }
       __builtin_amdgcn_sched_barrier(0);
     }
     buf = next_buf(buf);
-    lap(2);
     // ----------------- mid-epilogue: GELU (forward) / x gelu'(u) (backward), bf16 rounding, hand-over to GEMM 2 in registers
     fence();
     if constexpr (MODE == LAFS_MLP_BWD) {              // younger than the gelu' loads: the stage A issued above (item 0: stages 1 and 2)
@@ -519,8 +485,7 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) { v[r] = acc1[2 * ks][r]; v[4 + r] = acc1[2 * ks + 1][r]; }
       const int n = it * HC + 32 * ks + 8 * q;
-      if constexpr (MABL(1)) {
-      } else if constexpr (MODE == LAFS_MLP_FWD) {
+      if constexpr (MODE == LAFS_MLP_FWD) {
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] = gelu_f(v[e]);
       } else if constexpr (MODE == LAFS_MLP_FWD_SAVE) {
@@ -541,19 +506,16 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
     }
     }
     fence();
-    lap(3);
     // ================= stage B of the item: acc2 += Wb slice rows x intermediate (48 MFMAs)
     // younger than this stage's DMA: the stage A issued above (if any) and the mid-epilogue's stores
     if (PRJ && it == 0 && active) { if (prj_h) wait_vm<NDMA + NS + 2 * NOB>(); else wait_vm<NDMA + NS + NOB>(); }   // (NI >= 2: has_next)
     else if (has_next) { if (active) wait_vm<NDMA + NS>(); else wait_vm<NDMA>(); }
     else { if (active) wait_vm<NS>(); else wait_vm<0>(); }
-    if constexpr (!MABL(16)) __builtin_amdgcn_s_barrier();
-    lap(4);
+    __builtin_amdgcn_s_barrier();
     if (has_next) {
       issue_b(it + 1, next_buf(next_buf(buf)));        // stage 2 it + 3
       fetch_g(it + 1);
     }
-    lap(5);
     if (active) {
       __builtin_amdgcn_sched_barrier(0);
       const unsigned char* st = smem + buf * STAGE;
@@ -561,13 +523,9 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
       for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
         for (int ob = 0; ob < NOB; ++ob) {
-          bf16x8_t w = areg[ob % NKK];
-          if constexpr (MABL(32)) { if (ob % 2 == 0) wprev = *reinterpret_cast<const bf16x8_t*>(st + goff[ks] + ob * 2048); w = wprev; }
-          else if constexpr (!MABL(2)) w = *reinterpret_cast<const bf16x8_t*>(st + goff[ks] + ob * 2048);
-          if constexpr (!MABL(8)) acc2[ob] = mfma16(w, gfrag[ks], acc2[ob]);
-          else asm volatile("" :: "v"(w));
+          const bf16x8_t w = *reinterpret_cast<const bf16x8_t*>(st + goff[ks] + ob * 2048);
+          acc2[ob] = mfma16(w, gfrag[ks], acc2[ob]);
         }
-      if constexpr ((LAFS_MLP_ABL & (2 | 8 | 32 | 64)) == 0) {
       __builtin_amdgcn_sched_group_barrier(0x100, FD, 0);
 #pragma unroll
       for (int i = 0; i < 2 * NOB - FD; ++i) {
@@ -575,23 +533,10 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
       }
       __builtin_amdgcn_sched_group_barrier(0x008, FD, 0);
-      }
       __builtin_amdgcn_sched_barrier(0);
     }
     buf = next_buf(buf);
-    lap(6);
   }
-  auto stamp_out = [&]() {
-    if constexpr (MABL(128)) {
-      if (tid == 0 && p.stamps != nullptr) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        const unsigned long long now = __builtin_amdgcn_s_memtime();
-        tacc[8] = now - t_last; tacc[9] = now - t_begin;
-        for (int i = 0; i < 10; ++i) p.stamps[(size_t)blockIdx.x * 10 + i] = tacc[i];
-      }
-    }
-  };
-
   // ---- final epilogue of the unit: lane (t, q) owns row `row` and, per output block ob, 4 consecutive fp32 columns (forward)
   // or, per block pair, 8 consecutive bf16 columns (backward)
   if constexpr (!FWD && LNP) {
@@ -682,10 +627,9 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
         p.part[(size_t)blockIdx.x * (2 * D) + c] = sg;               // slot layout of lafs_layernorm_bwd: [workgroup][gamma | beta][D]
       }
     }
-    stamp_out();
     return;
   }
-  if (!rowok) { stamp_out(); return; }
+  if (!rowok) return;
   if constexpr (FWD) {
     const float* rs = p.resid + (size_t)row * p.ldr;
     float* o = reinterpret_cast<float*>(p.out) + (size_t)row * p.ldo;
@@ -746,12 +690,8 @@ __global__ __launch_bounds__(NTH, 1) void mlp_fused_kernel(MArgs p) {
       st16(o + 32 * P + 8 * q, pack_bf2(x[0], x[1]), pack_bf2(x[2], x[3]), pack_bf2(y[0], y[1]), pack_bf2(y[2], y[3]));
     }
   }
-  stamp_out();
 }
 
-#ifndef LAFS_MLP_UW
-#define LAFS_MLP_UW 0
-#endif
 // One workgroup per CU and unit: a launch costs whole rounds of the chip.  Rows beyond the last full round of 128-row units go out as
 // a second launch of 64-row units (one computing wave per SIMD: about 0.6 of a full unit's time, tools/lab/NOTES.md) when they fit one
 // round that way -- 44 160 rows: 256 x 128 + 178 x 64 instead of two rounds of 128.
@@ -759,9 +699,7 @@ template <int MODE, bool LNP, bool PRJ = false>
 int launch(MArgs a, int n_cu, hipStream_t s) {
   const int units = (a.M + UROWS - 1) / UROWS;
   int full = units, half = 0;
-  constexpr int LAB_UW = LAFS_MLP_UW > 0 ? LAFS_MLP_UW : NWV;
-  if (LAFS_MLP_UW > 0) { a.unit_waves = LAB_UW; full = (a.M + 16 * LAB_UW - 1) / (16 * LAB_UW); }      // lab
-  else if (n_cu > 0 && units > n_cu) {
+  if (n_cu > 0 && units > n_cu) {
     const int rounds = units / n_cu, rest = units - rounds * n_cu;          // rest: units of the last, partial round
     const int rest_rows = a.M - rounds * n_cu * UROWS;
     const int h = (rest_rows + 63) / 64;
@@ -822,8 +760,7 @@ extern "C" int lafs_mlp_fused(const lafs_mlp_args* g, hipStream_t stream) {
   a.resid = g->resid; a.ldr = g->ldr; a.seq_scale = g->seq_scale; a.row2seq = g->row2seq;
   a.out = g->out; a.ldo = g->ldo; a.g = (bf16_t*)g->save_grad; a.ldg = g->ldsg; a.a = (bf16_t*)g->save_act; a.lda = g->ldsa;
   a.unit_waves = NWV; a.row0 = 0;
-  a.stamps = MABL(128) ? (unsigned long long*)g->ctx : nullptr;
-  const int n_cu = (g->ctx != nullptr && !MABL(128)) ? g->ctx->n_cu : 0;                      // (no context: one launch of 128-row units)
+  const int n_cu = g->ctx != nullptr ? g->ctx->n_cu : 0;                      // (no context: one launch of 128-row units)
   a.nln_g = fwd ? g->next_ln_gamma : nullptr; a.nln_b = g->next_ln_beta; a.nln_eps = g->next_ln_eps; a.nln_stats = g->next_ln_stats;
   a.nln_out = (bf16_t*)g->next_ln_out; a.ldnln = g->ldnln_next;
   const bool lnp = fwd && g->ln_gamma != nullptr;

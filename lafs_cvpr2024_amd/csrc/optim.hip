@@ -76,27 +76,16 @@ __global__ __launch_bounds__(256) void seg_step_kernel(const int* __restrict__ s
 // The optimizer's state streams -- gradient, both moments, the teacher's fp32 copy and the master weights are each touched once per
 // step, by this kernel, which runs on its own stream BESIDE the backward pass: non-temporal loads / stores (the moments and the
 // teacher copy; the master weights are re-read by the transposed-shadow refresh, the bf16 shadows by the next forward: plain
-// stores) keep 2 GB per step from displacing what the backward's kernels re-read from the L2.  LAFS_OPT_NT=0: plain accesses (lab).
-#ifndef LAFS_OPT_NT
-#define LAFS_OPT_NT 1
-#endif
+// stores) keep 2 GB per step from displacing what the backward's kernels re-read from the L2.
 __device__ __forceinline__ float4 ldst4(const float* p) {
-#if LAFS_OPT_NT
   typedef float f4v __attribute__((ext_vector_type(4)));
   const f4v v = __builtin_nontemporal_load(reinterpret_cast<const f4v*>(p));
   return make_float4(v[0], v[1], v[2], v[3]);
-#else
-  return *reinterpret_cast<const float4*>(p);
-#endif
 }
 __device__ __forceinline__ void stst4(float* p, float4 x) {
-#if LAFS_OPT_NT
   typedef float f4v __attribute__((ext_vector_type(4)));
   const f4v v = {x.x, x.y, x.z, x.w};
   __builtin_nontemporal_store(v, reinterpret_cast<f4v*>(p));
-#else
-  *reinterpret_cast<float4*>(p) = x;
-#endif
 }
 
 __global__ __launch_bounds__(256) void clip_adamw_ema_kernel(float* __restrict__ param, const float* __restrict__ grad,

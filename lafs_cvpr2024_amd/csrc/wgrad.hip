@@ -16,7 +16,6 @@
 //     ds_read_b64_tr_b16 fragment reads (4 rows x 64 B per half-wave) hit four distinct 64-byte bank slots: conflict-free;
 //   * the token axis is cut into slices; every workgroup STORES its fp32 tile into a slice-major scratch image and a second
 //     kernel folds the slices into the gradient (overwrite or accumulate): no atomics, each partial written once, read once.
-#include <stdlib.h>
 #include <type_traits>
 #include "common.hpp"
 #include "lafs_hip.h"
@@ -46,26 +45,15 @@ template <bool F16> __device__ __forceinline__ f32x16_t mfma32(bf16x8_t a, bf16x
   if constexpr (F16) return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0, 0);
   else return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-constexpr int WG_F16 = 65536;          // ABL bit: operands are fp16 (lafs_wgrad_f16: the trainable landmark CNN); everything else as bf16
-// LDS-DMA with a cache policy chosen at compile time (lab: 0 = default, 1 = nt, 2 = sc1, 3 = sc0 sc1, 4 = sc0)
-template <int POL> __device__ __forceinline__ void lds_dma16_pol(const void* gsrc, unsigned lds_base) {
-  if constexpr (POL == 1) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off nt" : : "v"(gsrc), "s"(lds_base) : "memory");
-  else if constexpr (POL == 2) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc1" : : "v"(gsrc), "s"(lds_base) : "memory");
-  else if constexpr (POL == 3) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc0 sc1" : : "v"(gsrc), "s"(lds_base) : "memory");
-  else if constexpr (POL == 4) asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off sc0" : : "v"(gsrc), "s"(lds_base) : "memory");
-  else lds_dma16_m0(gsrc, lds_base);
-}
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 constexpr int KB = 32;                 // reduction rows per stage
 constexpr int PANEL = KB * 128;        // one 64-column panel of a stage
 
 // Wave grid WM x WN, FA x FB 32x32 accumulator blocks per wave: output tile (32 FA WM) x (32 FB WN), 64 WM WN threads.
-// ABL: timing ablations for tools/lab (0 on the product path): 1 = no DMA after the prologue, 2 = no MFMA, 4 = no fragment reads,
-// 8 = fragments read once (MFMA-only loop), 16 = no wait / barrier in the steady loop, 32 = every slice streams the rows of slice 0
-// (a fifth of the bytes: Infinity-Cache resident), 64 = the row pointers never advance (L2-resident stream)
-template <int WM, int WN, int FA, int FB, int NS, int OCC, int ABL = 0>
-__global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kernel(WgArgs p) {
+// F16: operands are fp16 (lafs_wgrad_f16: the trainable landmark CNN); everything else as bf16.
+template <int WM, int WN, int FA, int FB, int NS, bool F16>
+__global__ __launch_bounds__(64 * WM * WN, (WM * WN) / 4) void wgrad_kernel(WgArgs p) {
   constexpr int NTH = 64 * WM * WN;
   constexpr int T1 = 32 * FA * WM, T2 = 32 * FB * WN;
   static_assert(T1 % 64 == 0 && T2 % 64 == 0, "tile sides must be whole 64-column panels");
@@ -73,7 +61,7 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
   constexpr int STAGE = NP * PANEL;
   constexpr int NCH = NP * 256;                                      // 16-byte pieces per stage
   constexpr int NR = (NCH + NTH - 1) / NTH;                          // LDS-DMA instructions per thread and stage
-  static_assert(NS >= 3 && OCC * NS * STAGE <= 160 * 1024, "ring does not fit the LDS");
+  static_assert(NS >= 3 && NS * STAGE <= 160 * 1024, "ring does not fit the LDS");
   __shared__ __attribute__((aligned(16))) unsigned char smem[NS * STAGE];
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -116,7 +104,7 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
     if (panel < PA) { const int c = n1_0 + panel * 64 + dcol; col = gA + (c < N1 ? c : 0); dld[i] = lda; }
     else { const int c = n2_0 + (panel - PA) * 64 + dcol; col = gB + (c < N2 ? c : 0); dld[i] = ldb; }
     ddst[i] = smem_base + __builtin_amdgcn_readfirstlane((q & ~63) * 16);
-    gp[i] = col + (long)(((ABL & 32) ? 0 : mbeg) + drow) * dld[i];
+    gp[i] = col + (long)(mbeg + drow) * dld[i];
   }
   // Stages are issued in order; `ti` = next stage, `islot` = byte offset of its ring slot.  Only a stage that reaches past the
   // last row of the whole matrix needs its row indices clamped (rows past the SLICE but inside the matrix are real memory and
@@ -124,15 +112,15 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
   int ti = 0; unsigned islot = 0;
   const bool last_clamped = (mbeg + nk * KB > p.M);
   auto issue_piece = [&](int i) {
-    lds_dma16_pol<(ABL >> 8) & 7>(gp[i], ddst[i] + islot);
-    if (!(ABL & 64)) gp[i] += KB * dld[i];
+    lds_dma16_m0(gp[i], ddst[i] + islot);
+    gp[i] += KB * dld[i];
   };
   auto issue_done = [&]() { ++ti; islot += STAGE; if (islot == NS * STAGE) islot = 0; };
   auto issue = [&]() {
     if (last_clamped && ti == nk - 1) {
       const long back = max(mbeg + ti * KB + drow - (p.M - 1), 0);     // rows past the end of the matrix re-read its last row
 #pragma unroll
-      for (int i = 0; i < NR; ++i) lds_dma16_pol<(ABL >> 8) & 7>(gp[i] - back * dld[i], ddst[i] + islot);
+      for (int i = 0; i < NR; ++i) lds_dma16_m0(gp[i] - back * dld[i], ddst[i] + islot);
     } else {
 #pragma unroll
       for (int i = 0; i < NR; ++i) issue_piece(i);
@@ -174,7 +162,6 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
   for (int b = 0; b < FB; ++b) { const int f = wn * FB + b; offB[b] = (PA + (f >> 1)) * PANEL + (lb0 ^ ((f & 1) * 64)); }
 
   auto load_one = [&](bf16x8_t (&fa)[FA], bf16x8_t (&fb)[FB], const unsigned char* sk, int f) {   // fragment f: A blocks first
-    if (ABL & 4) return;
     const unsigned char* q = sk + (f < FA ? offA[f < FA ? f : 0] : offB[f < FA ? 0 : f - FA]);
     const s16x8_t v = __builtin_shufflevector(lds_read_tr16(q), lds_read_tr16(q + 512), 0, 1, 2, 3, 4, 5, 6, 7);
     if (f < FA) fa[f < FA ? f : 0] = __builtin_bit_cast(bf16x8_t, v);
@@ -191,32 +178,18 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
   auto group = [&](const bf16x8_t (&fa)[FA], const bf16x8_t (&fb)[FB], bf16x8_t (&na)[FA], bf16x8_t (&nb)[FB],
                    const unsigned char* nsk, auto READS, auto DMA, int half) {
     constexpr int NM = FA * FB, NF = FA + FB;
-    if (ABL & (2 | 4)) {
-      if (decltype(READS)::value) load_frags(na, nb, nsk);
-      if (decltype(DMA)::value && !(ABL & 1)) {
-#pragma unroll
-        for (int i = 0; i < NR; ++i) issue_piece(i);
-      }
-      if (!(ABL & 4)) {
-#pragma unroll
-        for (int a = 0; a < FA; ++a) asm volatile("" ::"v"(fa[a]));
-#pragma unroll
-        for (int b = 0; b < FB; ++b) asm volatile("" ::"v"(fb[b]));
-      }
-      return;
-    }
 #pragma unroll
     for (int a = 0; a < FA; ++a)
 #pragma unroll
       for (int b = 0; b < FB; ++b) {
         const int k = a * FB + b;
-        acc[a][b] = mfma32<(ABL & WG_F16) != 0>(fa[a], fb[b], acc[a][b]);
-        if (decltype(READS)::value && !(ABL & 8)) {
+        acc[a][b] = mfma32<F16>(fa[a], fb[b], acc[a][b]);
+        if (decltype(READS)::value) {
 #pragma unroll
           for (int f = 0; f < NF; ++f)
             if (f * NM / NF == k) load_one(na, nb, nsk, f);
         }
-        if (decltype(DMA)::value && !(ABL & 1)) {
+        if (decltype(DMA)::value) {
 #pragma unroll
           for (int i = 0; i < NR; ++i)
             if (i * NM / NR == k) issue_piece(i);
@@ -228,7 +201,7 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
       for (int a = 0; a < FA; ++a) {
         typedef __bf16 bf16x2v_t __attribute__((ext_vector_type(2)));
         const uint4 w = __builtin_bit_cast(uint4, fa[a]);
-        if constexpr ((ABL & WG_F16) != 0) {
+        if constexpr (F16) {
           cs[a] += (h_lo(w.x) + h_hi(w.x)) + (h_lo(w.y) + h_hi(w.y)) + (h_lo(w.z) + h_hi(w.z)) + (h_lo(w.w) + h_hi(w.w));
         } else {
         const bf16x2v_t one = __builtin_bit_cast(bf16x2v_t, 0x3f803f80u);        // v_dot2c_f32_bf16: cs += lo * 1 + hi * 1
@@ -272,16 +245,13 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
   if (ti < nk) issue();
   fix_tail(0);
   load_frags(a0, b0, smem);
-  if (ABL & 8) load_frags(a1, b1, smem + 16 * 128);
   unsigned rslot = 0;                                 // ring slot (byte offset) of the stage being multiplied
   int t = 0;
   for (; t < nk - NS; ++t) {                          // steady state: full ring, never the clamped stage
     cs_next();
     group(a0, b0, a1, b1, smem + rslot + 16 * 128, Yes{}, No{}, 0);
-    if (!(ABL & 16)) {
-      wait_vm<(NS - 3) * NR>();
-      __builtin_amdgcn_s_barrier();                  // everyone's pieces of stage t+1 landed; the slot of stage t-1 is free
-    }
+    wait_vm<(NS - 3) * NR>();
+    __builtin_amdgcn_s_barrier();                    // everyone's pieces of stage t+1 landed; the slot of stage t-1 is free
     __builtin_amdgcn_sched_barrier(0);
     rslot += STAGE; if (rslot == NS * STAGE) rslot = 0;
     group(a1, b1, a0, b0, smem + rslot, Yes{}, Yes{}, 1);
@@ -293,7 +263,7 @@ __global__ __launch_bounds__(64 * WM * WN, OCC * (WM * WN) / 4) void wgrad_kerne
     if (t + 1 < nk) {
       wait_stage(min(nk - 2 - t, NS - 3));
       __builtin_amdgcn_s_barrier();
-      if (ti < nk && !(ABL & 1)) issue();
+      if (ti < nk) issue();
       fix_tail(t + 1);
       rslot += STAGE; if (rslot == NS * STAGE) rslot = 0;
       group(a1, b1, a0, b0, smem + rslot, Yes{}, No{}, 1);
@@ -405,16 +375,10 @@ struct Plan { int fa, fb, tiles, slices, mlen; int tile0[MAXG], tiles_n2[MAXG]; 
 // all GEMMs times the token slices fill the 256 CUs once.
 // max_wg: workgroups (= CUs, one 512-register workgroup each) the launch may occupy; a two-stream backward keeps part of the
 // chip free for the HBM-bound kernels of its other stream this way (0 = the whole chip)
-// (Two workgroups per CU on three-stage rings -- OCC = 2, 256 registers per wave, twice the token slices -- were measured in
-// round 3: 233 against 194 us per ViT-S block; the lab instantiation is tools/lab/lab_wgrad.cpp's LAB_OCC2.)
-#ifdef LAFS_LAB_WGRAD_OCC2
-int wgrad_occ() { static const int occ = getenv("LAB_OCC2") ? 2 : 1; return occ; }
-#else
-constexpr int wgrad_occ() { return 1; }
-#endif
+// (Two workgroups per CU on three-stage rings -- 256 registers per wave, twice the token slices -- were measured in round 3:
+// 233 against 194 us per ViT-S block.)
 Plan make_plan(const lafs_wgrad_item* items, int n, int M, int max_wg) {
-  const int occ = wgrad_occ();
-  const int g_wgrad_cus = occ * ((max_wg >= 8 && max_wg <= 256) ? max_wg : 256);
+  const int g_wgrad_cus = (max_wg >= 8 && max_wg <= 256) ? max_wg : 256;
   // (4x4 blocks per wave = 256 accumulators leave hipcc no room: it spills the accumulators around the loop nest)
   static const int cand[4][2] = {{3, 3}, {4, 3}, {3, 4}, {2, 2}};
   Plan best = {};
@@ -423,7 +387,6 @@ Plan make_plan(const lafs_wgrad_item* items, int n, int M, int max_wg) {
   for (int c = 0; c < 4; ++c) {
     Plan pl = {};
     pl.fa = cand[c][0]; pl.fb = cand[c][1];
-    if (occ == 2 && pl.fa * pl.fb > 9) continue;
     for (int g = 0; g < n; ++g) {
       pl.tile0[g] = pl.tiles;
       pl.tiles_n2[g] = ceil_div(items[g].N2, 64 * pl.fb);
@@ -453,34 +416,15 @@ int64_t plan_bytes(const Plan& pl, const lafs_wgrad_item* items, int n) {
   return b;
 }
 
-template <int FA, int FB, int ABL>
+template <int FA, int FB, bool F16>
 int launch(const WgArgs& a, hipStream_t s) {
   constexpr int NS = 5;                              // 2-3 stages (28-32 KiB each) in flight per CU
-#ifdef LAFS_LAB_WGRAD_OCC2
-  if constexpr (FA * FB <= 9) {
-    if (wgrad_occ() == 2) {
-      hipLaunchKernelGGL((wgrad_kernel<2, 2, FA, FB, 3, 2, ABL>), dim3(a.nblk), dim3(256), 0, s, a);
-      LAFS_LAUNCH_CHECK();
-      return LAFS_OK;
-    }
-  }
-#endif
-#ifdef LAFS_LAB_WGRAD_OCC2
-  if constexpr (FA * FB <= 9 && (ABL & ~WG_F16) != 0) {          // lab: a sixth ring stage (3 x 3 blocks: 6 x 24 KiB)
-    static const bool ns6 = getenv("LAFS_WGRAD_NS6") != nullptr;
-    if (ns6) {
-      hipLaunchKernelGGL((wgrad_kernel<2, 2, FA, FB, 6, 1, ABL>), dim3(a.nblk), dim3(256), 0, s, a);
-      LAFS_LAUNCH_CHECK();
-      return LAFS_OK;
-    }
-  }
-#endif
-  hipLaunchKernelGGL((wgrad_kernel<2, 2, FA, FB, NS, 1, ABL>), dim3(a.nblk), dim3(256), 0, s, a);
+  hipLaunchKernelGGL((wgrad_kernel<2, 2, FA, FB, NS, F16>), dim3(a.nblk), dim3(256), 0, s, a);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }
 
-template <int ABL>
+template <bool F16>
 int group_impl(const lafs_wgrad_item* items, int n_items, int M, int max_workgroups, void* workspace, int64_t workspace_bytes,
                hipStream_t stream) {
   LAFS_CLEAR_ERROR();
@@ -521,10 +465,10 @@ int group_impl(const lafs_wgrad_item* items, int n_items, int M, int max_workgro
   a.n_items = n_items; a.M = M; a.mlen = pl.mlen; a.slices = pl.slices; a.tiles = pl.tiles;
   a.nblk = (pl.slices * pl.tiles + 7) & ~7;
   int rc;
-  if (pl.fa == 4 && pl.fb == 3) rc = launch<4, 3, ABL>(a, stream);
-  else if (pl.fa == 3 && pl.fb == 4) rc = launch<3, 4, ABL>(a, stream);
-  else if (pl.fa == 3 && pl.fb == 3) rc = launch<3, 3, ABL>(a, stream);
-  else rc = launch<2, 2, ABL>(a, stream);
+  if (pl.fa == 4 && pl.fb == 3) rc = launch<4, 3, F16>(a, stream);
+  else if (pl.fa == 3 && pl.fb == 4) rc = launch<3, 4, F16>(a, stream);
+  else if (pl.fa == 3 && pl.fb == 3) rc = launch<3, 3, F16>(a, stream);
+  else rc = launch<2, 2, F16>(a, stream);
   if (rc != LAFS_OK) return rc;
   if (pl.slices > 1 || any_cs) {
     f.n_items = n_items; f.slices = pl.slices; f.n4_total = n4; f.cs_total = any_cs ? ncs : 0;
@@ -545,7 +489,7 @@ extern "C" int64_t lafs_wgrad_group_workspace_bytes(const lafs_wgrad_item* items
 
 extern "C" int lafs_wgrad_group(const lafs_wgrad_item* items, int n_items, int M, int max_workgroups, void* workspace,
                                 int64_t workspace_bytes, hipStream_t stream) {
-  return group_impl<0>(items, n_items, M, max_workgroups, workspace, workspace_bytes, stream);
+  return group_impl<false>(items, n_items, M, max_workgroups, workspace, workspace_bytes, stream);
 }
 
 // fp16 operands (the trainable landmark CNN's activations / activation gradients): same kernel, v_mfma_f32_32x32x16_f16
@@ -554,7 +498,7 @@ extern "C" int lafs_wgrad_f16(const void* A, int lda, const void* B, int ldb, fl
   lafs_wgrad_item it = {};
   it.A = A; it.lda = lda; it.B = B; it.ldb = ldb; it.C = C; it.ldc = ldc; it.N1 = N1; it.N2 = N2;
   it.accumulate = accumulate; it.colsum_a = colsum_a;
-  return group_impl<WG_F16>(&it, 1, M, 0, workspace, workspace_bytes, stream);
+  return group_impl<true>(&it, 1, M, 0, workspace, workspace_bytes, stream);
 }
 
 extern "C" int64_t lafs_wgrad_workspace_bytes(int M, int N1, int N2) {

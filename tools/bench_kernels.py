@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the hot kernels at the C2 shapes (ViT-S, B=64: 44160 student tokens).  GPU box only.
-usage: python tools/bench_kernels.py [nt] [tn] [attn] [ablate] [tiles]      (default: nt tn attn)"""
+usage: python tools/bench_kernels.py [nt] [tn] [wg] [wgg] [tnsplits] [tnpart] [augment] [ln] [dzn] [attn]      (default: nt tn attn)"""
 import os
 import sys
 
@@ -70,10 +70,6 @@ if "tn" in which:
     tn(640, 100096, 256, "last wgrad")
     TB = 25216                                                          # ViT-B fine-tune: 128 x 197 tokens
     tn(TB, 768, 2048, "B fc2 wgrad"); tn(TB, 2048, 768, "B fc1 wgrad"); tn(TB, 2112, 768, "B qkv wgrad"); tn(TB, 768, 704, "B proj wgrad")
-    for flag, nm in ((1024, "128x128 kb32"), (4096, "256x128"), (2048, "256x256")):
-        _lib.lib().lafs_debug_set(flag)
-        tn(T, 1536, 384, f"fc1 wgrad {nm}"); tn(TB, 2048, 768, f"B fc1 wgrad {nm}"); tn(TB, 2112, 768, f"B qkv wgrad {nm}")
-    _lib.lib().lafs_debug_set(0)
 if "wg" in which:
     print("--- wide-tile weight gradient (lafs_wgrad) vs the round-1 kernel (lafs_gemm_tn_acc)")
     TB = 25216
@@ -103,7 +99,7 @@ if "tnsplits" in which:
         tn(T, 384, 1536, f"fc2 wgrad s{sp}", splits=sp); tn(T, 1536, 384, f"fc1 wgrad s{sp}", splits=sp)
         tn(T, 384, 384, f"proj wgrad s{sp}", splits=sp); tn(T, 1152, 384, f"qkv wgrad s{sp}", splits=sp)
 if "tnpart" in which:
-    print("--- TN wgrad: device atomics vs per-XCD partial images (+ fold) vs plain stores (wrong results, upper bound)")
+    print("--- TN wgrad: device atomics vs per-XCD partial images (+ fold)")
     for (M, N1, N2, name) in ((T, 384, 1536, "fc2 wgrad"), (T, 1536, 384, "fc1 wgrad"), (T, 384, 384, "proj wgrad"), (T, 1152, 384, "qkv wgrad")):
         A = torch.randn(M, N1, device=dev).to(bf); B = torch.randn(M, N2, device=dev).to(bf)
         Cd = torch.zeros(N1, N2, device=dev); part = torch.zeros(8, N1, N2, device=dev)
@@ -116,96 +112,7 @@ if "tnpart" in which:
         t1 = timeit(lambda: ops.gemm_tn_part(A, B, part))
         out = torch.zeros(N1, N2, device=dev)
         t2 = timeit(lambda: ops.reduce_partials(part, out))
-        _lib.lib().lafs_debug_set(1); t3 = timeit(lambda: ops.gemm_tn_acc(A, B, Cd)); _lib.lib().lafs_debug_set(0)
-        print(f"   {name}: atomics {t0*1e6:7.1f} us | partial {t1*1e6:7.1f} us + fold {t2*1e6:6.1f} us | stores {t3*1e6:7.1f} us")
-if "stagger" in which:
-    print("--- NT GEMMs (LAFS_USE_ABLATE_LIB=1): second round-robin slot of each CU held back by n x ~4 us; 16 = no stores, 32 = no MFMA")
-    for flag in (0, 1 << 20, 2 << 20, 3 << 20, 16, 32, 48):
-        _lib.lib().lafs_debug_set(flag)
-        for M, N, K, e, n in SHAPES[:8]:
-            nt(M, N, K, e, f"{n} f{flag}")
-    _lib.lib().lafs_debug_set(0)
-if "gelucost" in which:
-    print("--- fc1 forward (LAFS_USE_ABLATE_LIB=1): 0 product | 128 second tensor stored without the GELU math | 64 no second store")
-    for flag in (16, 16 + 2, 16 + 2 + 8, 16 + 4 + 8, 48, 48 + 2, 48 + 2 + 8, 48 + 4 + 8):
-        _lib.lib().lafs_debug_set(flag)
-        nt(T, 1536, 384, _lib.EPI_BF16_GELU, f"fc1 fwd f{flag}")
-        nt(25216, 1536, 384, _lib.EPI_BF16_GELU, f"fc1 fwd teacher-size f{flag}")
-    _lib.lib().lafs_debug_set(0)
-if "nttile" in which:
-    print("--- NT GEMMs (LAFS_USE_ABLATE_LIB=1): 0 library choice | 2 128x128 tiles | 4 256x128 tiles | 8 64-deep stages")
-    for flag in (0, 65536, 65536 + 8):
-        _lib.lib().lafs_debug_set(flag)
-        for M, N, K, e, n in SHAPES[:8]:
-            nt(M, N, K, e, f"{n} f{flag}")
-    _lib.lib().lafs_debug_set(0)
-if "ntstore" in which:
-    print("--- NT epilogue stores: normal (default) vs non-temporal (flag 256)")
-    for flag in (0, 256):
-        _lib.lib().lafs_debug_set(flag)
-        for M, N, K, e, n in SHAPES[:8]:
-            nt(M, N, K, e, f"{n} f{flag}")
-    _lib.lib().lafs_debug_set(0)
-if "mlp" in which:
-    print("--- fc1 (+GELU) -> fc2 (+residual) back to back, student shape; flags: 0 normal stores, 256 non-temporal stores")
-    A = torch.randn(T, 384, device=dev).to(bf); W1 = (torch.randn(1536, 384, device=dev) * .02).to(bf); W2 = (torch.randn(384, 1536, device=dev) * .02).to(bf)
-    b1 = torch.zeros(1536, device=dev); b2 = torch.zeros(384, device=dev)
-    # distinct buffers per "layer" so that the working set does not sit in the Infinity Cache between iterations
-    L = 6
-    us = [torch.empty(T, 1536, device=dev, dtype=bf) for _ in range(L)]; as_ = [torch.empty(T, 1536, device=dev, dtype=bf) for _ in range(L)]
-    xs = [torch.randn(T, 384, device=dev) for _ in range(L + 1)]
-    def chain():
-        for l in range(L):
-            ops.gemm_nt(A, W1, _lib.EPI_BF16_GELU, bias=b1, out=us[l], out2=as_[l])
-            ops.gemm_nt(as_[l], W2, _lib.EPI_RESID_F32, bias=b2, resid=xs[l], out=xs[l + 1])
-    for flag in (0, 256):
-        _lib.lib().lafs_debug_set(flag)
-        t = timeit(chain, iters=10)
-        print(f"   flag {flag:4d}: {t / L * 1e6:8.1f} us per fc1+fc2 pair")
-    _lib.lib().lafs_debug_set(0)
-TB = 25216
-SHAPES_B = [(TB, 2112, 768, _lib.EPI_BF16, "B qkv fwd"), (TB, 768, 704, _lib.EPI_RESID_F32, "B proj fwd"),
-            (TB, 2048, 768, _lib.EPI_BF16_GELU, "B fc1 fwd"), (TB, 768, 2048, _lib.EPI_RESID_F32, "B fc2 fwd"),
-            (TB, 2048, 768, _lib.EPI_DGELU_BF16, "B fc2 dgrad"), (TB, 768, 2048, _lib.EPI_BF16, "B fc1 dgrad"),
-            (TB, 704, 768, _lib.EPI_BF16, "B proj dgrad"), (TB, 768, 2112, _lib.EPI_BF16, "B qkv dgrad")]
-if "tilesb" in which:
-    print("--- ViT-B (fine-tune) NT tile variants: 0 = heuristic, 2 = 128x128 bk32, 4 = 256x128 bk32, 10 = 128x128 bk64, 12 = 256x128 bk64")
-    for flag in (0, 2, 4, 10, 12):
-        _lib.lib().lafs_debug_set(flag)
-        for M, N, K, e, n in SHAPES_B:
-            if (flag & 8) and K % 64:
-                continue
-            nt(M, N, K, e, f"{n} f{flag}")
-    _lib.lib().lafs_debug_set(0)
-if "interleave" in which:
-    print("--- fc1: separate u / GELU(u) buffers vs 64-byte interleaved in one [M, 2N] buffer (flag 16384)")
-    A = torch.randn(T, 384, device=dev).to(bf); W1 = (torch.randn(1536, 384, device=dev) * .02).to(bf); b1 = torch.zeros(1536, device=dev)
-    L = 6
-    bufs = [torch.empty(T, 3072, device=dev, dtype=bf) for _ in range(L)]
-    def chain():
-        for l in range(L):
-            ops.gemm_nt(A, W1, _lib.EPI_BF16_GELU, bias=b1, out=bufs[l][:, :1536], out2=bufs[l][:, 1536:])
-    def chain_i():
-        for l in range(L):
-            ops.gemm_nt(A, W1, _lib.EPI_BF16_GELU, bias=b1, out=bufs[l].view(-1)[:T * 1536].view(T, 1536), out2=bufs[l].view(-1)[T * 1536:].view(T, 1536))
-    _lib.lib().lafs_debug_set(32768)
-    tl = timeit(chain_i, iters=10) / L
-    _lib.lib().lafs_debug_set(0)
-    print(f"   piece-by-piece order (flag 32768), two buffers: {tl*1e6:7.1f} us")
-    t0 = timeit(chain, iters=10) / L
-    t0b = timeit(chain_i, iters=10) / L
-    _lib.lib().lafs_debug_set(16384)
-    t1 = timeit(chain_i, iters=10) / L
-    _lib.lib().lafs_debug_set(0)
-    print(f"   halves of one [M,3072] row: {t0*1e6:7.1f} us | two [M,1536] buffers: {t0b*1e6:7.1f} us | 64-B interleaved: {t1*1e6:7.1f} us")
-if "nt256" in which:
-    print("--- NT 256x256 tiles (flag 65536) vs the heuristic choice, wide-output shapes")
-    wide = [x for x in SHAPES[:8] + SHAPES_B if x[1] >= 1024 and x[3] in (_lib.EPI_BF16, _lib.EPI_BF16_GELU, _lib.EPI_DGELU_BF16)]
-    for flag in (0, 65536):
-        _lib.lib().lafs_debug_set(flag)
-        for M, N, K, e, n in wide:
-            nt(M, N, K, e, f"{n} f{flag}")
-    _lib.lib().lafs_debug_set(0)
+        print(f"   {name}: atomics {t0*1e6:7.1f} us | partial {t1*1e6:7.1f} us + fold {t2*1e6:6.1f} us")
 if "augment" in which:
     from lafs_cvpr2024_amd.augment import DeviceAugmenter
     da = DeviceAugmenter(64, n_local=8, device=dev, seed=0)
@@ -215,27 +122,6 @@ if "augment" in which:
     tk = timeit(lambda: call("lafs_augment_views", _p(u8), _p(da.params_dev), _p(da.table), 64, 10, _p(da.views)), iters=20)
     print(f"--- device augmentation: 64 images -> 1280 views: {t*1e6:8.1f} us per batch end to end, kernel alone {tk*1e6:8.1f} us "
           f"({1280/tk/1e6:.2f} M views/s)")
-if "tiles" in which:
-    print("--- NT tile variants: flag 2 = 128x128 bk32, 4 = 256x128 bk32, 10 = 128x128 bk64, 12 = 256x128 bk64")
-    for flag in (2, 4, 10, 12):
-        _lib.lib().lafs_debug_set(flag)
-        for M, N, K, e, n in SHAPES[:8]:
-            nt(M, N, K, e, f"{n} f{flag}")
-    _lib.lib().lafs_debug_set(0)
-if "ablate" in which:
-    print("--- NT ablations: 0 full, 16 no stores, 32 no mfma, 48 loads only, 64 no second (GELU) store")
-    for flag in (0, 16, 32, 48, 64, 128, 192):
-        _lib.lib().lafs_debug_set(flag)
-        nt(T, 1152, 384, _lib.EPI_BF16, f"qkv fwd abl{flag}")
-        nt(T, 1536, 384, _lib.EPI_BF16_GELU, f"fc1 fwd abl{flag}")
-    for flag in (2, 4):
-        _lib.lib().lafs_debug_set(flag)
-        nt(T, 1536, 384, _lib.EPI_BF16_GELU, f"fc1 fwd tile f{flag}")
-        nt(T, 1536, 384, _lib.EPI_DGELU_BF16, f"fc2 dgrad tile f{flag}")
-    _lib.lib().lafs_debug_set(1)
-    print("--- TN with plain stores instead of atomics (flag 1)")
-    tn(T, 384, 1536, "fc2 wgrad")
-    _lib.lib().lafs_debug_set(0)
 if "ln" in which:
     print("--- LayerNorm forward / backward at the student shape (44160 x 384); distinct buffers per call (no cache residency)")
     L = 6

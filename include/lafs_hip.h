@@ -630,6 +630,31 @@ typedef struct lafs_randaug_op {
 int lafs_randaug_apply(const uint8_t* images, uint8_t* out, const lafs_randaug_op* records, int B, int H, int W, int layers, int chw,
                        hipStream_t stream);
 
+/* The torchvision tensor chain of the fine-tune loader (reference image_iter.py:214-219, applied at :349-351 after RandAugment):
+ * Compose([RandomResizedCrop(112, scale=(0.9, 1.0)), ColorJitter(0.1, 0.1, 0.1, 0.1), RandomErasing(scale=(0.02, 0.1))]) on the
+ * uint8 CHW tensor.  PARITY UNPINNED (restated from torchvision 0.9.1; torchvision is not installed): the arithmetic is that of
+ * 0.9.1's functional_tensor as the installed torch evaluates it on the CPU, bit-exact against tests/facedataset_tv_oracle.py.
+ * One 80-byte record per image, drawn on the host with torchvision's own torch calls (lafs_cvpr2024_amd/face_tensor_aug.py):
+ *   crop_i, crop_j, crop_h, crop_w   RandomResizedCrop.get_params box in the source; resampled to S x S as F_t.resize does it
+ *                                    (float32 bilinear interpolate, align_corners=False, round half to even, uint8 cast)
+ *   order[4]                         ColorJitter.get_params fn_idx: 0 brightness, 1 contrast, 2 saturation, 3 hue, applied in turn
+ *   brightness, brightness_c         _blend weights r and 1 - r (float32 of the Python doubles) of adjust_brightness (b = 0),
+ *   contrast, contrast_c             adjust_contrast (b = mean grayscale) and
+ *   saturation, saturation_c         adjust_saturation (b = uint8 grayscale)
+ *   hue                              adjust_hue factor in [-0.1, 0.1] (float32): rgb2hsv, h = (h + f) % 1, hsv2rgb, truncating cast
+ *   erase                            1: RandomErasing applies, the box (erase_i, erase_j, erase_h, erase_w) of the S x S result is
+ *   erase_i, erase_j, erase_h, erase_w  set to 0 (value=0); 0: not applied, or no box was found in 10 tries
+ * images u8 [B,3,H,W], 3 <= H, W, H * W <= 112^2; out u8 [B,3,S,S], 3 <= S <= 112; out may alias images when H = W = S.
+ * Boxes outside the image are clamped into it (the host validates them first). */
+typedef struct lafs_face_tensor_aug_rec {
+  int32_t crop_i, crop_j, crop_h, crop_w;
+  int32_t order[4];
+  float brightness, brightness_c, contrast, contrast_c, saturation, saturation_c, hue;
+  int32_t erase, erase_i, erase_j, erase_h, erase_w;
+} lafs_face_tensor_aug_rec;
+int lafs_face_tensor_aug(const uint8_t* images, uint8_t* out, const lafs_face_tensor_aug_rec* recs, int B, int H, int W, int S,
+                         hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------
  * TRAINABLE landmark CNN of the fine-tune step (csrc/landmark_train.hip; reference face_pre_pro/mobilenet.py:224-313 trained through
  * ViT_face.py:679-711 by train_largescale.py:785-891).  Activations are NHWC bf16 [N H W, ld] matrices, ld = channel count padded

@@ -7,9 +7,16 @@ Kept from the reference: flags that define the step (batch size, epochs, the lr 
 `acc_step/480 * lr * sqrt(world*bs/336) * 336`, weight decay 0.1 on >= 2-D tensors (:618-627; `--weight-decay` is parsed by the
 reference but never reaches its optimizer), mixup alpha/prob, acc_step=3 from supervised_config.py:37, warm-up(5 epochs)+cosine(eta_min 1e-6) LR, loading
 `ckpt['teacher']` of an SSL checkpoint with the 'encoder.|backbone.|module.' prefixes stripped and strict=False).
-Out of scope here: MXNet recordio datasets, the torchvision tensor transforms of FaceDataset
-(RandomResizedCrop / ColorJitter / RandomErasing on uint8 tensors: torchvision is absent, unpinnable), LFW/CFP/AgeDB evaluation,
-tensorboard; `--data synthetic` feeds uint8 batches of the right shape.
+
+Input: `--data recordio --data_path DIR` reads DIR/train.rec (MXNet RecordIO, InsightFace layout, recordio.FaceRecordDataset) with
+the labels of its records, one pass over this rank's shard per epoch (lafs_train.epoch_shard: every rank runs the same number of
+steps); `--data synthetic` feeds random uint8 batches and labels.  The reference's FaceDataset (image_iter.py:299-351, built at
+train_largescale.py:506) is applied in its order: JPEG decode (Pillow, CPU workers) -> `--rand_mirror` -> channel reversal when
+'ms1m' is not in the path (RecordIO only) -> `--rand_au` RandAugment (randaug.py) -> `--random_resizecrop` torchvision tensor
+chain RandomResizedCrop / ColorJitter / RandomErasing (face_tensor_aug.py; PARITY UNPINNED (restated from torchvision 0.9.1;
+torchvision is not installed)), all after the decode on the device.  With RecordIO the tensor chain's decisions are drawn in the
+DataLoader workers next to the decode, from each worker's own torch generator, as the reference draws them.
+Out of scope here: LFW/CFP/AgeDB evaluation, tensorboard.
 """
 import argparse
 import math
@@ -50,12 +57,21 @@ def get_args_parser():
     p.add_argument("--drop_path", default=0.1, type=float)
     p.add_argument("--model_dir", default="", type=str, help="LAFS checkpoint whose ['teacher'] weights initialise the backbone")
     p.add_argument("--pretrain_path", default="", type=str, help="stage-1 checkpoint with the landmark CNN (alias of --landmark_ckpt)")
-    p.add_argument("--data", default="synthetic", type=str)
+    p.add_argument("--data", default="synthetic", type=str,
+                   help="'synthetic': random uint8 batches and labels; 'recordio': --data_path/train.rec (MXNet RecordIO, InsightFace "
+                        "layout; JPEG decode on --num_workers CPU workers, everything after it on the device)")
+    p.add_argument("--data_path", default="", type=str, help="directory holding train.rec / train.idx (--data recordio)")
+    p.add_argument("--num_workers", default=6, type=int, help="DataLoader workers decoding RecordIO samples")
     p.add_argument("--rand_au", default=False, type=utils.bool_flag,
                    help="RandAugment of the reference's FaceDataset (rand_au=True, train_largescale.py:506) on the device")
     p.add_argument("--rand_au_config", default="rand-m1-mstd0.5-inc1", type=str, help="config_str of train_largescale.py:506")
     p.add_argument("--rand_mirror", default=False, type=utils.bool_flag, help="FaceDataset's random horizontal flip (image_iter.py:308-311)")
-    p.add_argument("--steps_per_epoch", default=100, type=int)
+    p.add_argument("--random_resizecrop", default=False, type=utils.bool_flag,
+                   help="FaceDataset's torchvision tensor chain RandomResizedCrop(112, scale=(0.9, 1)) / ColorJitter(0.1, 0.1, 0.1, 0.1) / "
+                        "RandomErasing(scale=(0.02, 0.1)) (image_iter.py:214-219, applied at :349-351) on the device; "
+                        "PARITY UNPINNED (restated from torchvision 0.9.1; torchvision is not installed)")
+    p.add_argument("--steps_per_epoch", default=100, type=int,
+                   help="iterations per epoch for --data synthetic (with --data recordio an epoch is one pass over the rank's shard)")
     p.add_argument("--outdir", "-o", default=".", type=str)
     p.add_argument("--dist_url", default="env://", type=str)
     p.add_argument("--local_rank", default=0, type=int)
@@ -112,6 +128,76 @@ def load_landmark_branch(backbone, path):
     print("=> landmark branch:", len(part), "tensors;", backbone.load_state_dict(part, strict=False))
 
 
+class _WithTensorRecords:
+    """FaceRecordDataset + one tensor-chain record per sample, drawn in the DataLoader worker that decodes it from that worker's
+    own torch generator (seeded from the worker's torch seed, which the DataLoader derives from its base seed and the worker id),
+    as the reference's torchvision transforms draw from each worker's torch RNG."""
+
+    def __init__(self, ds, seed):
+        self.ds, self.seed = ds, seed                  # `seed` only serves num_workers=0 (no worker seed to derive from)
+        self._gen, self._pid = None, None
+
+    def __len__(self):
+        return len(self.ds)
+
+    def __getitem__(self, index):
+        from .face_tensor_aug import sample_one
+        arr, label = self.ds[index]
+        if self._gen is None or self._pid != os.getpid():
+            worker = torch.utils.data.get_worker_info()
+            self._gen = torch.Generator().manual_seed(worker.seed if worker is not None else self.seed)
+            self._pid = os.getpid()
+        return arr, label, sample_one(self._gen, arr.shape[0], arr.shape[1])
+
+
+class RecordIOFaces:
+    """--data_path/train.rec -> (uint8 [B,3,H,W] device batch, int64 labels, tensor-chain records or None), one pass over this
+    rank's shard per epoch (lafs_train.epoch_shard, DistributedSampler semantics: every rank gets len // world samples)."""
+
+    def __init__(self, path, batch, device, seed, num_workers, rank, world, num_class, tensor_records=False):
+        from .recordio import FaceRecordDataset
+        rec = os.path.join(path, "train.rec")
+        self.ds = FaceRecordDataset(rec)
+        self.reverse_channels = "ms1m" not in rec      # image_iter.py:320
+        self.all_seq = list(self.ds.seq)
+        self.rank, self.world, self.seed = rank, world, seed
+        self.per_rank = len(self.all_seq) // world
+        self.batch, self.device, self.workers, self.num_class = batch, device, num_workers, num_class
+        self.tensor_records = tensor_records
+        self.epoch = 0
+        self.set_epoch(0)
+        print(f"Data loaded: there are {len(self.all_seq)} images ({self.per_rank} per rank).")
+
+    def set_epoch(self, epoch):
+        from .lafs_train import epoch_shard
+        self.epoch = int(epoch)
+        mine = epoch_shard(len(self.all_seq), self.rank, self.world, self.seed, self.epoch)
+        self.ds.seq = [self.all_seq[i] for i in mine]
+
+    def __len__(self):
+        return self.per_rank // self.batch
+
+    def __iter__(self):
+        import numpy as np
+        from .face_tensor_aug import RECORD
+        g = torch.Generator().manual_seed(self.seed * 1000003 + self.rank * 1009 + self.epoch)
+        ds = _WithTensorRecords(self.ds, int(torch.randint(0, 2 ** 62, (1,), generator=g))) if self.tensor_records else self.ds
+
+        def collate(items):
+            x = torch.from_numpy(np.stack([it[0] for it in items])).permute(0, 3, 1, 2).contiguous()
+            y = torch.tensor([it[1] for it in items], dtype=torch.int64)
+            recs = np.stack([it[2] for it in items]).astype(RECORD) if self.tensor_records else None
+            return x, y, recs
+
+        loader = torch.utils.data.DataLoader(ds, batch_size=self.batch, shuffle=True, num_workers=self.workers, drop_last=True,
+                                             collate_fn=collate, pin_memory=(torch.device(self.device).type == "cuda"), generator=g)
+        for x, y, recs in loader:
+            top = int(y.max()) if int(y.min()) >= 0 else int(y.min())
+            if not 0 <= top < self.num_class:
+                raise ValueError(f"{self.ds.rec.rec_path}: label {top} is outside [0, --num_class={self.num_class})")
+            yield x.to(self.device, non_blocking=True), y.to(self.device, non_blocking=True), recs
+
+
 def main(args):
     utils.init_distributed_mode(args)
     cfg = get_config(args)
@@ -145,16 +231,38 @@ def main(args):
     if args.rand_au:                    # the loader's per-sample PIL RandAugment as ONE launch per batch (randaug.py / csrc/randaug.hip)
         from .randaug import DeviceRandAugment
         rand_au = DeviceRandAugment(args.rand_au_config, {"translate_const": 117}, seed=cfg["SEED"] + utils.get_rank())
+    tensor_aug = None
+    if args.random_resizecrop:          # the torchvision tensor chain as ONE launch per batch (face_tensor_aug.py / csrc/face_tensor_aug.hip)
+        from .face_tensor_aug import FaceTensorAug
+        tensor_aug = FaceTensorAug(seed=cfg["SEED"] + utils.get_rank())
+    data = None
+    if args.data == "recordio":
+        data = RecordIOFaces(args.data_path, args.batch_size, device, cfg["SEED"], args.num_workers, utils.get_rank(), world,
+                             args.num_class, tensor_records=args.random_resizecrop)
+        n_it = len(data)
+        if n_it == 0:
+            raise ValueError(f"{args.data_path}: {data.per_rank} images per rank are fewer than one batch of {args.batch_size}")
     t0 = time.time()
     for epoch in range(args.epochs):
+        if data is not None:
+            data.set_epoch(epoch)
+        batches = iter(data) if data is not None else None
         for it in range(n_it):
-            x = torch.randint(0, 256, (args.batch_size, 3, 112, 112), device=device, dtype=torch.uint8, generator=gen)
-            y = torch.randint(0, args.num_class, (args.batch_size,), device=device, generator=gen)
+            recs = None
+            if batches is not None:
+                x, y, recs = next(batches)
+            else:
+                x = torch.randint(0, 256, (args.batch_size, 3, 112, 112), device=device, dtype=torch.uint8, generator=gen)
+                y = torch.randint(0, args.num_class, (args.batch_size,), device=device, generator=gen)
             if args.rand_mirror:        # _rd = random.randint(0, 1) per sample, flip along the width
                 flip = torch.randint(0, 2, (args.batch_size, 1, 1, 1), device=device, generator=gen).bool()
                 x = torch.where(flip, x.flip(3), x)
+            if data is not None and data.reverse_channels:
+                x = x.flip(1)           # image_iter.py:320-321: _data[::-1] on CHW when 'ms1m' is not in the path
             if rand_au is not None:
                 x = rand_au(x)
+            if tensor_aug is not None:
+                x = tensor_aug(x, records=recs)
             lr = warmup_cosine(base_lr, epoch + it / n_it, cfg["WARMUP_EPOCH"], args.epochs)
             loss = engine.step(x, y, lr=lr, weight_decay=args.weight_decay)
             if it % 50 == 0:

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the hot kernels at the C2 shapes (ViT-S, B=64: 44160 student tokens).  GPU box only.
-usage: python tools/bench_kernels.py [nt] [tn] [wg] [wgg] [tnsplits] [tnpart] [augment] [ln] [dzn] [attn]      (default: nt tn attn)"""
+usage: python tools/bench_kernels.py [nt] [tn] [wg] [wgg] [tnsplits] [tnpart] [augment] [facetensor] [ln] [dzn] [attn]
+       (default: nt tn attn)"""
 import os
 import sys
 
@@ -122,6 +123,20 @@ if "augment" in which:
     tk = timeit(lambda: call("lafs_augment_views", _p(u8), _p(da.params_dev), _p(da.table), 64, 10, _p(da.views)), iters=20)
     print(f"--- device augmentation: 64 images -> 1280 views: {t*1e6:8.1f} us per batch end to end, kernel alone {tk*1e6:8.1f} us "
           f"({1280/tk/1e6:.2f} M views/s)")
+if "facetensor" in which:
+    import time
+    import numpy as np
+    from lafs_cvpr2024_amd.face_tensor_aug import FaceTensorAug, RECORD
+    from lafs_cvpr2024_amd.ops import _p, call
+    aug = FaceTensorAug(0)
+    t0 = time.perf_counter(); recs = aug.sample(128); th = time.perf_counter() - t0      # host draws, one CPU thread
+    u8 = torch.randint(0, 256, (128, 3, 112, 112), device=dev, dtype=torch.uint8)
+    out = torch.empty_like(u8)
+    rdev = torch.from_numpy(recs.view(np.uint8).reshape(128, RECORD.itemsize)).to(dev)
+    te = timeit(lambda: aug(u8, records=recs, out=out), iters=50)                   # record validation + upload + one launch
+    tk = timeit(lambda: call("lafs_face_tensor_aug", _p(u8), _p(out), _p(rdev), 128, 112, 112, 112), iters=50)
+    print(f"--- torchvision tensor chain (RandomResizedCrop / ColorJitter / RandomErasing), 128 x 3 x 112^2 uint8: kernel {tk*1e6:7.1f} us "
+          f"({2 * u8.numel() / tk / 1e9:.0f} GB/s), end to end with given records {te*1e6:7.1f} us, host sampling {th*1e3:.1f} ms per batch")
 if "ln" in which:
     print("--- LayerNorm forward / backward at the student shape (44160 x 384); distinct buffers per call (no cache residency)")
     L = 6

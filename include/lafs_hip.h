@@ -655,6 +655,25 @@ typedef struct lafs_face_tensor_aug_rec {
 int lafs_face_tensor_aug(const uint8_t* images, uint8_t* out, const lafs_face_tensor_aug_rec* recs, int B, int H, int W, int S,
                          hipStream_t stream);
 
+/* Face verification of the fine-tune loop (reference util/utils.py:292-397 perform_val, util/verification.py:38-87 calculate_roc,
+ * :224-234 calculate_accuracy; called every VER_FREQ optimizer steps by train_largescale.py:925-959).
+ * lafs_eval_flip_normalize: src u8 [B,3,S,S] -> dst f32 [2B,3,S,S]; rows 0..B-1 = x / div * mul + add, every operation rounded on its
+ *   own (div 255, mul 1, add -0.5 is the reference's `batch/255.0-0.5` of utils.py:314 as torch evaluates it on the CPU; div 1,
+ *   mul 2/255, add -1 is the training feed of lafs_mixup_normalize); rows B..2B-1 = the same images mirrored along W
+ *   (load_bin's mx.ndarray.flip(axis=2) on CHW, utils.py:38-41).  S % 16 == 0, both operands 16-byte aligned.
+ * lafs_verify_tail: feat f32 [2B, ldf] = the trunk's embeddings of those 2B rows (row B + i mirrors row i); pair j of the batch is
+ *   images 2j, 2j+1 = global pair pair0 + j of n_pairs.  Per pair, in fp64: norms[img] = ||feat_orig||, norms[2 n_pairs + img] =
+ *   ||feat_flip|| (utils.py:377-384, XNorm), e = feat_orig + feat_flip L2-normalised (utils.py:386-387, sklearn normalize),
+ *   dist = sum (e1 - e2)^2 (verification.py:51-52) -> dist[pair] and the normalised e -> emb f32 [2 n_pairs, D] when non-NULL;
+ *   k0 = #{k : thresholds[k] <= dist} (binary search of the ascending fp64 table, NaN -> n_thr) and
+ *   hist i32 [n_folds][2][n_thr + 1][fold(pair)][issame[pair] != 0][k0] += 1, fold f = [fold_start[f], fold_start[f + 1]).
+ *   The pair counts with dist < thresholds[k] are the prefix sums of hist over k0 <= k.  Integer atomics: deterministic.
+ *   B even, D <= 1024, n_thr * 8 + n_folds * 2 * (n_thr + 1) * 4 <= 64 KiB. */
+int lafs_eval_flip_normalize(const uint8_t* src_u8, float* dst, int B, int S, float div, float mul, float add, hipStream_t stream);
+int lafs_verify_tail(const float* feat, int ldf, int B, int D, int pair0, int n_pairs, const double* thresholds, int n_thr,
+                     const int32_t* fold_start, int n_folds, const uint8_t* issame, int32_t* hist, double* norms, double* dist,
+                     float* emb, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------
  * TRAINABLE landmark CNN of the fine-tune step (csrc/landmark_train.hip; reference face_pre_pro/mobilenet.py:224-313 trained through
  * ViT_face.py:679-711 by train_largescale.py:785-891).  Activations are NHWC bf16 [N H W, ld] matrices, ld = channel count padded

@@ -16,12 +16,20 @@ train_largescale.py:506) is applied in its order: JPEG decode (Pillow, CPU worke
 chain RandomResizedCrop / ColorJitter / RandomErasing (face_tensor_aug.py; PARITY UNPINNED (restated from torchvision 0.9.1;
 torchvision is not installed)), all after the decode on the device.  With RecordIO the tensor chain's decisions are drawn in the
 DataLoader workers next to the decode, from each worker's own torch generator, as the reference draws them.
-Out of scope here: LFW/CFP/AgeDB evaluation, tensorboard.
+Verification (`--val_path DIR`, off by default): the sets named by `--target` (DIR/<name>.bin) are evaluated with the flip test on the
+reference's cadence (train_largescale.py:702-703, 925) -- after the optimizer step where (eval_step - 2) % (VER_FREQ // acc_step) == 1,
+VER_FREQ = len(dataset) // (world * batch * 2) or `--ver_freq` -- printing XNorm, Accuracy-Flip and Best-Threshold per set (:945-947),
+and rank 0 saves a `_checkpoint.pth` whenever need_save (:49-62, 955-959) says the accuracies improved (verification.py).  Cadence:
+the divisor is clamped to >= 1 (the reference divides by zero on small datasets) and an evaluation happens at eval_step = 3, 3 + F,
+3 + 2F, ...: the reference's test for every divisor F >= 3; with F = 2 the reference would also fire at eval_step 1 (Python's -1 % 2 == 1),
+with F = 1 never.
+Out of scope here: tensorboard, IJB evaluation.
 """
 import argparse
 import math
 import os
 import time
+from datetime import datetime
 
 import numpy as np
 import torch
@@ -72,10 +80,65 @@ def get_args_parser():
                         "PARITY UNPINNED (restated from torchvision 0.9.1; torchvision is not installed)")
     p.add_argument("--steps_per_epoch", default=100, type=int,
                    help="iterations per epoch for --data synthetic (with --data recordio an epoch is one pass over the rank's shard)")
+    p.add_argument("--val_path", default="", type=str,
+                   help="directory holding the verification sets <target>.bin; empty (the default): no verification")
+    p.add_argument("--target", "-t", default="lfw,cfp_fp,agedb_30", type=str, help="verification targets (reference :329)")
+    p.add_argument("--val_batch_size", default=0, type=int, help="images per verification batch (even; 0: --batch_size)")
+    p.add_argument("--val_norm", default="reference", type=str, choices=["reference", "train"],
+                   help="verification input scaling: 'reference' x/255 - 0.5 (utils.py:314), 'train' x/255*2 - 1 (the training feed)")
+    p.add_argument("--ver_freq", default=0, type=int,
+                   help="VER_FREQ in micro-batches (0: the reference's len(dataset) // (world * batch_size * 2), :718)")
     p.add_argument("--outdir", "-o", default=".", type=str)
     p.add_argument("--dist_url", default="env://", type=str)
     p.add_argument("--local_rank", default=0, type=int)
     return p
+
+
+def need_save(acc, highest_acc):
+    """reference train_largescale.py:49-62 (updates `highest_acc` in place)."""
+    do_save = False
+    save_cnt = 0
+    if acc[0] > 0.98:
+        do_save = True
+    for i, accuracy in enumerate(acc):
+        if accuracy > highest_acc[i]:
+            highest_acc[i] = accuracy
+            do_save = True
+        if i > 0 and accuracy >= highest_acc[i] - 0.002:
+            save_cnt += 1
+    if save_cnt >= len(acc) * 3 / 4 and acc[0] > 0.99:
+        do_save = True
+    print("highest_acc:", highest_acc)
+    return do_save
+
+
+def ver_divisor(n_data, world, batch_size, acc_step, ver_freq=0):
+    """VER_FREQ // acc_step (reference :718, 925) with VER_FREQ = n_data // (world * batch_size * 2) unless `ver_freq` > 0, clamped
+    to >= 1."""
+    vf = ver_freq if ver_freq > 0 else n_data // (world * batch_size * 2)
+    return max(1, vf // acc_step)
+
+
+def is_eval_step(eval_step, divisor):
+    """Evaluate after the optimizer step that made the (never reset) optimizer-step counter `eval_step`: 3, 3 + F, 3 + 2F, ...
+    -- `(eval_step - 2) % F == 1` of the reference (:925) for F >= 3 (see the module docstring for F < 3)."""
+    return eval_step >= 3 and (eval_step - 3) % divisor == 0
+
+
+def get_time():
+    """reference util/utils.py:23-24."""
+    return (str(datetime.now())[:-10]).replace(' ', '-').replace(':', '-')
+
+
+def build_backbone(args):
+    """The fine-tune model of the reference (:432, 542-557) for these flags."""
+    sharded = args.head == "PartialFC"
+    # the dense ArcFace head lives in the same `loss.weight` tensor as CosFace (the reference names an ArcFace class it never
+    # defines, ViT_face.py:654-655); the margin is applied by the fused kernel
+    return ViT_face_landmark_patch8(loss_type="None" if sharded else "CosFace", GPU_ID=None, num_class=args.num_class,
+                                    image_size=112, patch_size=8, dim=768, depth=12, heads=11, mlp_dim=2048,
+                                    dropout=args.dropout, emb_dropout=args.dropout, with_land=args.with_land,
+                                    drop_path_rate=args.drop_path)
 
 
 def warmup_cosine(base_lr, epoch_float, warmup_epochs, total_epochs, eta_min=1e-6):
@@ -198,6 +261,26 @@ class RecordIOFaces:
             yield x.to(self.device, non_blocking=True), y.to(self.device, non_blocking=True), recs
 
 
+def verify(args, evaluator, engine, vers, highest_acc, backbone, epoch, batch):
+    """Evaluate every set (on every rank), print the reference's lines on rank 0 and save a checkpoint when need_save says so
+    (reference :925-959)."""
+    main_proc = utils.is_main_process()
+    if main_proc:
+        print("Perform Evaluation on", [v[0] for v in vers], ", and Save Checkpoints...")
+    acc = []
+    for name, images, issame in vers:
+        t = time.time()
+        res = evaluator(images, issame, engine=engine)
+        if main_proc:
+            from .verification import report
+            report(name, batch + 1, res)
+            print(f"[{name}] {len(issame)} pairs evaluated in {time.time() - t:.2f} s")
+        acc.append(res[0])
+    if main_proc and need_save(acc, highest_acc):
+        torch.save({"module." + k: v for k, v in backbone.state_dict().items()},
+                   os.path.join(args.outdir, f"Backbone_VIT_Epoch_{epoch + 1}_Batch_{batch + 1}_Time_{get_time()}_checkpoint.pth"))
+
+
 def main(args):
     utils.init_distributed_mode(args)
     cfg = get_config(args)
@@ -206,12 +289,7 @@ def main(args):
     world = utils.get_world_size()
     sharded = args.head == "PartialFC"
     arc = (args.partial_margin if sharded else args.head) == "ArcFace"
-    # the dense ArcFace head lives in the same `loss.weight` tensor as CosFace (the reference names an ArcFace class it never
-    # defines, ViT_face.py:654-655); the margin is applied by the fused kernel
-    backbone = ViT_face_landmark_patch8(loss_type="None" if sharded else "CosFace", GPU_ID=None, num_class=args.num_class,
-                                        image_size=112, patch_size=8, dim=768, depth=12, heads=11, mlp_dim=2048,
-                                        dropout=args.dropout, emb_dropout=args.dropout, with_land=args.with_land,
-                                        drop_path_rate=args.drop_path)
+    backbone = build_backbone(args)
     if args.model_dir:
         load_ssl_teacher(backbone, args.model_dir)
     if args.landmark_ckpt or args.pretrain_path:
@@ -242,6 +320,16 @@ def main(args):
         n_it = len(data)
         if n_it == 0:
             raise ValueError(f"{args.data_path}: {data.per_rank} images per rank are fewer than one batch of {args.batch_size}")
+    vers, evaluator, highest_acc, divisor = None, None, None, None
+    if args.val_path:
+        from .verification import VerificationEvaluator, get_val_data
+        vers = get_val_data(args.val_path, args.target)
+        highest_acc = [0.0 for _ in vers]
+        n_data = len(data.all_seq) if data is not None else args.steps_per_epoch * args.batch_size * world
+        divisor = ver_divisor(n_data, world, args.batch_size, cfg["acc_step"], args.ver_freq)
+        evaluator = VerificationEvaluator(backbone, args.val_batch_size or args.batch_size, device, norm=args.val_norm)
+    eval_step = 0
+    batch = 0
     t0 = time.time()
     for epoch in range(args.epochs):
         if data is not None:
@@ -268,6 +356,11 @@ def main(args):
             if it % 50 == 0:
                 print(f"Epoch {epoch} it {it}/{n_it} loss {float(loss.item()):.4f} lr {lr:.3e} "
                       f"{(epoch * n_it + it + 1) * args.batch_size * world / (time.time() - t0):.1f} samples/s")
+            if engine.micro % cfg["acc_step"] == 0:      # an optimizer step ran (reference :893)
+                eval_step += 1
+                if evaluator is not None and is_eval_step(eval_step, divisor):
+                    verify(args, evaluator, engine, vers, highest_acc, backbone, epoch, batch)
+            batch += 1
         if utils.is_main_process():
             torch.save({"module." + k: v for k, v in backbone.state_dict().items()},
                        os.path.join(args.outdir, f"Backbone_VIT_Epoch_{epoch + 1}.pth"))    # IJB loader expects 'module.' (IJB_evaluation.py:126)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the hot kernels at the C2 shapes (ViT-S, B=64: 44160 student tokens).  GPU box only.
-usage: python tools/bench_kernels.py [nt] [tn] [wg] [wgg] [tnsplits] [tnpart] [augment] [facetensor] [ln] [dzn] [attn]
+usage: python tools/bench_kernels.py [nt] [tn] [wg] [wgg] [tnsplits] [tnpart] [augment] [facetensor] [verify] [ln] [dzn] [attn]
        (default: nt tn attn)"""
 import os
 import sys
@@ -173,3 +173,57 @@ if "attn" in which:
         tb = timeit(lambda: ops.attention_bwd(qkv, out, dout, lse, cu, n, heads, 0.125))
         fl = 4 * nseq * heads * n * n * 64
         print(f"   {nseq:4d} x {n:3d}: fwd {tf*1e6:7.1f} us ({fl/tf/1e12:6.1f} TF/s)   bwd {tb*1e6:7.1f} us ({2.5*fl/tb/1e12:6.1f} TF/s)")
+
+if "verify" in which:
+    # verification (verification.py): extraction rate of the flip test at batch 128 on Part-fViT ViT-B with / without the landmark
+    # branch, the host metric at P = 6000, and a whole 6000-pair set against the module path + the reference-style numpy sweep
+    import time
+    import numpy as np
+    from lafs_cvpr2024_amd import verification as V
+    from lafs_cvpr2024_amd.face_pre_pro.ViT_face import ViT_face_landmark_patch8
+    from lafs_cvpr2024_amd.vision_transformer import attach_arena
+    P = 6000
+    x = torch.randint(0, 256, (2 * P, 3, 112, 112), dtype=torch.uint8)
+    issame = np.arange(P) % 2 == 0
+    for land in (True, False):
+        torch.manual_seed(0)
+        m = ViT_face_landmark_patch8(loss_type="None", GPU_ID=None, num_class=10, image_size=112, patch_size=8, dim=768, depth=12,
+                                     heads=11, mlp_dim=2048, dropout=0.1, emb_dropout=0.1, with_land=land)
+        attach_arena(m, dev)
+        ev = V.VerificationEvaluator(m, 128, dev)
+        ev(x[:1024], issame[:512])                                     # warm-up (code objects, plans)
+        torch.cuda.synchronize(); t0 = time.perf_counter()
+        ev(x, issame)
+        torch.cuda.synchronize(); tv = time.perf_counter() - t0
+        print(f"verify with_land={int(land)}: {P} pairs ({2 * P} images, x2 flip) in {tv:.2f} s = {2 * P / tv:.0f} images/s "
+              f"({4 * P / tv:.0f} embeddings/s) at batch 128")
+        if land:
+            # module path: backbone.eval() forward per copy (MIOpen landmark branch) + perform_val's numpy host math
+            m.eval()
+            t0 = time.perf_counter()
+            embs = []
+            with torch.no_grad():
+                for flip in (False, True):
+                    e = np.zeros((2 * P, 768))
+                    for i in range(0, 2 * P, 128):
+                        b = (x[i:i + 128].float() / 255.0 - 0.5).to(dev)
+                        e[i:i + 128] = m(b.flip(3) if flip else b).cpu().numpy()
+                    embs.append(e)
+            t_emb = time.perf_counter() - t0
+            e = embs[0] + embs[1]
+            e = e / np.linalg.norm(e, axis=1, keepdims=True)
+            dist = np.sum(np.square(e[0::2] - e[1::2]), 1)
+            t1 = time.perf_counter()
+            from sklearn.model_selection import KFold
+            for train, test in KFold(10, shuffle=False).split(np.arange(P)):
+                for t in V.THRESHOLDS:
+                    for sel in (train, test):
+                        pred = dist[sel] < t
+                        _ = (np.sum(pred & issame[sel]), np.sum(pred & ~issame[sel]), np.sum(~pred & ~issame[sel]), np.sum(~pred & issame[sel]))
+            t_sweep = time.perf_counter() - t1
+            print(f"module path: {P} pairs: forward {t_emb:.2f} s + numpy sweep {t_sweep:.2f} s = {t_emb + t_sweep:.2f} s")
+    h = V.hist_from_dist(np.random.RandomState(0).uniform(0, 4, P), issame)
+    t0 = time.perf_counter()
+    for _ in range(10):
+        V.metrics_from_hist(h)
+    print(f"host metric from the histogram at P = {P}: {(time.perf_counter() - t0) / 10 * 1e3:.2f} ms")

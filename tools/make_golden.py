@@ -12,7 +12,10 @@ reference source travels with the repo.  Import recipe follows SURVEY.md section
     `timm.models.layers.{DropPath, trunc_normal_}` (mapped to vision_transformer.DropPath and
     torch.nn.init.trunc_normal_);
   * hard-coded `.cuda()` calls are neutralised with `torch.Tensor.cuda = identity`;
-  * DINOLoss needs a process group -> gloo, world_size 1.
+  * DINOLoss needs a process group -> gloo, world_size 1;
+  * `util.utils` (F21: perform_val) additionally needs an empty `mxnet` stub and `torchvision.transforms.ToTensor` (used only for the
+    ROC image it returns; stubbed as a function that returns None), and the IPython stub `get_ipython` (None) and `version_info` (matplotlib draws the ROC image);
+    `util.verification` imports unmodified (sklearn, scipy).
 
 Usage:  python tools/make_golden.py   (rewrites tests/golden/*.npz deterministically)
 """
@@ -614,7 +617,106 @@ def main():
     import json as _json
     save("f15_checkpoint_manifests", manifest=np.array(_json.dumps({
         "student": man(stu), "teacher": man(tea), "dino_loss": man(dl), "finetune_backbone": man(ft), "landmark_cnn": man(lm)})))
+    f21(pl)
     print("done")
+
+
+def f21(pl):
+    """F21 verification (reference util/utils.py:292-397 perform_val -> util/verification.py evaluate / calculate_roc), its own seed."""
+    import torchvision.transforms as tvt
+    tvt.ToTensor = lambda: (lambda img: None)                  # the ROC image only
+    sys.modules.setdefault("mxnet", types.ModuleType("mxnet"))
+    ip = sys.modules["IPython"]
+    if not hasattr(ip, "get_ipython"):                         # (matplotlib asks the IPython stub for a shell and a version)
+        ip.get_ipython, ip.version_info = (lambda: None), (9, 0)
+    import util.utils as ref_uu                                # noqa: E402  (reference module)
+    import sklearn.preprocessing
+    rec = {}
+    ref_evaluate = ref_uu.evaluate
+
+    def recording_evaluate(embeddings, actual_issame, nrof_folds=10, pca=0):
+        out = ref_evaluate(embeddings, actual_issame, nrof_folds, pca)
+        rec["tpr"], rec["fpr"], rec["accuracy"], rec["best_thresholds"] = out
+        rec["embeddings"] = embeddings
+        return out
+
+    ref_uu.evaluate = recording_evaluate
+    # ---------------------------------------------------------------- F21a perform_val's host math at full scale: a lookup-table
+    # "backbone" maps every (scaled) input back to its index and returns a stored fp32 row; the flip copy holds idx + N
+    print("F21a verification metric")
+    rng = np.random.RandomState(21)
+    P, D = 605, 32
+    N = 2 * P
+    thr = np.arange(0, 4, 0.01)
+    t0 = np.zeros((N, D), np.float32)
+    t1 = np.zeros((N, D), np.float32)
+    issame = np.zeros(P, bool)
+    for i in range(P):
+        kind = i % 11
+        issame[i] = (i * 7) % 3 != 0
+        while True:
+            a = rng.randn(D) * rng.uniform(5, 30)
+            af = a + rng.randn(D) * rng.uniform(0.5, 5)
+            if kind == 0:                                       # identical rows: dist exactly 0 (0 < 0 is false at t = 0)
+                b, bf = a, af
+            elif kind == 1:                                     # antipodal rows: dist ~ 4, above every threshold
+                b, bf = -a, -af
+            else:
+                sim = rng.uniform(0.0, 1.6) if issame[i] else rng.uniform(0.6, 2.2)
+                b = a + rng.randn(D) * np.linalg.norm(a) / np.sqrt(D) * sim
+                bf = b + rng.randn(D) * rng.uniform(0.5, 5)
+            rows = np.stack([a, b]).astype(np.float32), np.stack([af, bf]).astype(np.float32)
+            e = sklearn.preprocessing.normalize(rows[0].astype(np.float64) + rows[1].astype(np.float64))
+            d = float(np.sum(np.square(e[0] - e[1])))
+            if kind in (0, 1) or np.min(np.abs(thr - d)) > 1e-9:
+                break
+        t0[2 * i:2 * i + 2], t1[2 * i:2 * i + 2] = rows
+    table = torch.from_numpy(np.concatenate([t0, t1]))
+
+    class Lookup(torch.nn.Module):
+        def forward(self, x):
+            idx = torch.round((x.view(-1).double() + 0.5) * 255.0).long()
+            return table[idx]
+
+    ids = torch.arange(N, dtype=torch.float32).view(N, 1, 1, 1)
+    acc, std, xn, bt, _ = ref_uu.perform_val(False, "cpu", D, 110, Lookup(), [ids, ids + N], list(issame))
+    emb = rec["embeddings"]
+    dist = np.sum(np.square(emb[0::2] - emb[1::2]), 1)
+    others = dist[(dist > 0) & (dist < 3.995)]
+    assert np.min(np.abs(thr[None, :] - others[:, None])) > 1e-9
+    save("f21a_verification_metric", t0=t0, t1=t1, issame=issame, accuracy=rec["accuracy"], best_thresholds=rec["best_thresholds"],
+         tpr=rec["tpr"], fpr=rec["fpr"], xnorm=np.float64(xn), acc_mean=np.float64(acc), acc_std=np.float64(std),
+         best_threshold_mean=np.float64(bt), dist=dist)
+    # ---------------------------------------------------------------- F21b the real model: F13's Part-fViT (eval, with_land, dim 128,
+    # weights in f13_partfvit_land.npz + det_fill) through perform_val, the per-copy embeddings captured by a wrapper
+    print("F21b verification, Part-fViT with_land")
+    torch.manual_seed(2121)
+    yy, xx = torch.meshgrid(torch.arange(112.0), torch.arange(112.0), indexing="ij")
+    x_u8 = torch.empty(20, 3, 112, 112, dtype=torch.uint8)
+    for k in range(20):
+        ident = k // 2 if k % 4 < 2 else k
+        base = torch.stack([127 + 90 * torch.sin(xx / (5.0 + ident % 7) + c) * torch.cos(yy / (6.0 + c) - ident) for c in range(3)])
+        x_u8[k] = (base + torch.randint(-6, 7, (3, 112, 112))).clamp(0, 255).to(torch.uint8)
+    issame_b = [i % 2 == 0 for i in range(10)]
+    caught = []
+
+    class Capture(torch.nn.Module):
+        def __init__(self, m):
+            super().__init__()
+            self.m = m
+
+        def forward(self, x):
+            e = self.m(x)
+            caught.append(e.detach().clone())
+            return e
+
+    xf = x_u8.float()
+    with torch.no_grad():
+        acc, std, xn, bt, _ = ref_uu.perform_val(False, "cpu", 128, 10, Capture(pl), [xf, xf.flip(3)], issame_b)
+    embs = torch.cat(caught).view(2, 20, 128)
+    save("f21b_verification_partfvit", x_u8=x_u8, issame=np.array(issame_b), emb=embs, xnorm=np.float64(xn), acc_mean=np.float64(acc),
+         acc_std=np.float64(std), best_threshold_mean=np.float64(bt), accuracy=rec["accuracy"], best_thresholds=rec["best_thresholds"])
+    ref_uu.evaluate = ref_evaluate
 
 
 if __name__ == "__main__":

@@ -674,6 +674,31 @@ int lafs_verify_tail(const float* feat, int ldf, int B, int D, int pair0, int n_
                      const int32_t* fold_start, int n_folds, const uint8_t* issame, int32_t* hist, double* norms, double* dist,
                      float* emb, hipStream_t stream);
 
+/* IJB-B / IJB-C template verification (csrc/ijb.hip; reference IJB_evaluation.py).
+ * lafs_ijb_align_flip_normalize (:198-247, Embedding.get's cv2.warpAffine + np.fliplr and forward_db's div_(255).sub_(0.5)):
+ *   src u8 = B loose crops packed back to back as HWC RGB, image b at byte offsets[b] with hw[2b], hw[2b+1] = (H, W); inv_maps f32
+ *   [B,6] = the INVERSE map, output pixel (x, y) -> source (m0 x + m1 y + m2, m3 x + m4 y + m5).  dst f32 [2B,3,S,S]: rows 0..B-1 the
+ *   aligned crops scaled as x / div * mul + add (lafs_eval_flip_normalize's arithmetic), rows B..2B-1 the same mirrored along W;
+ *   aligned_u8 u8 [B,3,S,S] (may be NULL) the aligned crops.  Float32 bilinear, four taps, a tap outside the image reads 0 (border
+ *   value 0), rounded to nearest even; the operation order is fixed in ijb.hip.  Reads outside [src, src + src_bytes) are refused
+ *   per image (such an image comes out as zeros).  OpenCV interpolates in fixed point on a 1/32 pixel grid: parity unpinned.
+ * lafs_ijb_template_pool (:731-751 and :501-535 image2template_feature): feats f32 [n_images, ldf] rows [emb(orig) | emb(flip)],
+ *   faceness f32 [n_images]; order i32 [n_images] = the images sorted by (template, media, index); media m holds order[media_start[m]
+ *   .. media_start[m+1]), template t holds media [template_start[t], template_start[t+1]).  Per column in float32: x = (a + b) * s
+ *   (b only when flip, s only when detector_score), sequential adds inside a media, one division by the count when it exceeds 1
+ *   (np.mean), sequential adds over the media (np.sum) -> sums f32 [n_templates, D], bit for bit numpy's; then in float64 the row
+ *   divided by its L2 norm, a zero row left as it is (sklearn.preprocessing.normalize) -> unit f64 [n_templates, D].  D <= 1024.
+ * lafs_ijb_pair_scores (:541-567 verification): scores[p] = sum_d unit[idx1[p], d] * unit[idx2[p], d] in float64; an index outside
+ *   [0, n_templates) scores NaN. */
+int lafs_ijb_align_flip_normalize(const uint8_t* src_u8, int64_t src_bytes, const int64_t* offsets, const int32_t* hw,
+                                  const float* inv_maps, int B, int S, float div, float mul, float add, float* dst, uint8_t* aligned_u8,
+                                  hipStream_t stream);
+int lafs_ijb_template_pool(const float* feats, int ldf, const float* faceness, int n_images, const int32_t* order,
+                           const int32_t* media_start, int n_media, const int32_t* template_start, int n_templates, int D, int flip,
+                           int detector_score, float* sums, double* unit, hipStream_t stream);
+int lafs_ijb_pair_scores(const double* unit, int n_templates, int D, const int32_t* idx1, const int32_t* idx2, int64_t n_pairs,
+                         double* scores, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------
  * TRAINABLE landmark CNN of the fine-tune step (csrc/landmark_train.hip; reference face_pre_pro/mobilenet.py:224-313 trained through
  * ViT_face.py:679-711 by train_largescale.py:785-891).  Activations are NHWC bf16 [N H W, ld] matrices, ld = channel count padded

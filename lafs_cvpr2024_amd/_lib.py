@@ -172,6 +172,9 @@ _PROTOS = {
     "lafs_face_tensor_aug": [vp, vp, vp, i32, i32, i32, i32],
     "lafs_eval_flip_normalize": [vp, vp, i32, i32, f32, f32, f32],
     "lafs_verify_tail": [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp],
+    "lafs_ijb_align_flip_normalize": [vp, i64, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp],
+    "lafs_ijb_template_pool": [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp],
+    "lafs_ijb_pair_scores": [vp, i32, i32, vp, vp, i64, vp],
     "lafs_landmark_theta": [vp, i32, i32, vp, f32, vp, i32, vp],
     "lafs_mixup_normalize": [vp, vp, i32, i32, f32, vp],
     "lafs_margin_softmax_ce_bf16": [vp, i32, i32, i32, vp, vp, f32, vp, f32, f32, i32, f32, vp, i32, vp, vp, vp],

@@ -179,6 +179,33 @@ def evaluate(hist, norm_sum, norm_count, thresholds=THRESHOLDS):
 
 
 # ----------------------------------------------------------------------------------------------------------------- device path
+def landmark_plan(model, device):
+    """The frozen-CNN inference plan of the landmark branch, built from the live weights and running statistics (None without one)."""
+    from .landmark_cnn import HipLandmarkCNN
+    return HipLandmarkCNN(model, device) if model.with_land else None
+
+
+@torch.no_grad()
+def extract_features(model, arena, x, n, cnn, mosaic, device):
+    """x f32 [2n,3,S,S] -> trunk embeddings f32 [2n, D] (eval mode); mosaic: f32 scratch [>= 2n,3,S,S] of the landmark branch.
+    Shared by VerificationEvaluator and ijb_evaluation.IJBEvaluator."""
+    S = x.shape[-1]
+    img = x
+    if cnn is not None:
+        t = cnn(x)
+        n_full = t.shape[1] // 2
+        theta = torch.empty(2 * n, n_full, 2, device=device, dtype=f32)
+        call("lafs_landmark_theta", _p(t), 2 * n, n_full, None, 0.0, None, n_full, _p(theta))
+        img = mosaic[: 2 * n]
+        call("lafs_patch_gather_fwd", _p(x), _p(theta), 2 * n, S, n_full, _p(img))
+    side = img.shape[-1]
+    geom = Fn.geometry([(2 * n, side)], device)
+    D = model._spec.trunk.dim
+    pos = arena.view(arena.master, model._spec.prefix + model._spec.pos).view(-1, D)[: geom.npatch(0) + 1]
+    feat, _, _ = Fn.vit_forward(arena, model._spec, geom, [img], [pos], None, save=False, dropout=None)
+    return feat
+
+
 class VerificationEvaluator:
     def __init__(self, backbone, batch_size, device=None, norm="reference", n_folds=N_FOLDS):
         """backbone: ViT_face_landmark_patch8 (with or without the landmark branch); batch_size: images per batch (even);
@@ -204,27 +231,11 @@ class VerificationEvaluator:
         return self._bufs
 
     def _landmark_plan(self):
-        from .landmark_cnn import HipLandmarkCNN
-        return HipLandmarkCNN(self.model, self.device) if self.model.with_land else None
+        return landmark_plan(self.model, self.device)
 
-    @torch.no_grad()
     def _features(self, x, n, cnn):
         """x f32 [2n,3,S,S] -> trunk embeddings f32 [2n, D] (eval mode)."""
-        m, a, S = self.model, self.arena, x.shape[-1]
-        img = x
-        if cnn is not None:
-            t = cnn(x)
-            n_full = t.shape[1] // 2
-            theta = torch.empty(2 * n, n_full, 2, device=self.device, dtype=f32)
-            call("lafs_landmark_theta", _p(t), 2 * n, n_full, None, 0.0, None, n_full, _p(theta))
-            img = self._bufs["mosaic"][: 2 * n]
-            call("lafs_patch_gather_fwd", _p(x), _p(theta), 2 * n, S, n_full, _p(img))
-        side = img.shape[-1]
-        geom = Fn.geometry([(2 * n, side)], self.device)
-        D = m._spec.trunk.dim
-        pos = a.view(a.master, m._spec.prefix + m._spec.pos).view(-1, D)[: geom.npatch(0) + 1]
-        feat, _, _ = Fn.vit_forward(a, m._spec, geom, [img], [pos], None, save=False, dropout=None)
-        return feat
+        return extract_features(self.model, self.arena, x, n, cnn, self._bufs["mosaic"], self.device)
 
     @torch.no_grad()
     def __call__(self, images, issame, engine=None):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Micro-benchmarks of the hot kernels at the C2 shapes (ViT-S, B=64: 44160 student tokens).  GPU box only.
-usage: python tools/bench_kernels.py [nt] [tn] [wg] [wgg] [tnsplits] [tnpart] [augment] [facetensor] [verify] [ln] [dzn] [attn]
+usage: python tools/bench_kernels.py [nt] [tn] [wg] [wgg] [tnsplits] [tnpart] [augment] [facetensor] [verify] [ijb] [ln] [dzn] [attn]
        (default: nt tn attn)"""
 import os
 import sys
@@ -227,3 +227,75 @@ if "verify" in which:
     for _ in range(10):
         V.metrics_from_hist(h)
     print(f"host metric from the histogram at P = {P}: {(time.perf_counter() - t0) / 10 * 1e3:.2f} ms")
+
+if "ijb" in which:
+    # IJB-C sized protocol (ijb_evaluation.py): N = 469 375 images, T = 23 124 templates, P = 15 658 489 pairs, D = 768, and the
+    # alignment kernel at the reference's batch of 360 loose crops; beside it the numpy oracle of tests/ijb_oracle.py on this host
+    import time
+    import numpy as np
+    from lafs_cvpr2024_amd import ijb_evaluation as J
+    from lafs_cvpr2024_amd.ops import _p, call
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import ijb_oracle as IO
+    N, Tn, P, D, B = 469375, 23124, 15658489, 768, 360
+    rng = np.random.RandomState(0)
+    # alignment
+    hw = np.stack([rng.randint(120, 201, B), rng.randint(120, 201, B)], 1).astype(np.int32)
+    sizes = hw[:, 0].astype(np.int64) * hw[:, 1] * 3
+    offs = np.r_[0, np.cumsum(sizes)]
+    src = torch.randint(0, 256, (int(offs[-1]),), dtype=torch.uint8, device=dev)
+    th = rng.uniform(-0.3, 0.3, B); z = rng.uniform(0.9, 1.5, B)
+    maps = np.stack([z * np.cos(th), -z * np.sin(th), rng.uniform(0, 20, B), z * np.sin(th), z * np.cos(th), rng.uniform(0, 20, B)], 1)
+    d_off, d_hw = torch.from_numpy(offs[:B].copy()).to(dev), torch.from_numpy(hw).to(dev)
+    d_map = torch.from_numpy(maps.astype(np.float32)).to(dev)
+    x = torch.empty(2 * B, 3, 112, 112, device=dev); al = torch.empty(B, 3, 112, 112, device=dev, dtype=torch.uint8)
+    t = timeit(lambda: call("lafs_ijb_align_flip_normalize", _p(src), int(offs[-1]), _p(d_off), _p(d_hw), _p(d_map), B, 112, 255.0, 1.0,
+                            -0.5, _p(x), _p(al)), iters=50)
+    by = int(offs[-1]) + x.numel() * 4 + al.numel()
+    print(f"ijb align B={B}: {t*1e6:8.1f} us   {by/1e6:.1f} MB (whole crops counted) -> {by/t/1e12:.3f} TB/s = {by/t/8e12*100:.1f}% of 8 TB/s")
+    del src, x, al
+    # template pooling: skewed template sizes, as IJB's are
+    w = rng.lognormal(0.0, 1.2, Tn); cnt = np.maximum(1, np.floor(w / w.sum() * (N - Tn)).astype(np.int64) + 1)
+    cnt[0] += N - cnt.sum()
+    tids = rng.permutation(Tn * 4)[:Tn]
+    templates = np.repeat(tids, cnt)
+    medias = np.concatenate([rng.randint(0, c // 3 + 1, c) for c in cnt])
+    perm = rng.permutation(N); templates, medias = templates[perm], medias[perm]
+    print(f"ijb templates: {Tn} of {cnt.min()}..{cnt.max()} images (median {int(np.median(cnt))})")
+    feats = torch.randn(N, 2 * D, device=dev); fac = torch.rand(N, device=dev)
+    t0 = time.perf_counter()
+    order, ms, ts, uq = J.build_csr(templates, medias)
+    t_csr = time.perf_counter() - t0
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+    d_order, d_ms, d_ts = d(order), d(ms), d(ts)
+    sums = torch.empty(Tn, D, device=dev); unit = torch.empty(Tn, D, device=dev, dtype=torch.float64)
+    t = timeit(lambda: call("lafs_ijb_template_pool", _p(feats), 2 * D, _p(fac), N, _p(d_order), _p(d_ms), len(ms) - 1, _p(d_ts), Tn, D, 1, 1,
+                            _p(sums), _p(unit)), iters=10)
+    by = feats.numel() * 4 + N * 8 + Tn * D * 12
+    print(f"ijb pool N={N} T={Tn} D={D}: {t*1e6:9.1f} us   {by/1e9:.2f} GB -> {by/t/1e12:.3f} TB/s = {by/t/8e12*100:.1f}% of 8 TB/s   (host CSR {t_csr:.2f} s)")
+    # pair scores: random pairs, and the same pairs sorted by their first template
+    i1 = rng.randint(0, Tn, P).astype(np.int32); i2 = rng.randint(0, Tn, P).astype(np.int32)
+    sc = torch.empty(P, device=dev, dtype=torch.float64)
+    for tag, (a, b) in (("random order", (i1, i2)), ("sorted by idx1", (np.sort(i1), i2))):
+        da, db = d(a), d(b)
+        t = timeit(lambda: call("lafs_ijb_pair_scores", _p(unit), Tn, D, _p(da), _p(db), P, _p(sc)), iters=5)
+        print(f"ijb pairs P={P} ({tag}): {t*1e3:8.2f} ms   {P/t/1e6:.1f} M pairs/s   gathered {P*2*D*8/t/1e12:.2f} TB/s "
+              f"(table {Tn*D*8/1e6:.0f} MB; 8 TB/s HBM would give {P*2*D*8/8e12*1e3:.1f} ms)")
+    # the whole protocol through the public function (host CSR, H2D of the index lists, both kernels, D2H of the scores)
+    p1, p2 = uq[i1], uq[i2]
+    fac_h = fac.cpu().numpy()
+    J.protocol(feats[:1000], fac_h[:1000], templates[:1000], medias[:1000], templates[:10], templates[10:20])
+    torch.cuda.synchronize(); t0 = time.perf_counter()
+    scores, _, _ = J.protocol(feats, fac_h, templates, medias, p1, p2)
+    t_dev = time.perf_counter() - t0
+    t0 = time.perf_counter(); fpr, tpr = J.roc_points(rng.randint(0, 2, P), scores); cells = J.tar_at_far(fpr, tpr)[2]
+    t_roc = time.perf_counter() - t0
+    print(f"ijb protocol wall: {t_dev:.2f} s on the device path + {t_roc:.2f} s host ROC / table ({len(fpr)} points)")
+    # numpy oracle on this host: all template sums, and the pair scores of the first 1 000 000 pairs scaled to P
+    fh = feats.cpu().numpy()
+    t0 = time.perf_counter(); o_sums, o_uq = IO.template_sums(fh, fac_h, templates, medias); t_sum = time.perf_counter() - t0
+    un = IO.unit_rows(o_sums)
+    t0 = time.perf_counter(); o_sc = IO.pair_scores(un, o_uq, p1[:1000000], p2[:1000000]); t_pair = time.perf_counter() - t0
+    print(f"numpy oracle on this host: template sums {t_sum:.1f} s, pair scores {t_pair:.1f} s per 1e6 pairs = {t_pair * P / 1e6:.0f} s for all "
+          f"(extrapolated)   sums bit-equal to the device's: {np.array_equal(o_sums, sums.cpu().numpy())}, "
+          f"scores max abs diff {float(np.abs(o_sc - scores[:1000000]).max()):.1e}")

@@ -618,7 +618,99 @@ def main():
     save("f15_checkpoint_manifests", manifest=np.array(_json.dumps({
         "student": man(stu), "teacher": man(tea), "dino_loss": man(dl), "finetune_backbone": man(ft), "landmark_cnn": man(lm)})))
     f21(pl)
+    f22(pl)
     print("done")
+
+
+def _ijb_reference_lines(first, last):
+    """Lines first..last (1-based, inclusive) of the reference's IJB_evaluation.py, dedented: the file is a script that runs on
+    import, so its functions and protocol lines are executed from their text."""
+    import textwrap
+    with open(os.path.join(REF, "IJB_evaluation.py")) as f:
+        lines = f.read().splitlines()
+    return textwrap.dedent("\n".join(lines[first - 1:last]))
+
+
+def _ijb_reference_protocol(img_feats, faceness_scores, templates, medias, p1, p2, label, flip=True, detector=True):
+    """IJB_evaluation.py:731-754 + :766 (protocol), :501-567 (image2template_feature, verification), :799-802 + :809-814 (ROC and
+    table) executed on the given arrays.  -> dict(sums, uq, scores, fpr, tpr, table, idx)."""
+    import sklearn.preprocessing
+    from sklearn.metrics import roc_curve
+    rec = {}
+
+    def recording_normalize(x, *a, **k):
+        rec["sums"] = np.array(x, copy=True)
+        return sklearn.preprocessing.normalize(x, *a, **k)
+
+    sk = types.SimpleNamespace(preprocessing=types.SimpleNamespace(normalize=recording_normalize))
+    ns = dict(np=np, sklearn=sk, print=lambda *a, **k: None, img_feats=img_feats, faceness_scores=faceness_scores,
+              templates=templates, medias=medias, p1=p1, p2=p2, use_flip_test=flip, use_norm_score=True, use_detector_score=detector)
+    exec(_ijb_reference_lines(501, 567), ns)
+    exec(_ijb_reference_lines(731, 754), ns)
+    exec(_ijb_reference_lines(766, 766), ns)
+    score = ns["score"]
+    x_labels = [10 ** -6, 10 ** -5, 10 ** -4, 10 ** -3, 10 ** -2, 10 ** -1]               # :795
+    rs = dict(np=np, roc_curve=roc_curve, label=label, scores={"m": score}, method="m", target="T", x_labels=x_labels)
+    exec(_ijb_reference_lines(799, 799) + "\n" + _ijb_reference_lines(801, 802) + "\n" + _ijb_reference_lines(809, 814), rs)
+    fpr_r, tpr_r = rs["fpr"], rs["tpr"]
+    idx = [min(list(zip(abs(fpr_r - x), range(len(fpr_r)))))[1] for x in x_labels]
+    table = rs["tpr_fpr_row"][1:]
+    assert table == ["%.2f" % (tpr_r[i] * 100) for i in idx]
+    sums = rec["sums"]
+    assert sums.dtype == np.float64 and np.array_equal(sums, sums.astype(np.float32))      # float32 sums stored in a float64 array
+    return dict(sums=sums.astype(np.float32), uq=ns["unique_templates"], scores=score, fpr=fpr_r[::-1].copy(), tpr=tpr_r[::-1].copy(),
+                table=np.array(table), idx=np.array(idx))
+
+
+def f22(pl):
+    """F22 IJB-B / IJB-C template verification (reference IJB_evaluation.py), executed from the reference's own lines."""
+    from sklearn.metrics import roc_curve
+    sys.path.insert(0, os.path.join(os.path.dirname(OUT)))                                 # tests/: ijb_oracle
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))                         # tools/: make_synthetic_ijb
+    import ijb_oracle as IO
+    import make_synthetic_ijb as syn
+    # ---------------------------------------------------------------- F22a the protocol's host math on seeded features
+    print("F22a IJB protocol")
+    args = dict(seed=22, T=96, D=384, n_ident=32, noise=9.0)
+    img_feats, faceness, templates, medias, p1, p2, label = syn.protocol_inputs(**args)
+    _, mcount = np.unique(np.stack([templates, medias], 1), axis=0, return_counts=True)
+    _, tcount = np.unique(templates, return_counts=True)
+    assert not np.all(np.diff(templates) >= 0) and np.unique(templates).max() > 10 * len(tcount)
+    assert (mcount == 1).any() and (mcount >= 3).any() and (tcount == 1).any()
+    key = np.sort(np.stack([p1, p2], 1), axis=1)
+    assert len(np.unique(key, axis=0)) == len(key) and np.all(p1 != p2)
+    out = {}
+    for tag, fl, det in (("", True, True), ("noflip_", False, True), ("nodet_", True, False)):
+        r = _ijb_reference_protocol(img_feats, faceness, templates, medias, p1, p2, label, fl, det)
+        gap = np.diff(np.unique(r["scores"])).min()
+        print(f"  {tag or 'default'}: table {list(r['table'])}, smallest score gap {gap:.2e}, {len(r['fpr'])} ROC points")
+        assert gap >= 1e-10, gap
+        assert len(set(r["table"])) > 1
+        out.update({tag + k: v for k, v in r.items()})
+    tie_scores = np.round(out["scores"], 1)                                                # heavy ties for roc_points
+    tf, tt, _ = roc_curve(label, tie_scores)
+    save("f22a_ijb_protocol", **{k: np.asarray(v) for k, v in args.items()}, n_images=np.int64(len(templates)),
+         templates=templates, medias=medias, p1=p1, p2=p2, label=label, tie_scores=tie_scores, tie_fpr=tf, tie_tpr=tt, **out)
+    # ---------------------------------------------------------------- F22b the real model: F13's Part-fViT (eval, with_land) on the
+    # oracle-aligned synthetic loose crops through forward_db (:232-247), then the reference protocol on its embeddings
+    print("F22b IJB, Part-fViT with_land")
+    n = 40
+    ds = syn.dataset(n)
+    imgs = syn.images(n)
+    invs = [IO.similarity(l)[1] for l in ds["lmk"].astype(np.float32)]
+    al = np.stack([IO.align(im, mv) for im, mv in zip(imgs, invs)])
+    batch = np.empty((2 * n, 3, 112, 112), np.uint8)
+    batch[0::2], batch[1::2] = al, al[..., ::-1]                                           # :431-432
+    fns = dict(torch=torch)
+    exec(_ijb_reference_lines(232, 247), fns)
+    pl.eval()
+    emb = fns["forward_db"](types.SimpleNamespace(model=pl, batch_size=n), batch)
+    assert emb.shape == (n, 256) and emb.dtype == np.float32
+    fac = ds["faceness"].astype(np.float32)
+    r = _ijb_reference_protocol(emb, fac, ds["tid"], ds["mid"], ds["p1"], ds["p2"], ds["label"])
+    print(f"  table {list(r['table'])}")
+    save("f22b_ijb_partfvit", n=np.int64(n), sizes=ds["sizes"], lmk=ds["lmk"], faceness=fac, tid=ds["tid"], mid=ds["mid"], p1=ds["p1"],
+         p2=ds["p2"], label=ds["label"], aligned_sum=al.reshape(n, -1).sum(1).astype(np.int64), emb=emb, **r)
 
 
 def f21(pl):

@@ -312,6 +312,14 @@ int lafs_attention_fwd(const void* qkv, int ldqkv, const int32_t* cu_seqlens, in
 int lafs_attention_bwd(const void* qkv, int ldqkv, const void* out_bf16, int ldo, const void* dout_bf16, int lddo,
                        const float* lse, const int32_t* cu_seqlens, int n_seq, int max_len, int heads, float scale,
                        void* dqkv, int lddqkv, hipStream_t stream);
+/* The attention probabilities themselves, for inspection (vision_transformer.py:85-86 `attn`, returned by get_last_selfattention;
+ * face_pre_pro/ViT_face.py:165,175-177 `attention_score`): probs(f32) [n_seq, H, nq, max_len], nq = q_rows > 0 ? q_rows : max_len,
+ * row (s, h, i, :) = softmax_j(scale * q_i . k_j) over the len_s keys of sequence s.  Key columns j >= len_s and query rows i >= len_s
+ * are written as exact zeros (the buffer needs no clearing); q_rows = 1 is the cls-query form (attn[:, :, 0, :]) and costs one query
+ * tile per (sequence, head).  The scores are formed as lafs_attention_fwd forms them (bf16 operands, fp32 accumulation, exp2 of the
+ * scale * log2(e)-folded scores, fp32 maximum / sum / normalisation); P is not rounded to bf16 and the forward's lse is not needed. */
+int lafs_attention_probs(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
+                         float scale, int q_rows, float* probs, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Patch embedding front end  (vision_transformer.py:126-131, 196-207; face_pre_pro/ViT_face.py:760-766)

@@ -671,8 +671,8 @@ __global__ __launch_bounds__(512) void attn_bwd_stream_kernel(AttnArgs a) {
   }
 }
 
-template <typename K>
-int launch_attn(K kernel, int n_pairs, int ppb, int threads, size_t lds, const AttnArgs& a, hipStream_t s) {
+template <typename K, typename A>
+int launch_attn(K kernel, int n_pairs, int ppb, int threads, size_t lds, const A& a, hipStream_t s) {
   // raise the dynamic-LDS limit once per kernel instantiation (not a stream operation; kept out of graph capture)
   static std::mutex mu;
   static std::set<const void*> done;
@@ -727,6 +727,140 @@ int dispatch_len(int which, int max_len, const AttnArgs& a, hipStream_t s) {
   return dispatch<16, 1>(which, a, s);
 }
 
+
+// ------------------------------------------------------------------------------------------------ probability read-out
+// P = softmax(scale Q K^T) itself, fp32, for inspection (vision_transformer.py:85-86 `attn`; face_pre_pro/ViT_face.py:165,175-177
+// `attention_score`): the forward above never materialises it.  The scores are formed exactly as in attn_fwd_kernel (K of the pair in
+// LDS, S^T = K Q^T through the MFMA, log2 domain, fp32 maximum and sum), then normalised in fp32 and NOT rounded to bf16.
+// The kernel is bound by its output: a lane holds 4 keys of ONE query per tile, i.e. 16-byte pieces of 16 different rows -- so a
+// wave parks its 16 x max_len tile in LDS (row stride NT*16 + 4 floats: the 16 rows of a ds_write_b128 lane group fall on 16 disjoint
+// bank quads) and writes it out as what it is in memory, ONE contiguous run of rows * max_len floats (rows are stored whole, zero
+// padding included): dwords up to the first 16-byte boundary, then 16-byte stores of 1 KiB per wave instruction, then the dword tail.
+struct ProbsArgs {
+  const bf16_t* qkv; int ldqkv;
+  const int* __restrict__ cu; int n_seq, heads; float scale;
+  int nq, max_len; float* probs;
+};
+
+template <int NT, int PPB, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_probs_kernel(ProbsArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  constexpr int TILE = NT * 16 * 128;
+  constexpr int PS = NT * 16 + 4;                             // floats per row of a wave's probability tile
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int g = lane >> 4, c16 = lane & 15;
+  const int inner = a.heads * 64;
+  const int n_pairs = a.n_seq * a.heads;
+  {
+    constexpr int TPP = (NW * 64) / PPB;
+    constexpr int IT = (NT * 16 * 8 + TPP - 1) / TPP;
+    const int pl = tid / TPP, lt = tid % TPP;
+    const int pair = blockIdx.x * PPB + pl;
+    if (pair < n_pairs) {
+      const int seq = pair / a.heads, h = pair % a.heads;
+      const int tok0 = a.cu[seq], len = a.cu[seq + 1] - tok0;
+      const bf16_t* kb = a.qkv + (size_t)tok0 * a.ldqkv + inner + h * 64;
+      uint4 vk[IT];
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const int idx = lt + i * TPP, row = idx >> 3, ch = idx & 7;
+        vk[i] = make_uint4(0, 0, 0, 0);
+        if (idx < NT * 16 * 8 && row < len) vk[i] = *reinterpret_cast<const uint4*>(kb + (size_t)row * a.ldqkv + ch * 8);
+      }
+#pragma unroll
+      for (int i = 0; i < IT; ++i) {
+        const int idx = lt + i * TPP, row = idx >> 3, ch = idx & 7;
+        if (idx < NT * 16 * 8) lds_put<0>(smem + pl * TILE, row, ch, vk[i]);
+      }
+    }
+  }
+  __syncthreads();
+  float* pt = reinterpret_cast<float*>(smem + PPB * TILE) + wave * 16 * PS;
+  const float inv_ml = 1.0f / (float)a.max_len;
+  for (int item = wave; item < PPB * NT; item += NW) {
+    const int pl = item % PPB, qt = item / PPB;
+    const int pair = blockIdx.x * PPB + pl;
+    if (pair >= n_pairs || qt * 16 >= a.nq) continue;
+    const int seq = pair / a.heads, h = pair % a.heads;
+    const int tok0 = a.cu[seq], len = a.cu[seq + 1] - tok0;
+    const bool live = qt * 16 < len;                          // wave-uniform: a tile of query rows past the sequence is all zeros
+    if (live) {
+      const unsigned char* Ks = smem + pl * TILE;
+      const int q = qt * 16 + c16;
+      const bf16_t* qp = a.qkv + (size_t)(tok0 + min(q, len - 1)) * a.ldqkv + h * 64 + g * 8;
+      const bf16x8_t qf0 = *reinterpret_cast<const bf16x8_t*>(qp);
+      const bf16x8_t qf1 = *reinterpret_cast<const bf16x8_t*>(qp + 32);
+      f32x4_t st[NT];
+      float mx = -INFINITY;
+      const float c2 = a.scale * 1.4426950408889634f;        // as the forward: p = exp2(s * c2 - max)
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        f32x4_t s = {0.f, 0.f, 0.f, 0.f};
+        const int krow = t * 16 + c16;
+        s = mfma16(rfrag(Ks, krow, g), qf0, s);
+        s = mfma16(rfrag(Ks, krow, 4 + g), qf1, s);
+        if (t * 16 + 16 <= len) {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) { s[r] *= c2; mx = fmaxf(mx, s[r]); }
+        } else {
+#pragma unroll
+          for (int r = 0; r < 4; ++r) {
+            s[r] = (t * 16 + g * 4 + r < len) ? s[r] * c2 : -INFINITY;
+            mx = fmaxf(mx, s[r]);
+          }
+        }
+        st[t] = s;
+      }
+      mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      float sum = 0.f;
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const float e = __builtin_amdgcn_exp2f(st[t][r] - mx);   // a masked key: exp2(-inf) = 0 exactly
+          st[t][r] = e;
+          sum += e;
+        }
+      sum += __shfl_xor(sum, 16, 64);
+      sum += __shfl_xor(sum, 32, 64);
+      const float inv = (q < len) ? 1.0f / sum : 0.f;         // a query row past the sequence: zeros
+#pragma unroll
+      for (int t = 0; t < NT; ++t)
+        *reinterpret_cast<float4*>(pt + c16 * PS + t * 16 + g * 4) = make_float4(st[t][0] * inv, st[t][1] * inv, st[t][2] * inv, st[t][3] * inv);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");   // the tile is read back across lanes of the same wave
+    __builtin_amdgcn_wave_barrier();
+    const int rows = min(16, a.nq - qt * 16);
+    const int n_out = rows * a.max_len;
+    float* dst = a.probs + ((size_t)pair * a.nq + qt * 16) * a.max_len;
+    auto at = [&](int f) -> float {                           // element f of the run: row f / max_len (exact: f + 1/2 is never a multiple)
+      const int row = (int)(((float)f + 0.5f) * inv_ml);
+      return live ? pt[row * PS + (f - row * a.max_len)] : 0.f;
+    };
+    const int head = min(n_out, (int)((4u - ((unsigned)(reinterpret_cast<uintptr_t>(dst) >> 2) & 3u)) & 3u));
+    if (lane < head) dst[lane] = at(lane);
+    const int nbody = (n_out - head) >> 2;
+    for (int i = lane; i < nbody; i += 64) {
+      const int f = head + 4 * i;
+      *reinterpret_cast<float4*>(dst + f) = make_float4(at(f), at(f + 1), at(f + 2), at(f + 3));
+    }
+    const int tail = head + 4 * nbody + lane;
+    if (tail < n_out) dst[tail] = at(tail);
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");   // the next item overwrites the tile
+    __builtin_amdgcn_wave_barrier();
+  }
+}
+
+// Tile shapes as the forward's: four pairs per workgroup for the 37-token crops, one for the 197-token ones (K tile + four
+// wave tiles: 80 KB at 13 tiles, two workgroups per CU)
+template <int NT, int PPB>
+int dispatch_probs(const ProbsArgs& a, hipStream_t s) {
+  constexpr int NW = 4;
+  const size_t lds = (size_t)PPB * NT * 16 * 128 + (size_t)NW * 16 * (NT * 16 + 4) * 4;
+  return launch_attn(attn_probs_kernel<NT, PPB, NW>, a.n_seq * a.heads, PPB, NW * 64, lds, a, s);
+}
+
 }  // namespace
 
 extern "C" int lafs_attention_fwd(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
@@ -753,4 +887,25 @@ extern "C" int lafs_attention_bwd(const void* qkv, int ldqkv, const void* out_bf
   a.out = (bf16_t*)out_bf16; a.ldo = ldo; a.lse = const_cast<float*>(lse);
   a.dout = (const bf16_t*)dout_bf16; a.lddo = lddo; a.dqkv = (bf16_t*)dqkv; a.lddqkv = lddqkv;
   return dispatch_len(1, max_len, a, stream);
+}
+
+extern "C" int lafs_attention_probs(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
+                                    float scale, int q_rows, float* probs, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(qkv && cu_seqlens && probs, "null operand");
+  LAFS_CHECK_ARG(n_seq > 0 && heads > 0 && max_len > 0 && max_len <= 256, "sequence length must be in 1..256");
+  LAFS_CHECK_ARG(q_rows >= 0 && q_rows <= max_len, "q_rows must be 0 (all query rows) or in 1..max_len");
+  LAFS_CHECK_ARG(ldqkv % 8 == 0, "row strides must be multiples of 8 elements");
+  ProbsArgs a = {};
+  a.qkv = (const bf16_t*)qkv; a.ldqkv = ldqkv; a.cu = cu_seqlens; a.n_seq = n_seq; a.heads = heads; a.scale = scale;
+  a.nq = q_rows > 0 ? q_rows : max_len; a.max_len = max_len; a.probs = probs;
+  const int nt = ceil_div(max_len, 16);
+  if (nt <= 1) return dispatch_probs<1, 4>(a, stream);
+  if (nt <= 2) return dispatch_probs<2, 4>(a, stream);
+  if (nt <= 3) return dispatch_probs<3, 4>(a, stream);
+  if (nt <= 4) return dispatch_probs<4, 4>(a, stream);
+  if (nt <= 7) return dispatch_probs<7, 2>(a, stream);
+  if (nt <= 10) return dispatch_probs<10, 1>(a, stream);
+  if (nt <= 13) return dispatch_probs<13, 1>(a, stream);
+  return dispatch_probs<16, 1>(a, stream);
 }

@@ -265,14 +265,9 @@ class ViT_face_landmark_patch8(nn.Module):
         tmax, tmin = t.max(dim=1, keepdim=True)[0], t.min(dim=1, keepdim=True)[0]
         return ((t - tmin) / (tmax - tmin) * 111).view(-1, self.row_num * self.row_num, 2)
 
-    def forward(self, x, label=None, mask=None, visualize=False, save_token=False, opt=None, keep_num=None, glo_diff=False):
-        """(reference :659-795)  `save_token`: also the patch tokens behind the transformer, in front of the head's LayerNorm, detached
-        (an analysis dump in the reference: returns (emb, tokens, theta)); `use_standcoord` (constructor): the patches are gathered at
-        the centres of the regular 8 x 8 grid -- jittered by N(0, 3^2) px with `Random_prob`, re-drawn with replacement with `shuffle`,
-        both from the CPU generator in the reference's order -- and the mosaic is transposed (:717-742).  Attention masks are not
-        supported (never passed by either entry point)."""
-        if mask is not None:
-            raise NotImplementedError("attention masks are not on the training hot path (never passed by either entry point)")
+    def _gather_inputs(self, x, keep_num=None):
+        """The front of `forward` (reference :679-742): images -> (what the trunk embeds, theta).  With the landmark branch or the
+        standard coordinates a 4-D batch becomes the mosaic of patches gathered at theta; anything else passes through."""
         if self._arena is None:
             attach_arena(self)
         theta = self.theta
@@ -295,6 +290,17 @@ class ViT_face_landmark_patch8(nn.Module):
             theta = theta.to(x.device)
             x = extract_patches_pytorch_gridsample(x, theta[:, :num_land], patch_shape=self.patch_shape, num_landm=num_land)
             x = x.permute(0, 1, 3, 2).contiguous()
+        return x, theta
+
+    def forward(self, x, label=None, mask=None, visualize=False, save_token=False, opt=None, keep_num=None, glo_diff=False):
+        """(reference :659-795)  `save_token`: also the patch tokens behind the transformer, in front of the head's LayerNorm, detached
+        (an analysis dump in the reference: returns (emb, tokens, theta)); `use_standcoord` (constructor): the patches are gathered at
+        the centres of the regular 8 x 8 grid -- jittered by N(0, 3^2) px with `Random_prob`, re-drawn with replacement with `shuffle`,
+        both from the CPU generator in the reference's order -- and the mosaic is transposed (:717-742).  Attention masks are not
+        supported (never passed by either entry point)."""
+        if mask is not None:
+            raise NotImplementedError("attention masks are not on the training hot path (never passed by either entry point)")
+        x, theta = self._gather_inputs(x, keep_num)
         self._want_tokens = bool(save_token)
         emb = self.forward_embedding(x)
         self._want_tokens = False
@@ -303,6 +309,33 @@ class ViT_face_landmark_patch8(nn.Module):
         if label is not None:
             return self.loss(emb, label), self.theta
         return (emb, theta) if visualize else emb
+
+    @torch.no_grad()
+    def get_selfattention(self, x, layer=-1, cls_only=False):
+        """Attention probabilities of block `layer` and the landmarks they belong to: (attn f32 [B, heads, n+1, n+1] -- or
+        [B, heads, 1, n+1], the cls query alone, with `cls_only` -- , theta [B, r*r, 2] in pixels as `visualize=True` returns it).
+        Replaces reading ``transformer.layers[l][0].fn.fn.attention_score`` behind a forward of the reference
+        (face_pre_pro/ViT_face.py:175-177; drawn by util/utils.py visualize_attentionmap_*_landmark): the fused forward never stores
+        the probabilities, so the blocks in front of `layer` run as usual and lafs_attention_probs forms P from that block's own q
+        and k with the block's dim ** -0.5 scale.  Eval mode only: element dropout and DropPath would make the read-out differ from
+        the forward that just ran.  Attention masks are not supported."""
+        if self.training:
+            raise RuntimeError("get_selfattention reads out the deterministic eval-mode forward: call model.eval() first")
+        if not -self.depth <= layer < self.depth:
+            raise ValueError(f"layer must be in {-self.depth}..{self.depth - 1}, got {layer}")
+        layer %= self.depth
+        x, theta = self._gather_inputs(x)
+        self._arena.ensure_fresh()
+        n_img = x.shape[0]
+        n = x.shape[1] if x.dim() == 3 else (x.shape[-1] // 8) ** 2
+        side = 8 * int(math.isqrt(n))
+        if (side // 8) ** 2 != n:
+            raise _lib.LafsHipError("the packed engine needs a square number of patches per image")
+        geom = Fn.geometry([(n_img, side)], x.device)
+        tokens, streams = Fn.vit_streams(self._arena, self._spec, geom, [x.contiguous().float()],
+                                         [self.pos_embedding[0, :n + 1].detach().contiguous()], [max(layer, 1)])
+        attn = Fn.vit_block_probs(self._arena, self._spec, geom, streams[0] if layer > 0 else tokens, layer, q_rows=1 if cls_only else 0)
+        return attn, theta
 
 
 # ------------------------------------------------------------------------------------------------- landmark CNN wrapper

@@ -6,7 +6,7 @@ wrappers) and by the fused, hipGraph-captured training engine.
 import os
 import ctypes as C
 import math
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import torch
 
@@ -188,6 +188,60 @@ def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, dr
                                           want_bf16=False, want_f32=True)
     st.feat = feat
     return feat, st, x_out
+
+
+# ----------------------------------------------------------------------------------------------- forward-only read-outs
+def _trunk_prefix(spec: ViTSpec, depth):
+    """The same ViT cut behind its first `depth` blocks (the block table of a descriptor may be any prefix of the model's)."""
+    return replace(spec, trunk=replace(spec.trunk, depth=depth, block_names=spec.trunk.block_names[:depth]))
+
+
+def vit_streams(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, depths, drop_scales=None, dropout=None):
+    """Residual stream f32 [n_tok, D] behind the first k blocks for every k in `depths` (ascending, 1 <= k <= depth), nothing saved
+    for a backward: lafs_trunk_forward on prefix descriptors over ONE token assembly.  The last entry at k = depth is bit for bit
+    the stream of vit_forward.  Returns (embedded tokens f32 [n_tok, D], [stream per k])."""
+    dev = imgs[0].device
+    _, st, x = vit_forward(arena, _trunk_prefix(spec, depths[0]), geom, imgs, pos_tokens, drop_scales, save=False, dropout=dropout)
+    outs = [x]
+    p_trunk, _, dseed, dstep = st.dropout
+    for k in depths[1:]:
+        desc = make_trunk_desc(arena, _trunk_prefix(spec, k).trunk, geom, drop_scales, with_grad=False, dropout_p=p_trunk,
+                               dropout_seed=dseed, dropout_step=dstep)
+        x = torch.empty(geom.n_tok, spec.trunk.dim, device=dev, dtype=f32)
+        call("lafs_trunk_forward", C.byref(desc), _p(st.x_in), _p(x), _p(trunk_workspace(desc, False, dev)), 0)
+        outs.append(x)
+    return st.x_in, outs
+
+
+LN_TWO_ROW_MIN = 4096               # lafs_layernorm_fwd switches to its two-rows-per-wave kernel from this many rows on
+
+
+def vit_final_norm_rows(arena, spec: ViTSpec, geom: PackedGeometry, x):
+    """The model's final LayerNorm on EVERY token row, f32 [n_tok, D].  vit_forward normalises the n_seq gathered cls rows in one
+    launch; the two kernels lafs_layernorm_fwd chooses between by row count sum in different orders, so the rows go in slices that
+    make the choice that launch makes: the cls rows of the result are bit for bit the features of vit_forward."""
+    D, pre = spec.trunk.dim, spec.prefix
+    out = torch.empty(geom.n_tok, D, device=x.device, dtype=f32)
+    stats = torch.empty(geom.n_tok, 2, device=x.device, dtype=f32)
+    g, b = arena.view(arena.master, pre + spec.final_g), arena.view(arena.master, pre + spec.final_b)
+    step = geom.n_tok if geom.n_seq >= LN_TWO_ROW_MIN else LN_TWO_ROW_MIN - 1
+    for r0 in range(0, geom.n_tok, step):
+        R = min(step, geom.n_tok - r0)
+        call("lafs_layernorm_fwd", _p(x[r0:]), D, _p(g), _p(b), spec.trunk.ln_eps, None, D, _p(out[r0:]), D, _p(stats[r0:]), R, D)
+    return out
+
+
+def vit_block_probs(arena, spec: ViTSpec, geom: PackedGeometry, x, layer, q_rows=0):
+    """Attention probabilities of block `layer` from the residual stream `x` in front of it (the embedded tokens for layer 0):
+    LayerNorm 1 and the qkv GEMM of the block as the trunk runs them (bf16 shadow weights), then lafs_attention_probs.
+    One crop resolution per call.  Returns f32 [n_seq, heads, q_rows or N, N]."""
+    if len(geom.groups) != 1:
+        raise _lib.LafsHipError("attention read-out takes one crop resolution per call")
+    t, nm = spec.trunk, spec.trunk.block_names[layer]
+    m = lambda k: arena.view(arena.master, nm[k])
+    h, _, _ = ops.layernorm_fwd(x, m("ln1_g"), m("ln1_b"), t.ln_eps)
+    qkv = ops.gemm_nt(h, arena.bf(nm["w_qkv"]), _lib.EPI_BF16, bias=m("b_qkv") if nm.get("b_qkv") else None)
+    return ops.attention_probs(qkv, geom.cu_seqlens, geom.max_len, t.heads, t.attn_scale, q_rows)
 
 
 def vit_backward_begin(arena, spec: ViTSpec, st: ViTState, dfeat, g_buf=None):

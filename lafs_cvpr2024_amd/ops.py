@@ -299,6 +299,18 @@ def attention_bwd(qkv, out, dout, lse, cu_seqlens, max_len, heads, scale):
     return dqkv
 
 
+def attention_probs(qkv, cu_seqlens, max_len, heads, scale, q_rows=0):
+    """softmax(scale q k^T) itself, f32 [n_seq, heads, nq, max_len] with nq = q_rows or max_len (lafs_attention_probs): what
+    attention_fwd used, for inspection.  Padding rows / columns of shorter sequences are zeros."""
+    _chk(qkv, bf16, "qkv"); _chk(cu_seqlens, torch.int32, "cu_seqlens")
+    n_seq = cu_seqlens.numel() - 1
+    nq = q_rows if q_rows > 0 else max_len
+    # (a bad argument is the entry point's to refuse, with its reason: the buffer only has to exist)
+    probs = torch.empty(max(n_seq, 1), max(heads, 1), max(nq, 1), max(max_len, 1), device=qkv.device, dtype=torch.float32)
+    call("lafs_attention_probs", _p(qkv), _ld(qkv), _p(cu_seqlens), n_seq, max_len, heads, scale, q_rows, _p(probs))
+    return probs
+
+
 def patchify(img, order=_lib.PATCH_ORDER_CHW):
     _chk(img, torch.float32, "img")
     B, _, S, _ = img.shape

@@ -180,6 +180,36 @@ class VisionTransformer(nn.Module):
     def forward(self, x):
         return self.forward_groups([x])
 
+    def _inspect_inputs(self, x):
+        """One crop batch as the packed passes take it: (geometry, [images], [position table]) -- the table resampled as `forward` does."""
+        if x.dim() != 4:
+            raise _lib.LafsHipError("VisionTransformer expects NCHW crops")
+        self._ensure_arena()
+        n = (x.shape[-1] // 8) ** 2
+        pos = self.interpolate_pos_encoding(torch.empty(1, n + 1, 0), x.shape[-2], x.shape[-1])[0]
+        geom = Fn.geometry([(x.shape[0], x.shape[-1])], x.device)
+        return geom, [x.contiguous().float()], [pos.detach().contiguous()]
+
+    @torch.no_grad()
+    def get_last_selfattention(self, x):
+        """Attention probabilities of the last block, f32 [B, heads, N, N] with N = 1 + (H/8)(W/8) (reference :217-224): the fused
+        forward never stores them, so the blocks in front of the last one run as usual and lafs_attention_probs forms P from the last
+        block's own q and k."""
+        geom, imgs, pos = self._inspect_inputs(x)
+        drop = self._sample_drop_scales(geom) if self.training else None
+        tokens, streams = Fn.vit_streams(self._arena, self._spec, geom, imgs, pos, [max(self.depth - 1, 1)], drop)
+        return Fn.vit_block_probs(self._arena, self._spec, geom, streams[0] if self.depth > 1 else tokens, self.depth - 1)
+
+    @torch.no_grad()
+    def get_intermediate_layers(self, x, n=1):
+        """Output tokens of the `n` last blocks, each through the final norm: list of f32 [B, N, D] in block order (reference :226-234)."""
+        if not 1 <= n <= self.depth:
+            raise ValueError(f"n must be in 1..{self.depth} (the number of blocks), got {n}")
+        geom, imgs, pos = self._inspect_inputs(x)
+        drop = self._sample_drop_scales(geom) if self.training else None
+        _, streams = Fn.vit_streams(self._arena, self._spec, geom, imgs, pos, list(range(self.depth - n + 1, self.depth + 1)), drop)
+        return [Fn.vit_final_norm_rows(self._arena, self._spec, geom, s).view(x.shape[0], geom.max_len, -1) for s in streams]
+
 
 def vit_tiny(patch_size=16, **kwargs):
     return VisionTransformer(patch_size=patch_size, embed_dim=192, depth=12, num_heads=3, mlp_ratio=4, qkv_bias=True,

@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Where the model looks: the cls -> patch attention of the last block, per head, as .npy and as a PNG overlay.
+
+  python tools/attention_maps.py --arch vit_small --checkpoint ckpt.pth --bin lfw.bin --out maps/
+  python tools/attention_maps.py --arch partfvit --random-init --dims 128,2,3,256 --out maps/      (smoke run, synthetic batch)
+
+--arch vit_tiny / vit_small / vit_base: the DINO ViT with patch 8 (VisionTransformer.get_last_selfattention); the r x r patch grid
+is upsampled x8 to the image.  --arch partfvit: Part-fViT with its landmark branch (ViT_face_landmark_patch8.get_selfattention):
+every patch's weight is spread over its 8 x 8 footprint at the predicted landmark, overlapping coverage is averaged and the
+landmark centres are marked -- the picture the reference's visualize_attentionmap_DINO_landmark draws (util/utils.py:808-990).
+
+Files: <out>/img<b>_head<h>.npy (f32: [r, r] for the ViT, [n] in landmark order for Part-fViT; plus img<b>_theta.npy [n, 2] pixels)
+and <out>/img<b>_head<h>.png.  The attention comes from the HIP read-out kernel; the drawing is host-side numpy + Pillow.
+"""
+import argparse
+import os
+import sys
+
+import numpy as np
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def get_args():
+    p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    p.add_argument("--arch", default="vit_small", choices=["vit_tiny", "vit_small", "vit_base", "partfvit"])
+    p.add_argument("--dims", default="", help="dim,depth,heads,mlp: a smaller model than the architecture's (smoke runs)")
+    p.add_argument("--checkpoint", default="", help="a state_dict, or a training checkpoint (its 'teacher' / 'state_dict' entry)")
+    p.add_argument("--random-init", dest="random_init", action="store_true", help="no checkpoint: seeded random weights")
+    p.add_argument("--bin", default="", help="verification set (.bin) to take the images from; default: a synthetic batch")
+    p.add_argument("--num", default=2, type=int, help="number of images")
+    p.add_argument("--image_size", default=112, type=int)
+    p.add_argument("--layer", default=-1, type=int, help="block to read (partfvit only; the ViT reads its last block)")
+    p.add_argument("--out", default="attention_maps")
+    return p.parse_args()
+
+
+def build_model(args):
+    from functools import partial
+    from lafs_cvpr2024_amd import vision_transformer as vits
+    from lafs_cvpr2024_amd.face_pre_pro.ViT_face import ViT_face_landmark_patch8
+    dims = [int(v) for v in args.dims.split(",")] if args.dims else None
+    if args.arch == "partfvit":
+        dim, depth, heads, mlp = dims or (768, 12, 11, 2048)
+        return ViT_face_landmark_patch8(loss_type="None", GPU_ID=None, num_class=1, image_size=args.image_size, patch_size=8, dim=dim,
+                                        depth=depth, heads=heads, mlp_dim=mlp, with_land=True)
+    if dims:
+        dim, depth, heads, mlp = dims
+        return vits.VisionTransformer(img_size=[args.image_size], patch_size=8, embed_dim=dim, depth=depth, num_heads=heads,
+                                      mlp_ratio=mlp / dim, qkv_bias=True, norm_layer=partial(torch.nn.LayerNorm, eps=1e-6))
+    return getattr(vits, args.arch)(patch_size=8, img_size=[args.image_size])
+
+
+def load_weights(model, path):
+    ck = torch.load(path, map_location="cpu", weights_only=False)
+    sd = ck.get("teacher", ck.get("state_dict", ck)) if isinstance(ck, dict) else ck
+    own = model.state_dict()
+    clean = {}
+    for k, v in sd.items():
+        k = k.replace("module.", "").replace("backbone.", "").replace("encoder.", "")
+        if k in own and tuple(own[k].shape) == tuple(v.shape):
+            clean[k] = v
+    if not clean:
+        raise SystemExit(f"{path}: no tensor of the checkpoint fits --arch (wrong architecture?)")
+    model.load_state_dict(clean, strict=False)
+    print(f"loaded {len(clean)} of {len(own)} tensors from {path}")
+
+
+def load_images(args):
+    """uint8 [B, 3, S, S]"""
+    if args.bin:
+        from lafs_cvpr2024_amd.verification import load_bin
+        data, _ = load_bin(args.bin, (args.image_size, args.image_size))
+        return data[:args.num]
+    g = torch.Generator().manual_seed(0)                           # smooth blobs: something to look at under the overlay
+    low = torch.rand(args.num, 3, args.image_size // 8, args.image_size // 8, generator=g)
+    return (torch.nn.functional.interpolate(low, scale_factor=8, mode="bilinear") * 255).to(torch.uint8)
+
+
+def heat_rgb(h):
+    """[H, W] in 0..1 -> uint8 [H, W, 3]: blue -> red ramp."""
+    h = np.clip(h, 0.0, 1.0)
+    return (np.stack([h, 1.0 - np.abs(2.0 * h - 1.0), 1.0 - h], -1) * 255).astype(np.uint8)
+
+
+def overlay(img_u8, heat):
+    """img uint8 [3, S, S], heat [S, S] >= 0 (NaN: not covered) -> uint8 [S, S, 3]"""
+    img = img_u8.transpose(1, 2, 0).astype(np.float32)
+    covered = ~np.isnan(heat)
+    top = np.nanmax(heat) if covered.any() else 0.0
+    h = np.where(covered, heat / top if top > 0 else 0.0, 0.0)
+    out = np.where(covered[..., None], 0.45 * img + 0.55 * heat_rgb(h).astype(np.float32), img)
+    return out.astype(np.uint8)
+
+
+def landmark_heat(w, theta, S):
+    """Part-fViT: weight w[j] over the 8 x 8 footprint centred at theta[j] = (x, y) px; overlaps averaged; NaN where no patch lies."""
+    acc, cnt = np.zeros((S, S), np.float64), np.zeros((S, S), np.int64)
+    for wj, (x, y) in zip(w, theta):
+        x0, y0 = int(round(float(x))) - 4, int(round(float(y))) - 4
+        xs, ys = slice(max(x0, 0), min(x0 + 8, S)), slice(max(y0, 0), min(y0 + 8, S))
+        acc[ys, xs] += wj
+        cnt[ys, xs] += 1
+    return np.where(cnt > 0, acc / np.maximum(cnt, 1), np.nan)
+
+
+def main():
+    args = get_args()
+    if bool(args.checkpoint) == bool(args.random_init):
+        raise SystemExit("give either --checkpoint or --random-init")
+    from PIL import Image
+    torch.manual_seed(0)
+    model = build_model(args)
+    if args.checkpoint:
+        load_weights(model, args.checkpoint)
+    model.eval()
+    u8 = load_images(args)
+    S = u8.shape[-1]
+    x = (u8.float() / 255.0 * 2.0 - 1.0).cuda()                    # the training feed's scaling
+    if args.arch == "partfvit":
+        from lafs_cvpr2024_amd.vision_transformer import attach_arena
+        attach_arena(model)                                        # moves the landmark CNN (stock PyTorch) to the device too
+        attn, theta = model.get_selfattention(x, layer=args.layer, cls_only=True)
+        cls = attn[:, :, 0, 1:].cpu().numpy()                      # [B, heads, n] in landmark order
+        theta = theta.detach().float().cpu().numpy()
+    else:
+        cls = model.get_last_selfattention(x)[:, :, 0, 1:].cpu().numpy()
+        r = S // 8
+        cls = cls.reshape(cls.shape[0], cls.shape[1], r, r)
+    os.makedirs(args.out, exist_ok=True)
+    img = u8.numpy()
+    for b in range(cls.shape[0]):
+        if args.arch == "partfvit":
+            np.save(os.path.join(args.out, f"img{b}_theta.npy"), theta[b])
+        for h in range(cls.shape[1]):
+            np.save(os.path.join(args.out, f"img{b}_head{h}.npy"), cls[b, h])
+            if args.arch == "partfvit":
+                pic = overlay(img[b], landmark_heat(cls[b, h], theta[b], S))
+                for px, py in np.clip(np.rint(theta[b]).astype(int), 0, S - 1):
+                    pic[py, px] = 255                              # landmark centres
+            else:
+                pic = overlay(img[b], np.kron(cls[b, h], np.ones((8, 8), np.float32)))
+            Image.fromarray(pic).save(os.path.join(args.out, f"img{b}_head{h}.png"))
+    print(f"wrote {cls.shape[0] * cls.shape[1]} maps ({cls.shape[0]} images x {cls.shape[1]} heads) to {args.out}")
+
+
+if __name__ == "__main__":
+    main()

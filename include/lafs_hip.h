@@ -308,7 +308,12 @@ int lafs_debug_dropout_mask(int rows, int cols, float drop_p, uint32_t drop_seed
 int lafs_attention_fwd(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
                        float scale, void* out_bf16, int ldo, float* lse, hipStream_t stream);
 /* dqkv(bf16) [T, 3*H*64] from dout(bf16) [T, H*64], out(bf16) and lse(f32) [T, H] of the forward: one launch per call (Q, K, V,
- * dO of a (sequence, head) staged once; delta = rowsum(dO * O) formed on the way in). */
+ * dO of a (sequence, head) staged once; delta = rowsum(dO * O) formed on the way in).
+ * Padded positions (the tiles are 16 rows; a sequence's last tile and the tiles up to max_len's dispatch class are padding): both
+ * entry points write exactly the rows of the T tokens and the columns of their H*64 (3*H*64) channels, nothing else, and a padded
+ * position never contributes to a stored value, whatever the logits: padded keys are excluded from the forward's maximum and sum
+ * and from dQ (their weight against a real query would be exp(-lse), which overflows for lse < -88.7), padded queries carry
+ * dO = 0, Q = 0.  Finite inputs with finite fp32 logits give finite outputs for every lse a row can have. */
 int lafs_attention_bwd(const void* qkv, int ldqkv, const void* out_bf16, int ldo, const void* dout_bf16, int lddo,
                        const float* lse, const int32_t* cu_seqlens, int n_seq, int max_len, int heads, float scale,
                        void* dqkv, int lddqkv, hipStream_t stream);

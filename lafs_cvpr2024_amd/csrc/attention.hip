@@ -242,9 +242,13 @@ __global__ __launch_bounds__(NW * 64) void attn_fwd_kernel(AttnArgs a) {
 // streams the key tiles); both only read LDS.  Against the three-kernel form (delta, dQ, dK/dV) the pair's operands cross HBM
 // once instead of 2-3 times: 4.4 -> 3.1 bytes per token-channel.
 //
-// No masks in either phase: rows beyond the sequence are ZERO in all four tiles, so an out-of-range query contributes
-// dO = 0 / Q = 0 to dV / dK, an out-of-range key contributes K = 0 to dQ, and out-of-range outputs are never stored; the
-// probabilities of padded positions only have to stay finite (their lse entry is 0).
+// Rows beyond the sequence are ZERO in all four tiles and their lse / delta entries are 0.  A padded QUERY therefore has score 0 and
+// p = exp2(0) = 1 against every key, with dO = 0 and Q = 0: it adds exact zeros to dV and dK, no mask needed.  A padded KEY has score
+// 0 against a real query, i.e. p = exp(-lse): finite only while lse > -88.7, and a row whose logits are all strongly negative is
+// legal input.  In the dK/dV phase that p (and its dS) only reaches the padded key's own output column, which is never stored; in
+// the dQ phase it would meet the key's zero K row in the MFMA (inf * 0 = NaN in a real dQ row), so the dQ phase sets dS of padded
+// keys to zero -- in tiles that have any, under a wave-uniform branch as in the forward; elsewhere the zero K row made the same
+// contribution, so finite results are unchanged bit for bit.
 // Each wave item covers TPI consecutive 16-row tiles, so every LDS fragment (the MFMA A operand) feeds TPI MFMAs: with one
 // tile per item the loops ask the LDS for 256 B/clk/CU at MFMA rate -- twice what it delivers -- and sit in LDS issue stalls.
 
@@ -390,6 +394,13 @@ __device__ __forceinline__ void bwd_phase_queries(const unsigned char* QsF, cons
 #pragma unroll
           for (int r = 0; r < 4; ++r)
             ds[x][tt * 4 + r] = __builtin_amdgcn_exp2f(fmaf(sx[r], c2, nlse_q[x])) * fmaf(dp[r], scale, ndel_q[x]);
+        }
+        if (t * 16 + 16 > len) {                              // wave-uniform: only a tile with padded keys pays for the mask
+#pragma unroll
+          for (int x = 0; x < TPI; ++x)
+#pragma unroll
+            for (int r = 0; r < 4; ++r)
+              if (t * 16 + g * 4 + r >= len) ds[x][tt * 4 + r] = 0.f;
         }
       } else {
 #pragma unroll

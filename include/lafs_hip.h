@@ -572,6 +572,25 @@ int lafs_mixup_normalize(const uint8_t* src_u8, float* dst, int B, int S, float 
 int lafs_margin_softmax_ce_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, float lam,
                                 const float* lam_dev, float s, float m, int margin_type, float loss_scale, void* dcos, int lddc,
                                 float* loss_out, float* row_ws, float* part_ws, hipStream_t stream);
+/* The mixing recipe beyond batch-mode mixup (util/mixup_my.py:27-81 CutMix boxes, :114-187 pair / elem modes, :18-24 label smoothing).
+ * One parameter row per sample in DEVICE memory, LAFS_MIX_WORDS 32-bit words each, read when the kernels run (a captured micro-step
+ * replays with new parameters):  [0] lambda (f32; after CutMix's area correction), [1] CutMix flag (i32, 0 / 1), [2..5] box yl, yh, xl,
+ * xh (i32; rows [yl, yh) x columns [xl, xh)).  The partner of row b is row B-1-b in every mode (:157, :174, :196).
+ * lafs_mix_normalize: src u8 [B,3,S,S] -> dst f32, x/255*2-1 folded in.  Flag 0: lam*x[b] + (1-lam)*x[B-1-b] with the arithmetic of
+ *   lafs_mixup_normalize (lambda 1: the row passes through); flag 1: x[B-1-b] inside the box, x[b] outside (all three channels). */
+enum { LAFS_MIX_LAM = 0, LAFS_MIX_CUT, LAFS_MIX_YL, LAFS_MIX_YH, LAFS_MIX_XL, LAFS_MIX_XH, LAFS_MIX_WORDS };
+int lafs_mix_normalize(const uint8_t* src_u8, float* dst, int B, int S, const int32_t* table, hipStream_t stream);
+/* lafs_margin_softmax_ce_bf16 with a lambda per row and label smoothing `eps`: lambda of row b = lam_rows[b * lam_stride] (f32 in
+ * device memory; lam_stride = 1: a plain array, LAFS_MIX_WORDS: the table above).  Target of row b, never materialised:
+ *   y_k = eps/C + (1-eps) (lam_b [k = y1[b]] + (1-lam_b) [k = y2[b]])     (util/mixup_my.py:18-24; equal classes: the summed weight)
+ * entering the CosFace margin itself, z_k = s (cos_k - m y_k) (face_pre_pro/ViT_face.py:69-73);  loss_b = lse(z) - sum_k y_k z_k
+ * (timm SoftTargetCrossEntropy, train_largescale.py:820) = lse(z) - eps/C sum_k z_k - the two spikes;  dcos = loss_scale/B (softmax - y) s.
+ * Same (row, chunk) decomposition, bf16 dcos [B, lddc] with zeroed pad columns and y2 == NULL convention; with eps = 0 and one lambda on
+ * every row, loss and dcos equal lafs_margin_softmax_ce_bf16's bit for bit.  margin_type 1 (ArcFace) treats the two spikes as that
+ * entry point does and requires eps = 0.  row_ws f32 [B]; part_ws f32 [B * 48] (per row and chunk: max, sum exp, sum z). */
+int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, const float* lam_rows,
+                                    int lam_stride, float eps, float s, float m, int margin_type, float loss_scale, void* dcos, int lddc,
+                                    float* loss_out, float* row_ws, float* part_ws, hipStream_t stream);
 /* dst(i32)[n] = src(i64)[n]: the loader's int64 labels (train_largescale.py:842) into the kernels' index type without an ATen cast */
 int lafs_cast_i64_i32(const int64_t* src, int32_t* dst, int n, hipStream_t stream);
 /* Patch-vector gradient f32 [B, (S/8)^2, 192] -> image gradient f32 [B, 3, S, S]: the inverse re-indexing of lafs_patchify (the

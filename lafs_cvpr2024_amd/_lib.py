@@ -80,6 +80,8 @@ CHUNK = 1024
 SEG_DECAY, SEG_LAST_LAYER, SEG_TRAINABLE, SEG_LOW_DECAY, SEG_OVERWRITTEN = 1, 2, 4, 8, 16
 HP_LR, HP_WD, HP_BETA1, HP_BETA2, HP_EPS, HP_CLIP, HP_EMA_M, HP_FREEZE_LAST, HP_GRAD_SCALE, HP_WD_LOW, HP_STEP, HP_MIX_LAM = range(12)
 HP_COUNT = 16
+# parameter row of lafs_mix_normalize / lafs_margin_softmax_ce_mix_bf16 (enum LAFS_MIX_* of lafs_hip.h)
+MIX_LAM, MIX_CUT, MIX_YL, MIX_YH, MIX_XL, MIX_XH, MIX_WORDS = range(7)
 OPT_SIDE_STREAMS, OPT_ROW_CHAINS, OPT_KRES_MASK, OPT_KRES_MIN_ITEMS, OPT_NT_WIDE, OPT_NT_TALL, OPT_COMM_CUS, OPT_NT_BIG, OPT_MLP_FUSED = range(9)
 
 vp, i32, i64, f32, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
@@ -179,6 +181,8 @@ _PROTOS = {
     "lafs_landmark_theta": [vp, i32, i32, vp, f32, vp, i32, vp],
     "lafs_mixup_normalize": [vp, vp, i32, i32, f32, vp],
     "lafs_margin_softmax_ce_bf16": [vp, i32, i32, i32, vp, vp, f32, vp, f32, f32, i32, f32, vp, i32, vp, vp, vp],
+    "lafs_mix_normalize": [vp, vp, i32, i32, vp],
+    "lafs_margin_softmax_ce_mix_bf16": [vp, i32, i32, i32, vp, vp, vp, i32, f32, f32, f32, i32, f32, vp, i32, vp, vp, vp],
     "lafs_cast_i64_i32": [vp, vp, i32],
     "lafs_dino_head_loss": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32, f32, vp, vp],
     "lafs_transpose_bf16": [vp, i32, i32, i32, vp, i32],

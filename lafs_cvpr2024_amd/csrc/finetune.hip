@@ -4,6 +4,8 @@
 //   SoftTargetCrossEntropy (timm)   train_largescale.py:602,820
 //   Mixup batch mode                util/mixup_my.py:189-200, 18-24  (target has <= 2 non-zeros per row, so it is
 //                                   passed as (y1, y2, lam) and the dense [B,C] matrix is never materialised)
+//   CutMix, pair / elem modes, label smoothing   util/mixup_my.py:27-81, 114-187 (a parameter row per sample; the smoothed
+//                                   target is dense but has closed form: a constant plus two spikes)
 //   extract_patches_pytorch_gridsample   face_pre_pro/ViT_face.py:1615-1656 (n sequential grid_sample launches -> 1)
 #include "common.hpp"
 #include "lafs_hip.h"
@@ -161,6 +163,111 @@ __global__ __launch_bounds__(256) void margin_ce_grad_kernel(const float* __rest
     for (int k = C + threadIdx.x; k < lddc; k += 256) drow[k] = 0;
 }
 
+// ---- the same (row, chunk) loss with a lambda PER ROW and label smoothing (util/mixup_my.py:18-24 with smoothing > 0; pair / elem
+// modes :152-187; CutMix's area-corrected lambda :71-81).  The target of row b is dense,
+//     y_k = off + (1 - eps) (lam_b [k = a1] + (1 - lam_b) [k = a2]),   off = eps / C,
+// and enters the CosFace margin itself, z_k = s (cos_k - m y_k) (ViT_face.py:69-73); it is never built:
+//     loss_b = lse(z) - sum_k y_k z_k = lse(z) - off sum_k z_k - (the two spikes),      d loss / d z_k = softmax_k - y_k.
+// Pass 1 therefore keeps a third per-chunk partial, sum_k z_k, beside (max, sum exp): part f32 [B, NCH, 3].  With eps = 0 every
+// expression below reduces exactly (off = 0, 1 - eps = 1) to the one of margin_ce_part_kernel / margin_ce_grad_kernel, evaluated
+// in the same order: the results are bit-identical.  lam of row b = lam_rows[b * lam_stride] (the parameter table of
+// lafs_mix_normalize, read when the kernel runs).
+struct MixLabel {
+  int a1, a2; float w1, w2, off;
+  __device__ __forceinline__ float operator()(int k) const { return off + (((k == a1) ? w1 : 0.f) + ((k == a2) ? w2 : 0.f)); }
+};
+__device__ __forceinline__ MixLabel mix_label(const int* y1, const int* y2, const float* lam_rows, int lam_stride, float eps, int b, int B,
+                                              int C) {
+  MixLabel L;
+  mce_labels(y1, y2, b, B, L.a1, L.a2);
+  const float lam = lam_rows[(size_t)b * lam_stride], on = 1.f - eps;
+  L.w1 = on * lam; L.w2 = on * (1.f - lam); L.off = eps / (float)C;
+  return L;
+}
+__global__ __launch_bounds__(256) void margin_ce_mix_part_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
+                                                                const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
+                                                                float eps, float s, float m, int type, float* __restrict__ part) {
+  __shared__ float sm[4], ss[4], sz[4];
+  const int b = blockIdx.y, ch = blockIdx.x;
+  const float* row = cosv + (size_t)b * ld;
+  const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, eps, b, B, C);
+  const int per = ((C + MCE_NCH - 1) / MCE_NCH + 3) & ~3, k0 = ch * per, k1 = min(C, k0 + per);
+  float mx = -INFINITY, sum = 0.f, zs = 0.f;
+  for (int k = k0 + threadIdx.x; k < k1; k += 256) {
+    const float z = margin_logit(row[k], label(k), s, m, type);
+    zs += z;
+    if (z > mx) { sum = sum * __expf(mx - z) + 1.f; mx = z; } else { sum += __expf(z - mx); }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float mo = __shfl_xor(mx, o, 64), so = __shfl_xor(sum, o, 64);
+    const float mn = fmaxf(mx, mo);
+    sum = (mn == -INFINITY) ? 0.f : sum * __expf(mx - mn) + so * __expf(mo - mn);
+    mx = mn;
+  }
+  zs = wave_sum(zs);
+  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = mx; ss[threadIdx.x >> 6] = sum; sz[threadIdx.x >> 6] = zs; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+    float S = 0.f;
+    for (int w = 0; w < 4; ++w) if (sm[w] != -INFINITY) S += ss[w] * __expf(sm[w] - M);
+    float* p = part + ((size_t)b * MCE_NCH + ch) * 3;
+    p[0] = M; p[1] = S; p[2] = (sz[0] + sz[1]) + (sz[2] + sz[3]);
+  }
+}
+__global__ __launch_bounds__(256) void margin_ce_mix_grad_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
+                                                                const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
+                                                                float eps, float s, float m, int type, float gscale,
+                                                                const float* __restrict__ part, bf16_t* __restrict__ dcos, int lddc,
+                                                                float* __restrict__ row_loss) {
+  const int b = blockIdx.y, ch = blockIdx.x;
+  const float* row = cosv + (size_t)b * ld;
+  const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, eps, b, B, C);
+  const int a1 = label.a1, a2 = label.a2;
+  const float* prow = part + (size_t)b * MCE_NCH * 3;
+  float M = -INFINITY;
+#pragma unroll
+  for (int c = 0; c < MCE_NCH; ++c) M = fmaxf(M, prow[c * 3]);
+  float S = 0.f;
+#pragma unroll
+  for (int c = 0; c < MCE_NCH; ++c) {
+    const float mc = prow[c * 3];
+    if (mc != -INFINITY) S += prow[c * 3 + 1] * __expf(mc - M);
+  }
+  const float lse = M + __logf(S);
+  if (ch == 0 && threadIdx.x == 0) {
+    // the spikes' share of sum_k y_k z_k: (y_k - off) z_k at a1 and a2 (a1 == a2: the summed weight, once)
+    float dot = (label(a1) - label.off) * margin_logit(row[a1], label(a1), s, m, type);
+    if (a2 != a1) dot += (label(a2) - label.off) * margin_logit(row[a2], label(a2), s, m, type);
+    float Zs = 0.f;
+    for (int c = 0; c < MCE_NCH; ++c) Zs += prow[c * 3 + 2];
+    row_loss[b] = (lse - dot) - label.off * Zs;             // sum_k y_k = 1
+  }
+  const int per = ((C + MCE_NCH - 1) / MCE_NCH + 3) & ~3, k0 = ch * per, k1 = min(C, k0 + per);
+  bf16_t* drow = dcos + (size_t)b * lddc;
+  for (int k = k0 + 4 * threadIdx.x; k < k1; k += 1024) {           // 4 consecutive classes per thread: 16-byte loads, 8-byte stores
+    if (k + 3 < k1) {
+      const float4 c4 = *reinterpret_cast<const float4*>(row + k);
+      const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
+      float g[4];
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float y = label(k + e);
+        g[e] = gscale * (__expf(margin_logit(cv[e], y, s, m, type) - lse) - y) * margin_dlogit(cv[e], y, s, m, type);
+      }
+      *reinterpret_cast<uint2*>(drow + k) = make_uint2(pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]));
+    } else {
+      for (int e = 0; e < 4 && k + e < k1; ++e) {
+        const float c = row[k + e], y = label(k + e);
+        drow[k + e] = f2bf(gscale * (__expf(margin_logit(c, y, s, m, type) - lse) - y) * margin_dlogit(c, y, s, m, type));
+      }
+    }
+  }
+  if (ch == MCE_NCH - 1)
+    for (int k = C + threadIdx.x; k < lddc; k += 256) drow[k] = 0;
+}
+
 __global__ __launch_bounds__(256) void cast_i64_i32_kernel(const long long* __restrict__ src, int* __restrict__ dst, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i < n) dst[i] = (int)src[i];
@@ -198,6 +305,28 @@ __global__ __launch_bounds__(256) void mixup_norm_kernel(const uint8_t* __restri
     const float x = (float)src[i] * (2.f / 255.f) - 1.f;
     const float xf = (float)src[(B - 1 - b) * per + r] * (2.f / 255.f) - 1.f;
     dst[i] = (lam == 1.f) ? x : x * lam + xf * (1.f - lam);
+  }
+}
+
+// u8 -> [-1,1] with this micro-step's mixing folded in, per ROW (util/mixup_my.py:152-200: batch, pair and elem modes all mix row b
+// with row B-1-b of the unmixed batch).  tab: LAFS_MIX_WORDS 32-bit words per row -- lambda (f32), CutMix flag, box yl, yh, xl, xh --
+// read when the kernel runs.  A CutMix row takes its partner inside the box ([yl, yh) x [xl, xh), every channel: :163, :180-181, :196)
+// and itself outside; any other row is blended with mixup_norm_kernel's arithmetic (lambda 1: the row passes through).
+__global__ __launch_bounds__(256) void mix_norm_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int B, int S,
+                                                      const int* __restrict__ tab) {
+  const size_t per = (size_t)3 * S * S, total = (size_t)B * per;
+  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
+    const size_t b = i / per, r = i % per;
+    const int* t = tab + b * LAFS_MIX_WORDS;
+    const float lam = __int_as_float(t[0]);
+    const float x = (float)src[i] * (2.f / 255.f) - 1.f;
+    const float xf = (float)src[(B - 1 - b) * per + r] * (2.f / 255.f) - 1.f;
+    if (t[1] != 0) {
+      const int px = (int)(r % S), py = (int)((r / S) % S);
+      dst[i] = (py >= t[2] && py < t[3] && px >= t[4] && px < t[5]) ? xf : x;
+    } else {
+      dst[i] = (lam == 1.f) ? x : x * lam + xf * (1.f - lam);
+    }
   }
 }
 
@@ -396,6 +525,28 @@ extern "C" int lafs_margin_softmax_ce_bf16(const float* cos, int ld, int B, int 
   return LAFS_OK;
 }
 
+extern "C" int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2,
+                                               const float* lam_rows, int lam_stride, float eps, float s, float m, int margin_type,
+                                               float loss_scale, void* dcos, int lddc, float* loss_out, float* row_ws, float* part_ws,
+                                               hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(cos && y1 && lam_rows && dcos && loss_out && row_ws && part_ws && B > 0 && C > 0 && ld >= C && lddc >= C, "bad operand");
+  LAFS_CHECK_ARG(ld % 4 == 0 && lddc % 4 == 0, "row strides must be multiples of 4 elements");
+  LAFS_CHECK_ARG(lam_stride >= 1, "lam_stride counts 32-bit words between two rows' lambdas (>= 1)");
+  LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
+  LAFS_CHECK_ARG(eps >= 0.f && eps < 1.f, "label smoothing must lie in [0, 1)");
+  LAFS_CHECK_ARG(eps == 0.f || margin_type == 0, "label smoothing needs the CosFace margin (ArcFace has no margin for a dense target)");
+  hipLaunchKernelGGL(margin_ce_mix_part_kernel, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, eps, s, m,
+                     margin_type, part_ws);
+  LAFS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(margin_ce_mix_grad_kernel, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, eps, s, m,
+                     margin_type, loss_scale / (float)B, part_ws, (bf16_t*)dcos, lddc, row_ws);
+  LAFS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, stream, row_ws, B, 1.0f / (float)B, loss_out);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
 extern "C" int lafs_cast_i64_i32(const int64_t* src, int32_t* dst, int n, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(src && dst && n > 0, "bad operand");
@@ -421,6 +572,16 @@ extern "C" int lafs_mixup_normalize(const uint8_t* src_u8, float* dst, int B, in
   size_t blocks = ((size_t)B * per + 255) / 256;
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(mixup_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src_u8, dst, B, per, lam, lam_dev);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_mix_normalize(const uint8_t* src_u8, float* dst, int B, int S, const int32_t* table, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(src_u8 && dst && table && B > 0 && S > 0, "bad operand");
+  size_t blocks = ((size_t)B * 3 * S * S + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(mix_norm_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, src_u8, dst, B, S, table);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }

@@ -3,6 +3,9 @@
     u8 batch -> (x/255*2-1) + batch mixup (one kernel) -> [trainable landmark CNN -> theta -> patch gather] -> Part-fViT trunk ->
     L2-normalised embedding x L2-normalised class centres (MFMA GEMM) -> fused margin + softmax + soft-target CE (the dense [B, C]
     mixup target is never built: it has <= 2 non-zeros per row) -> backward -> every `acc_step` micro-steps: AdamW over the flat arena.
+The rest of the reference's mixing recipe (CutMix, pair / elem modes, label smoothing: util/mixup_my.py, train_largescale.py:383-395)
+runs through lafs_mix_normalize and lafs_margin_softmax_ce_mix_bf16, driven by one parameter row per sample that is uploaded per
+micro-step and read by the kernels when they run; with the reference's defaults the step launches exactly what it launched before.
 
 Round 4: every per-step tensor is allocated once, no ATen kernel is left in a micro-step (labels, DropPath masks, operand
 transposes, the image gradient re-indexing and the gradient zeroing are lafs_* launches), the mixup lambda / step counter are read
@@ -45,10 +48,23 @@ def finetune_decay_group(name, param):
 
 class FinetuneEngine:
     def __init__(self, backbone: ViT_face_landmark_patch8, batch_size, acc_step=3, mixup_alpha=0.2, mixup_prob=0.1,
-                 s=64.0, m=0.4, margin_type=0, image_size=112, device=None, sharded_head=None, use_graph=None):
+                 s=64.0, m=0.4, margin_type=0, image_size=112, device=None, sharded_head=None, use_graph=None,
+                 cutmix_alpha=0.0, cutmix_minmax=None, switch_prob=0.5, mix_mode="batch", label_smoothing=0.0):
         """margin_type 0 = CosFace (the reference), 1 = ArcFace (parity unpinned), on the dense `backbone.loss.weight` head;
         `sharded_head` (a partial_fc.PartialFC) replaces it by the class-sharded head (CosFace: mixup targets as on the dense head).
-        use_graph: None = capture the micro-step whenever it is capturable (single rank, dense head; LAFS_FT_GRAPH=0 disables)."""
+        use_graph: None = capture the micro-step whenever it is capturable (single rank, dense head; LAFS_FT_GRAPH=0 disables).
+        cutmix_alpha / cutmix_minmax / switch_prob / mix_mode / label_smoothing: util.mixup_my.Mixup's arguments of the same meaning
+        (train_largescale.py:528-531).  Any of them away from the reference's default (0, None, -, 'batch', 0) selects the per-row
+        kernels; label smoothing needs the dense CosFace head."""
+        if mix_mode not in ("batch", "pair", "elem"):
+            raise _lib.LafsHipError(f"mix_mode must be 'batch', 'pair' or 'elem', not {mix_mode!r}")
+        if not 0.0 <= label_smoothing < 1.0:
+            raise _lib.LafsHipError("label_smoothing must lie in [0, 1)")
+        if label_smoothing > 0.0 and sharded_head is not None:
+            raise _lib.LafsHipError("label smoothing on the class-sharded head is not supported (a smoothed target over a sampled class "
+                                    "subset is not defined here): use the dense CosFace head")
+        if label_smoothing > 0.0 and margin_type != 0:
+            raise _lib.LafsHipError("label smoothing needs the CosFace margin: ArcFace has no margin for a dense target")
         if not isinstance(backbone, ViT_face_landmark_patch8) or (sharded_head is None and not hasattr(backbone, "loss")):
             raise _lib.LafsHipError("FinetuneEngine drives ViT_face_landmark_patch8(loss_type='CosFace') or a sharded head")
         if batch_size % 8:
@@ -56,6 +72,14 @@ class FinetuneEngine:
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
         self.model, self.B, self.acc_step = backbone, batch_size, acc_step
         self.mixup_alpha, self.mixup_prob = mixup_alpha, mixup_prob
+        self.label_smoothing = float(label_smoothing)
+        # per-row mixing (CutMix, pair / elem modes, smoothing): the reference's own class draws the parameters
+        self.mix_rows = cutmix_alpha > 0.0 or cutmix_minmax is not None or mix_mode != "batch" or label_smoothing > 0.0
+        self.mixer = None
+        if self.mix_rows:
+            from .util.mixup_my import Mixup
+            self.mixer = Mixup(mixup_alpha=mixup_alpha, cutmix_alpha=cutmix_alpha, cutmix_minmax=cutmix_minmax, prob=mixup_prob,
+                               switch_prob=switch_prob, mode=mix_mode, label_smoothing=label_smoothing)
         self.s, self.m, self.margin_type = float(s), float(m), margin_type
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.arena = attach_arena(backbone, self.device)
@@ -82,6 +106,9 @@ class FinetuneEngine:
         self.hyper = torch.zeros(_lib.HP_COUNT, device=dev, dtype=f32)
         self.hyper_ring = PinnedRing((_lib.HP_COUNT,), f32)     # asynchronous upload; a pageable copy would block the host
         self._hp = {}                                            # host copy of the hyper-parameters (every upload rewrites the whole vector)
+        if self.mix_rows:                                        # the micro-step's parameter rows (lafs_hip.h LAFS_MIX_*), uploaded the same way
+            self.mix_tab = torch.zeros(batch_size, _lib.MIX_WORDS, device=dev, dtype=torch.int32)
+            self.mix_ring = PinnedRing((batch_size, _lib.MIX_WORDS), torch.int32)
         # data parallelism (reference: DDP bucketed all-reduce overlapped with backward, train_largescale.py:676-677, 867): on the
         # last micro-step of an accumulation window the flat gradient goes out over RCCL in slices AS THE BACKWARD RETIRES
         # THEM -- the 0.6 GB margin head first (it is final before the trunk backward starts), then runs of blocks from the top,
@@ -130,7 +157,7 @@ class FinetuneEngine:
             self.inv_w = torch.empty(self.C, device=dev, dtype=f32)
             self.dwn = torch.empty(self.Cpad, D, device=dev, dtype=f32)
             self.row_ws = torch.empty(B, device=dev, dtype=f32)
-            self.part_ws = torch.empty(B * 32, device=dev, dtype=f32)
+            self.part_ws = torch.empty(B * (48 if self.mix_rows else 32), device=dev, dtype=f32)
             self.xn = torch.empty(B, D, device=dev, dtype=bf16)
             self.xn_t = torch.empty(D, B, device=dev, dtype=bf16)
             self.inv_x = torch.empty(B, device=dev, dtype=f32)
@@ -196,6 +223,35 @@ class FinetuneEngine:
             return float(np.random.beta(self.mixup_alpha, self.mixup_alpha))
         return 1.0
 
+    def draw_mix(self):
+        """(lam f32 [B], cut bool [B], box i32 [B, 4]) of this micro-step from util.mixup_my.Mixup.draw_params: the global np.random
+        stream moves exactly as the reference's Mixup.__call__ moves it."""
+        if not (self.mixup_alpha > 0.0 or self.mixer.cutmix_alpha > 0.0):
+            return np.ones(self.B, np.float32), np.zeros(self.B, bool), np.zeros((self.B, 4), np.int32)
+        return self.mixer.draw_params(self.B, (self.S, self.S))
+
+    def _upload_mix(self, mix):
+        """Validate one micro-step's per-row parameters and send them to the device table (pinned ring, outside the graph)."""
+        B, S = self.B, self.S
+        lam = np.array(np.broadcast_to(np.asarray(mix[0], dtype=np.float32), (B,)))      # (an own, writable copy)
+        cut = np.zeros(B, bool) if mix[1] is None else np.broadcast_to(np.asarray(mix[1], dtype=bool), (B,))
+        box = np.zeros((B, 4), np.int32) if mix[2] is None else np.broadcast_to(np.asarray(mix[2], dtype=np.int32), (B, 4))
+        if not (np.all(lam >= 0.0) and np.all(lam <= 1.0)):
+            raise _lib.LafsHipError("mixing lambdas must lie in [0, 1]")
+        if np.any(box < 0) or np.any(box > S):
+            raise _lib.LafsHipError(f"CutMix boxes must lie inside the {S}x{S} image")
+        if self.head is not None and self.head.margin_type != 0:
+            lam, cut = np.ones(B, np.float32), np.zeros(B, bool)      # ArcFace on the sharded head takes hard labels, unmixed images
+        self._mix = (lam, cut, box)
+
+        def fill(h):
+            h.zero_()
+            v = h.numpy()
+            v[:, _lib.MIX_LAM] = lam.view(np.int32)
+            v[:, _lib.MIX_CUT] = cut
+            v[:, _lib.MIX_YL:_lib.MIX_XH + 1] = box
+        self.mix_ring.upload(self.mix_tab, fill)
+
     def _upload_hyper(self, kw):
         self._hp.update(kw)
 
@@ -220,13 +276,21 @@ class FinetuneEngine:
         m = self.model
         return self.use_graph and (not m.with_land or self.cnn is not None)
 
-    def micro_step(self, inputs_u8, labels, lam=None):
+    def micro_step(self, inputs_u8, labels, lam=None, mix=None):
         """One forward/backward on a uint8 NCHW batch.  Gradients accumulate in the arena (loss pre-divided by acc_step).
+        lam: this micro-step's lambda instead of a draw (one blend lambda for the whole batch).  mix = (lam [B], cut [B] or None, box
+        [B, 4] or None): explicit per-row parameters as Mixup.draw_params returns them (engines built with a per-row option only).
         The FIRST micro-step after an optimizer step overwrites / zeroes the gradients itself: between optimizer_step and the next
         micro_step, arena.grad and p.grad hold the previous window's (stale) gradients unless `zero_after_step` is set."""
         a, m = self.arena, self.model
         a.ensure_fresh()
-        lam = self.draw_lambda() if lam is None else float(lam)
+        if mix is not None and not self.mix_rows:
+            raise _lib.LafsHipError("per-row mixing parameters need an engine built with cutmix / mix_mode / label_smoothing")
+        if self.mix_rows:
+            self._upload_mix(mix if mix is not None else ((lam, None, None) if lam is not None else self.draw_mix()))
+            lam = 1.0                                    # (the scalar lambda of the batch-mode kernels is not read)
+        else:
+            lam = self.draw_lambda() if lam is None else float(lam)
         if self.head is not None and self.head.margin_type != 0:
             lam = 1.0                                    # ArcFace on the sharded head takes hard labels (parity unpinned either way)
         self._lam = lam
@@ -320,7 +384,10 @@ class FinetuneEngine:
         hp = self.hyper
         if first:                                        # gradient of everything no kernel overwrites <- 0
             call("lafs_zero_chunks", _p(a.grad), _p(a.chunk_seg), _p(a.seg_flags), a.n_chunks, _lib.SEG_OVERWRITTEN)
-        call("lafs_mixup_normalize", _p(self.in_u8), _p(self.x), B, self.S, 1.0, _p(hp[_lib.HP_MIX_LAM:]))
+        if self.mix_rows:
+            call("lafs_mix_normalize", _p(self.in_u8), _p(self.x), B, self.S, _p(self.mix_tab))
+        else:
+            call("lafs_mixup_normalize", _p(self.in_u8), _p(self.x), B, self.S, 1.0, _p(hp[_lib.HP_MIX_LAM:]))
         drop = None
         if m.training and self.drop is not None:         # Residual_droppath: the same rate on both branches of every layer (:106-112)
             call("lafs_droppath_scales", _p(self.keep), m.depth, self.geom.n_seq, self.drop_seed, _p(hp[_lib.HP_STEP:]), _p(self.drop))
@@ -351,9 +418,12 @@ class FinetuneEngine:
             # demb is the gradient of the GLOBAL-batch mean loss, so the later all-reduce of the backbone gradients is a SUM.
             # soft (mixup) targets as the reference's margin head always gets them (train_largescale.py:802): the partner of row b is
             # row B-1-b of this rank's batch (util/mixup_my.py:189-200), its weight 1 - lambda
-            soft = self._lam != 1.0                      # (more than one rank: PartialFC takes the soft form on every rank, normalize_targets)
+            lam_h = self._lam
+            if self.mix_rows:                            # CutMix / pair / elem modes: the shard kernels' per-row lambda
+                lam_h = self.mix_tab.view(f32)[:, _lib.MIX_LAM] if bool((self._mix[0] != 1.0).any()) else 1.0     # (already uploaded)
+            soft = torch.is_tensor(lam_h) or lam_h != 1.0    # (more than one rank: PartialFC takes the soft form on every rank, normalize_targets)
             loss, demb = self.head.forward_backward(emb, self._labels, grad_scale=1.0 / self.acc_step,
-                                                    labels2=self._labels.flip(0) if soft else None, lam=self._lam)
+                                                    labels2=self._labels.flip(0) if soft else None, lam=lam_h)
             self.loss.copy_(loss.detach().view(1))
             yield from self._backward_trunk(st, demb, th, theta)
             return
@@ -364,8 +434,13 @@ class FinetuneEngine:
         ops.gemm_nt(self.xn, self.wn, _lib.EPI_F32, out=self.cos, n_cols=self.Cpad)
         # margin + softmax + soft-target CE; d/dcos leaves as bf16 (the operand of the two class-gradient GEMMs); the mixup partner of
         # row b is row B-1-b, lambda comes from device memory
-        call("lafs_margin_softmax_ce_bf16", _p(self.cos), self.Cpad, B, self.C, _p(self.y1), None, 1.0, _p(hp[_lib.HP_MIX_LAM:]), self.s,
-             self.m, self.margin_type, 1.0 / self.acc_step, _p(self.dcos), self.Cpad, _p(self.loss), _p(self.row_ws), _p(self.part_ws))
+        if self.mix_rows:                                # a lambda per row (read from the parameter table) and label smoothing
+            call("lafs_margin_softmax_ce_mix_bf16", _p(self.cos), self.Cpad, B, self.C, _p(self.y1), None, _p(self.mix_tab), _lib.MIX_WORDS,
+                 self.label_smoothing, self.s, self.m, self.margin_type, 1.0 / self.acc_step, _p(self.dcos), self.Cpad, _p(self.loss),
+                 _p(self.row_ws), _p(self.part_ws))
+        else:
+            call("lafs_margin_softmax_ce_bf16", _p(self.cos), self.Cpad, B, self.C, _p(self.y1), None, 1.0, _p(hp[_lib.HP_MIX_LAM:]), self.s,
+                 self.m, self.margin_type, 1.0 / self.acc_step, _p(self.dcos), self.Cpad, _p(self.loss), _p(self.row_ws), _p(self.part_ws))
         call("lafs_transpose_bf16", _p(self.dcos), B, self.Cpad, self.Cpad, _p(self.dcos_t), B)
         # d(emb_n) [B, D] = dcos @ Wn: reduction over the classes = the token axis of the wide-tile weight-gradient kernel (slices
         # + fold: no atomics, no zero fill)

@@ -140,7 +140,7 @@ class PartialFC:
 
     def forward_backward(self, emb, labels, grad_scale=1.0, labels2=None, lam=1.0):
         """emb f32 [B, D] (this rank's embeddings), labels [B] global class ids.  Soft (mixup) targets as the reference's margin head
-        takes them (train_largescale.py:802, ViT_face.py:69-73): labels2 [B] = the mixup partners' classes, lam = this rank's lambda
+        takes them (train_largescale.py:802, ViT_face.py:69-73): labels2 [B] = the mixup partners' classes, lam = this rank's lambda (a float, or a [B] tensor: one per row)
         (target lam e_labels + (1 - lam) e_labels2, entering the CosFace margin itself); labels2 None = hard labels.
         Returns (loss = mean CE over the GLOBAL batch, d loss/d emb [B, D] * grad_scale); the class-centre gradient
         accumulates in this rank's arena."""
@@ -153,7 +153,10 @@ class PartialFC:
             if self.margin_type != 0:
                 raise _lib.LafsHipError("soft (mixup) targets need the CosFace margin (ArcFace takes hard labels)")
             labels2 = labels2.to(dev, torch.int64).contiguous()
-            lam_rows = torch.full((B,), float(lam), device=dev, dtype=f32)
+            if torch.is_tensor(lam):                    # a lambda per row (CutMix, pair / elem mixing modes)
+                lam_rows = lam.to(dev, f32).reshape(B).contiguous()
+            else:
+                lam_rows = torch.full((B,), float(lam), device=dev, dtype=f32)
         if W > 1:
             E, L = _gather_rows(emb, W), _gather_rows(labels, W)
             if soft:

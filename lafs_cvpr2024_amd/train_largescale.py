@@ -5,7 +5,7 @@ landmark branch), dropout = emb_dropout = 0.1, DropPath 0.1, CosFace(s=64, m=0.4
 
 Kept from the reference: flags that define the step (batch size, epochs, the lr rescale of :472
 `acc_step/480 * lr * sqrt(world*bs/336) * 336`, weight decay 0.1 on >= 2-D tensors (:618-627; `--weight-decay` is parsed by the
-reference but never reaches its optimizer), mixup alpha/prob, acc_step=3 from supervised_config.py:37, warm-up(5 epochs)+cosine(eta_min 1e-6) LR, loading
+reference but never reaches its optimizer), mixup alpha/prob, cutmix / cutmix-minmax / switch-prob / mixup-mode / smoothing (:383-395), acc_step=3 from supervised_config.py:37, warm-up(5 epochs)+cosine(eta_min 1e-6) LR, loading
 `ckpt['teacher']` of an SSL checkpoint with the 'encoder.|backbone.|module.' prefixes stripped and strict=False).
 
 Input: `--data recordio --data_path DIR` reads DIR/train.rec (MXNet RecordIO, InsightFace layout, recordio.FaceRecordDataset) with
@@ -62,6 +62,14 @@ def get_args_parser():
     p.add_argument("--num_class", default=205990, type=int)
     p.add_argument("--mixup", default=0.2, type=float)
     p.add_argument("--mixup-prob", dest="mixup_prob", default=0.1, type=float)
+    p.add_argument("--cutmix", default=0.0, type=float, help="cutmix alpha, cutmix enabled if > 0 (reference :385)")
+    p.add_argument("--cutmix-minmax", dest="cutmix_minmax", default=None, type=float, nargs=2, metavar=("MIN", "MAX"),
+                   help="cutmix min/max box ratio, overrides alpha and enables cutmix if set (reference :387)")
+    p.add_argument("--mixup-switch-prob", dest="mixup_switch_prob", default=0.5, type=float,
+                   help="probability of switching to cutmix when both mixup and cutmix are enabled (reference :391)")
+    p.add_argument("--mixup-mode", dest="mixup_mode", default="batch", type=str, choices=["batch", "pair", "elem"],
+                   help="how to apply mixup/cutmix parameters: per batch, per pair of rows or per row (reference :393)")
+    p.add_argument("--smoothing", default=0.0, type=float, help="label smoothing (reference :395); dense CosFace head only")
     p.add_argument("--drop_path", default=0.1, type=float)
     p.add_argument("--model_dir", default="", type=str, help="LAFS checkpoint whose ['teacher'] weights initialise the backbone")
     p.add_argument("--pretrain_path", default="", type=str, help="stage-1 checkpoint with the landmark CNN (alias of --landmark_ckpt)")
@@ -123,6 +131,12 @@ def is_eval_step(eval_step, divisor):
     """Evaluate after the optimizer step that made the (never reset) optimizer-step counter `eval_step`: 3, 3 + F, 3 + 2F, ...
     -- `(eval_step - 2) % F == 1` of the reference (:925) for F >= 3 (see the module docstring for F < 3)."""
     return eval_step >= 3 and (eval_step - 3) % divisor == 0
+
+
+def mixing_active(args):
+    """timm's rule: mixing runs when any of mixup, cutmix or a cutmix min/max ratio is set.  The reference commented the last two
+    out (train_largescale.py:526), so its `--mixup 0 --cutmix 1` silently trains unmixed; here it mixes."""
+    return args.mixup > 0 or args.cutmix > 0.0 or args.cutmix_minmax is not None
 
 
 def get_time():
@@ -299,8 +313,11 @@ def main(args):
         from .partial_fc import PartialFC
         head = PartialFC(768, args.num_class, args.batch_size, sample_rate=args.sample_rate, s=64.0, m=0.5 if arc else 0.4,
                          margin_type=1 if arc else 0, device=device, seed=cfg["SEED"])
-    engine = FinetuneEngine(backbone, args.batch_size, acc_step=cfg["acc_step"], mixup_alpha=args.mixup, mixup_prob=args.mixup_prob,
-                            s=64.0, m=0.5 if arc else 0.4, margin_type=1 if arc else 0, device=device, sharded_head=head)
+    engine = FinetuneEngine(backbone, args.batch_size, acc_step=cfg["acc_step"], mixup_alpha=args.mixup,
+                            mixup_prob=args.mixup_prob if mixing_active(args) else 0.0,
+                            s=64.0, m=0.5 if arc else 0.4, margin_type=1 if arc else 0, device=device, sharded_head=head,
+                            cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, switch_prob=args.mixup_switch_prob,
+                            mix_mode=args.mixup_mode, label_smoothing=args.smoothing)
     # train_largescale.py:472:  lr = acc_step / 480 * lr * sqrt(world * BATCH_SIZE / 336) * 336
     base_lr = cfg["acc_step"] / 480.0 * args.lr * math.sqrt(world * args.batch_size / 336.0) * 336
     n_it = args.steps_per_epoch

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Fine-tune step benchmark (BASELINE.json configs C4/C5 on ONE GPU): Part-fViT ViT-B (dim 768, depth 12, heads 11, mlp 2048)
 + margin head, batch 128, uint8 112x112 synthetic faces resident in HBM.  GPU box only.
-usage: python tools/bench_finetune.py [--head CosFace|ArcFace|PartialFC] [--with-land 0|1] [--dropout 0.1] [--classes N] [--batch B]"""
+usage: python tools/bench_finetune.py [--head CosFace|ArcFace|PartialFC] [--with-land 0|1] [--dropout 0.1] [--classes N] [--batch B]
+                                      [--mixup A] [--mixup-prob P] [--cutmix A] [--mixup-mode batch|pair|elem] [--smoothing E]"""
 import argparse
 import json
 import os
@@ -25,6 +26,11 @@ ap.add_argument("--steps", type=int, default=12)
 ap.add_argument("--warmup", type=int, default=3)
 ap.add_argument("--miopen-find", type=int, default=0, help="torch.backends.cudnn.benchmark (MIOpen exhaustive find) for the CNN branch")
 ap.add_argument("--channels-last", type=int, default=0)
+ap.add_argument("--mixup", type=float, default=0.2)
+ap.add_argument("--mixup-prob", type=float, default=0.1)
+ap.add_argument("--cutmix", type=float, default=0.0)
+ap.add_argument("--mixup-mode", default="batch")
+ap.add_argument("--smoothing", type=float, default=0.0)
 a = ap.parse_args()
 torch.backends.cudnn.benchmark = bool(a.miopen_find)
 dev = torch.device("cuda", 0)
@@ -38,7 +44,8 @@ if sharded:
     from lafs_cvpr2024_amd.partial_fc import PartialFC
     head = PartialFC(768, a.classes, a.batch, sample_rate=a.sample_rate, device=dev)
 eng = FinetuneEngine(m, a.batch, acc_step=1, margin_type=1 if a.head == "ArcFace" else 0, m=0.5 if a.head == "ArcFace" else 0.4,
-                     device=dev, sharded_head=head)
+                     device=dev, sharded_head=head, mixup_alpha=a.mixup, mixup_prob=a.mixup_prob, cutmix_alpha=a.cutmix, mix_mode=a.mixup_mode,
+                     label_smoothing=a.smoothing)
 m.train()
 if a.channels_last and a.with_land:
     m.stn.to(memory_format=torch.channels_last)
@@ -52,5 +59,6 @@ for _ in range(a.steps):
     loss = eng.step(x, y, lr=1e-4)
 torch.cuda.synchronize(); dt = (time.perf_counter() - t0) / a.steps
 print(json.dumps({"workload": f"Part-fViT ViT-B + {a.head} fine-tune step, batch {a.batch}, {a.classes} classes, with_land={a.with_land}, "
-                              f"dropout={a.dropout}" + (f", sample_rate={a.sample_rate}" if sharded else ""),
+                              f"dropout={a.dropout}" + (f", sample_rate={a.sample_rate}" if sharded else "") +
+                              (f", cutmix={a.cutmix} mode={a.mixup_mode} smoothing={a.smoothing} mixup_prob={a.mixup_prob}" if eng.mix_rows else ""),
                   "ms_per_step": round(dt * 1e3, 2), "images_per_s": round(a.batch / dt, 1), "loss": round(float(loss.item()), 4), "warmup_losses": trace}))

@@ -125,17 +125,30 @@ typedef struct lafs_gemm_nt_args {
  * needs u only through gelu'(u): saved this way, the derivative's exponential / reciprocal are the forward's (shared with
  * gelu(u)) and the GELU' epilogue of the input gradient is one multiply per value. */
 #define LAFS_GELU_SAVE_GRAD 1
-/* C[M,N] = A[M,K] * B[N,K]^T with a fused epilogue. */
 /* Number of K slices a request for `splits` actually produces (slices are whole pipeline stages): the image count of a
  * K-split LAFS_EPI_F32 GEMM. */
 int lafs_gemm_nt_slices(int K, int splits);
+/* C[M,N] = A[M,K] * B[N,K]^T with a fused epilogue.
+ * Shape and alignment contract (a request that breaks it returns a negative code and launches nothing):
+ *   - K % 32 == 0.  N is free: it need NOT be a multiple of 8 (or of 4 for the fp32 outputs); the last, partial column group of a row
+ *     is read and written element by element, and nothing between column N and the row stride is touched.
+ *   - A, B: 16-byte aligned, lda % 8 == 0, ldb % 8 == 0 (16-byte row pieces).
+ *   - C: 16-byte aligned and ldc % 8 == 0 for every epilogue but ATOMIC_F32 (element-wise atomics: ldc % 8 == 0 only).
+ *   - C2 (BF16_GELU): 16-byte aligned, ldc2 % 8 == 0.
+ *   - resid (RESID_F32): 16-byte aligned, ldr % 4 == 0 (one 16-byte load per group of 4 columns); it may alias C.
+ *   - aux of DGELU_BF16: 16-byte aligned, ldaux % 8 == 0 (one 16-byte load per group of 8 columns).
+ *     aux of BF16_ACT is read element by element: any ldaux >= N.
+ *   - bias, pos, seq_scale, row2seq: element-aligned.
+ * A column slice of a wider buffer is therefore a legal operand when it starts at a multiple of 8 elements (16-bit) / 4 elements
+ * (fp32) of a 16-byte aligned row. */
 int lafs_gemm_nt(const lafs_gemm_nt_args* args, hipStream_t stream);
 /* Which kernel lafs_gemm_nt runs for this request: 0 = the tiled LDS-DMA kernel (gemm.hip), 1 = the K-resident streaming kernel
  * (gemm_kres.hip: K == 384, N % 64 == 0, N <= 1536, M >= 2048, plain / GELU / GELU' / residual epilogue, no dropout, bf16 operands),
  * 3 = the tiled kernel in its 128x384 / 12-wave form (whole N per workgroup: long reductions onto N = 384 whose tiles fit one
  * round of the chip), 4 = the tiled kernel with 160-row tiles (long reductions whose 128-row tiles would spill into one more
  * round of the 512 workgroup slots than 160-row ones need), 5 = the 256x256 one-workgroup-per-CU kernel (gemm_big.hip).
- * Mirrors lafs_gemm_nt's own decisions, including its operand-format and validation order. */
+ * Mirrors lafs_gemm_nt's own decisions, including its operand-format and validation order; a request that breaks the alignment
+ * contract above (which lafs_gemm_nt refuses) gives a negative code here too, not a route. */
 int lafs_gemm_nt_route(const lafs_gemm_nt_args* args);
 
 /* ------------------------------------------------------------------------------------------------
@@ -212,7 +225,8 @@ int lafs_gemm_tn_acc(const void* A, int lda, const void* B, int ldb, float* C, i
  * be zero before the first accumulation (lafs_reduce_partials leaves them zeroed). */
 int lafs_gemm_tn_part(const void* A, int lda, const void* B, int ldb, float* part, int ldc, int64_t part_stride,
                       int M, int N1, int N2, int splits, float* colsum_a, hipStream_t stream);
-/* out(f32)[i] += sum_x part[x*part_stride + i], then part[...] = 0;  n, part_stride multiples of 4. */
+/* out(f32)[i] += sum_x part[x*part_stride + i], then part[...] = 0;  n, part_stride multiples of 4; part and out 16-byte aligned
+ * (float4 loads and stores; likewise lafs_sum_slices) -- anything else is refused with a negative code. */
 int lafs_reduce_partials(float* part, int64_t part_stride, int n_part, int64_t n, float* out, hipStream_t stream);
 /* out(f32)[n] = sum over x < n_part of part[x * part_stride + i]: folds the slice images of a K-split LAFS_EPI_F32 GEMM. */
 int lafs_sum_slices(const float* part, int64_t part_stride, int n_part, int64_t n, float* out, hipStream_t stream);

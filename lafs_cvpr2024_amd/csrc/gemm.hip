@@ -721,8 +721,25 @@ int ksplit_len(int K, int splits) {
 
 extern "C" int lafs_gemm_nt_slices(int K, int splits) { return K >= 32 ? ceil_div(K, ksplit_len(K, splits)) : 1; }
 
+// Every kernel behind lafs_gemm_nt moves its operands in 16-byte pieces (LDS-DMA of A / B, one vector load or store per column
+// group of C / C2 / resid / the GELU' aux): a base address or row stride that breaks that is refused, never launched.  (ATOMIC_F32
+// adds element by element, and the BF16_ACT residual is read element by element: those two only need their element size.)
+// Returns the reason, or nullptr when the request keeps the contract of lafs_hip.h.
+static bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+static const char* nt_alignment_error(const lafs_gemm_nt_args* g) {
+  if (g->lda % 8 != 0 || g->ldb % 8 != 0) return "lda/ldb must be multiples of 8 elements (16-byte rows)";
+  if (!al16(g->A) || !al16(g->B)) return "A and B must be 16-byte aligned";
+  if (g->epilogue != LAFS_EPI_ATOMIC_F32 && !al16(g->C)) return "C must be 16-byte aligned";
+  if (g->epilogue == LAFS_EPI_BF16_GELU && !al16(g->C2)) return "C2 must be 16-byte aligned";
+  if (g->epilogue == LAFS_EPI_RESID_F32 && !al16(g->resid)) return "resid must be 16-byte aligned";
+  if (g->epilogue == LAFS_EPI_DGELU_BF16 && (!al16(g->aux) || g->ldaux % 8 != 0))
+    return "GELU' epilogue: aux must be 16-byte aligned and ldaux a multiple of 8 elements";
+  return nullptr;
+}
+
 extern "C" int lafs_gemm_nt_route(const lafs_gemm_nt_args* g) {
   if (g == nullptr) return 0;
+  if (nt_alignment_error(g) != nullptr) return LAFS_ESHAPE;   // lafs_gemm_nt refuses it: no kernel runs
   if (lafs_kres_eligible(g)) return 1;
   if (lafs_big_eligible(g)) return 5;               // wide long-K shapes: 192x256 tiles, one persistent workgroup per CU (gemm_big.hip)
   if (g->operand_f16) return 0;                     // fp16 operands (landmark CNN plan): launch_nt takes the 128x128 fp16 kernel first
@@ -742,7 +759,10 @@ extern "C" int lafs_gemm_nt(const lafs_gemm_nt_args* g, hipStream_t stream) {
   LAFS_CHECK_ARG(g != nullptr && g->A && g->B && (g->C || (g->epilogue == LAFS_EPI_BF16_GELU && g->C2)), "null operand");
   LAFS_CHECK_ARG(g->M > 0 && g->N > 0 && g->K > 0, "empty problem");
   LAFS_CHECK_ARG(g->K % 32 == 0, "K must be a multiple of 32");
-  LAFS_CHECK_ARG(g->lda % 8 == 0 && g->ldb % 8 == 0, "lda/ldb must be multiples of 8 elements (16-byte rows)");
+  if (const char* why = nt_alignment_error(g)) {
+    lafs_set_error("%s:%d: %s", __FILE__, __LINE__, why);
+    return LAFS_ESHAPE;
+  }
   NTArgs a;
   a.A = (const bf16_t*)g->A; a.B = (const bf16_t*)g->B;
   a.M = g->M; a.N = g->N; a.K = g->K; a.lda = g->lda; a.ldb = g->ldb;
@@ -864,6 +884,7 @@ extern "C" int lafs_gemm_tn_part(const void* A, int lda, const void* B, int ldb,
 extern "C" int lafs_reduce_partials(float* part, int64_t part_stride, int n_part, int64_t n, float* out, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(part && out && n_part > 0 && n > 0 && n % 4 == 0 && part_stride % 4 == 0, "n and part_stride must be multiples of 4");
+  LAFS_CHECK_ARG(((uintptr_t)part & 15) == 0 && ((uintptr_t)out & 15) == 0, "part and out must be 16-byte aligned (float4 loads and stores)");
   const long n4 = n / 4;
   hipLaunchKernelGGL(reduce_partials_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, (long)part_stride,
                      n_part, n4, out);
@@ -874,6 +895,7 @@ extern "C" int lafs_reduce_partials(float* part, int64_t part_stride, int n_part
 extern "C" int lafs_sum_slices(const float* part, int64_t part_stride, int n_part, int64_t n, float* out, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(part && out && n_part > 0 && n > 0 && n % 4 == 0 && part_stride % 4 == 0, "n and part_stride must be multiples of 4");
+  LAFS_CHECK_ARG(((uintptr_t)part & 15) == 0 && ((uintptr_t)out & 15) == 0, "part and out must be 16-byte aligned (float4 loads and stores)");
   const long n4 = n / 4;
   hipLaunchKernelGGL(sum_slices_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, stream, part, (long)part_stride, n_part, n4, out);
   LAFS_LAUNCH_CHECK();

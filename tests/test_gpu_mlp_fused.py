@@ -20,10 +20,6 @@ from lafs_cvpr2024_amd import _lib, ops  # noqa: E402
 DEV = "cuda"
 bf16, f32, f64 = torch.bfloat16, torch.float32, torch.float64
 D = 384
-U = 2.0 ** -24          # fp32 unit roundoff
-# |Phi(u) - kernel's (1 + erf(u / sqrt 2)) / 2|: Abramowitz-Stegun 7.1.26 (common.hpp erf_fast, |err| <= 1.5e-7) plus the fp32
-# rounding of its ~15 operations on values <= 1.5
-EPS_PHI = 1e-6
 EPS = 1e-6              # LayerNorm eps of the ViT blocks
 GR = 16                 # guard rows past M in every buffer (a wave owns 16 rows)
 GUARD = 12345.0
@@ -63,45 +59,8 @@ H_OPT = [256, 704, 1536]                             # NI % 3 = 1, 2, 0
 
 
 # ------------------------------------------------------------------------------------------------ fp64 reference with bounds
-def rbf(v):
-    return v.to(f32).to(bf16).to(f64)
-
-
-def flip(v, e):
-    """bf16 rounding of a value the kernel holds to within +-e before it rounds: the reference rbf(v) and the most the kernel's
-    bf16 value can differ from it (rounding is monotone: the kernel's result lies between rbf(v - e) and rbf(v + e))."""
-    r = rbf(v)
-    return r, torch.maximum(rbf(v + e) - r, r - rbf(v - e))
-
-
-def gemm(x, xe, w, bias=None):
-    """x w^T (+ bias) and a bound on the kernel's fp32 value, whose operand x is known to within xe."""
-    K = w.shape[1]
-    wa = w.abs()
-    v, s = x @ w.t(), x.abs() @ wa.t()
-    if bias is not None:
-        v, s = v + bias, s + bias.abs()
-    pe = None if xe is None else xe @ wa.t()
-    if pe is not None:
-        s = s + pe
-    # fp32 accumulation over K of exact bf16 products of random sign: the partial sums walk like sqrt(k), so even rounding errors of
-    # one sign add up to < 1.4 sqrt(K) u sum|terms| (rounding toward zero); 3x margin.  The bias, where the sums start, may
-    # collect K same-sign roundings.
-    e = 4 * math.sqrt(K) * U * s
-    if bias is not None:
-        e = e + K * U * bias.abs()
-    return v, (e if pe is None else e + pe)
-
-
-def gelu(u, ue):
-    cdf = 0.5 * (1 + torch.erf(u / math.sqrt(2)))
-    pdf = torch.exp(-0.5 * u * u) / math.sqrt(2 * math.pi)
-    g, dg = u * cdf, cdf + u * pdf
-    # |gelu(u + d) - gelu(u)| <= |gelu'(u)| |d| + 0.4 d^2 (|gelu''| < 0.8); Phi off by EPS_PHI; 4 fp32 roundings
-    ge = (dg.abs() + 0.4 * ue) * ue + u.abs() * EPS_PHI + 4 * U * (g.abs() + u.abs())
-    # gelu'(u): |gelu''| < 0.8; Phi off by EPS_PHI; exp(-u^2 / 2) in fp32 good to (u^2 + 4) u relative
-    dge = 0.8 * ue + EPS_PHI + 4 * U * (u.abs() * pdf * (u * u + 4) + dg.abs())
-    return g, ge, dg, dge
+# rbf, flip, gemm (4 sqrt(K) u sum|terms| + K u |bias|) and gelu (EPS_PHI) live in tests/fp64_bounds.py, shared with the GEMM modules
+from fp64_bounds import EPS_PHI, U, flip, gelu, gemm, rbf  # noqa: E402,F401
 
 
 def mlp_fwd(X, Xe, Wa, Wb, ba, bb, resid, s, a_kernel=None):

@@ -17,6 +17,7 @@
 #ifndef LAFS_HIP_H
 #define LAFS_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -744,6 +745,30 @@ int lafs_ijb_template_pool(const float* feats, int ldf, const float* faceness, i
                            int detector_score, float* sums, double* unit, hipStream_t stream);
 int lafs_ijb_pair_scores(const double* unit, int n_templates, int D, const int32_t* idx1, const int32_t* idx2, int64_t n_pairs,
                          double* scores, hipStream_t stream);
+
+/* IJB-B / IJB-C 1:N identification: every probe template against every gallery template, top-k and three scalars per probe; the
+ * n_probes x n_gallery scores are never stored (csrc/ijb.hip).  No counterpart in the reference.
+ *   unit f64 [n_templates, D] (lafs_ijb_template_pool's rows), D in [1, 1024]; probe_idx i32 [n_probes] and gallery_idx i32 [n_gallery]
+ *   name rows of unit (nothing is gathered; a row may repeat, no order is assumed); mate i32 [n_probes] = the POSITION in gallery_idx
+ *   of the probe's subject, -1: none (a value outside [-1, n_gallery) is treated as -1); k in [1, 64].
+ * Score: score(i, j) = the float64 dot product of rows probe_idx[i] and gallery_idx[j].  Its order of summation is a function of D
+ *   alone (column blocks of 4 in ascending order, zeros up to the next multiple of 32): it does not depend on where the rows sit in
+ *   a tile, a workgroup or either list, on the launch geometry, or on whether the pair is the mate -- the same two rows give the same
+ *   64 bits wherever they appear.
+ * Ranking order of the gallery positions of one probe: larger score first; equal scores: smaller position first; a NaN score (a
+ *   non-finite row, e.g. from non-finite image features) after every number, among NaNs the smaller
+ *   position first.
+ * top_score f64 / top_idx i32 [n_probes, k]: the first k entries of that order (positions in gallery_idx); when n_gallery < k the
+ *   tail is idx -1, score NaN.  mate_score f64 [n_probes] = score(i, mate[i]), NaN without a mate.  mate_rank i32 [n_probes] = the
+ *   number of gallery positions that precede the mate in the ranking order over the WHOLE gallery (0: a rank-1 hit), -1 without a
+ *   mate.  best_nonmate f64 [n_probes] = the first score of the ranking order with position mate[i] left out, NaN if nothing is left.
+ * A probe index outside [0, n_templates) gives that probe idx -1, NaN scores and rank -1; a gallery index outside it scores NaN
+ *   against every probe (lafs_ijb_pair_scores' rule), so it ranks last.  Nothing outside unit is read.
+ * lafs_ijb_search_workspace returns the bytes of workspace the search needs (0 in this design: workspace may then be NULL). */
+int64_t lafs_ijb_search_workspace(int n_probes, int n_gallery, int k);
+int lafs_ijb_search(const double* unit, int n_templates, int D, const int32_t* probe_idx, int n_probes, const int32_t* gallery_idx,
+                    int n_gallery, const int32_t* mate, int k, double* top_score, int32_t* top_idx, double* mate_score,
+                    int32_t* mate_rank, double* best_nonmate, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------------------------
  * TRAINABLE landmark CNN of the fine-tune step (csrc/landmark_train.hip; reference face_pre_pro/mobilenet.py:224-313 trained through

@@ -178,6 +178,7 @@ _PROTOS = {
     "lafs_ijb_align_flip_normalize": [vp, i64, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp],
     "lafs_ijb_template_pool": [vp, i32, vp, i32, vp, vp, i32, vp, i32, i32, i32, i32, vp, vp],
     "lafs_ijb_pair_scores": [vp, i32, i32, vp, vp, i64, vp],
+    "lafs_ijb_search": [vp, i32, i32, vp, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp, C.c_size_t],
     "lafs_landmark_theta": [vp, i32, i32, vp, f32, vp, i32, vp],
     "lafs_mixup_normalize": [vp, vp, i32, i32, f32, vp],
     "lafs_margin_softmax_ce_bf16": [vp, i32, i32, i32, vp, vp, f32, vp, f32, f32, i32, f32, vp, i32, vp, vp, vp],
@@ -210,6 +211,7 @@ _NO_STREAM = {
     "lafs_trunk_workspace_bytes": ([C.POINTER(TrunkDesc), i32], i64),
     "lafs_trunk_row_ranges": ([C.POINTER(TrunkDesc)], i32),
     "lafs_layernorm_bwd_parts": ([i32, i32], i32),
+    "lafs_ijb_search_workspace": ([i32, i32, i32], i64),
     "lafs_wgrad_workspace_bytes": ([i32, i32, i32], i64),
     "lafs_wgrad_group_workspace_bytes": ([C.POINTER(WgradItem), i32, i32, i32], i64),
 }

@@ -203,6 +203,191 @@ __global__ __launch_bounds__(PAIR_THREADS) void ijb_pair_kernel(const double* __
   }
 }
 
+// ---- 1:N search.  One workgroup (4 waves) owns SR_TQ = 64 probes, wave w the 16 probes 16 w .. 16 w + 15.  The gallery list is
+// streamed in tiles of SR_TG = 64 positions; a tile is a 64 x 64 float64 GEMM block over D in chunks of SR_KC = 32 columns: both
+// operands' chunks go through LDS (rows of SR_LD = 34 doubles: the 16 rows x 2 columns a half wave reads cover the 64 banks once),
+// the next chunk is fetched into registers while v_mfma_f64_16x16x4_f64 works on the current one.  Lane l supplies
+// A[probe l & 15][k = l >> 4] and B[k = l >> 4][gallery l & 15] and receives C[probe (l >> 4) + 4 reg][gallery l & 15] (the f64 map).
+// Summation order of every score: chunks in order, four columns per MFMA in order, the columns from D up to the next multiple of 32
+// are zeros -- the same instruction sequence for every (probe, gallery) pair, so the same rows give the same bits anywhere.
+// The mates' scores come from one more tile in front of the stream whose row j is the mate of probe j (the diagonal of that block),
+// through the very same code.  After a tile the wave parks its 16 x 64 scores in LDS (over the operand chunks) and lane p < 16 walks
+// probe p's row in position order: counts what precedes the mate, keeps the best non-mate, and inserts into the probe's sorted top-k
+// list (LDS, [64][k]); the Q x G matrix never exists.  Results leave in the epilogue through plain stores.
+constexpr int SR_THREADS = 256;
+constexpr int SR_TQ = 64, SR_TG = 64, SR_KC = 32, SR_LD = 34, SR_SLD = 65, SR_MAX_K = 64;
+constexpr int SR_ROWS = SR_THREADS / SR_KC;            // 8 rows of a chunk per pass of the workgroup
+constexpr int SR_PASSES = SR_TQ / SR_ROWS;             // 8 values per thread, chunk and operand
+static_assert(SR_TQ == SR_TG && 4 * 16 * SR_SLD <= (SR_TQ + SR_TG) * SR_LD, "the score scratch lies over the operand chunks");
+typedef __attribute__((ext_vector_type(4))) double f64x4_t;
+
+__device__ __forceinline__ double qnan_f64() { return __longlong_as_double(0x7ff8000000000000LL); }
+
+// the ranking order: larger score first, equal scores by position, NaN after every number (among NaNs by position)
+__device__ __forceinline__ bool rank_before(double a, int ia, double b, int ib) {
+  const bool na = a != a, nb = b != b;
+  if (na || nb) return na ? (nb && ia < ib) : true;
+  return a > b || (a == b && ia < ib);
+}
+
+// rows[i] >= 0: a row of unit; -1: NaN (an index outside the table); -2: zeros (no such row)
+__device__ __forceinline__ void sr_fetch(const double* __restrict__ unit, int D, const int (&rows)[SR_PASSES], int col, double (&v)[SR_PASSES]) {
+#pragma unroll
+  for (int i = 0; i < SR_PASSES; ++i) {
+    const int r = rows[i];
+    v[i] = (r >= 0 && col < D) ? unit[(size_t)r * D + col] : (r == -1 ? qnan_f64() : 0.0);
+  }
+}
+
+__global__ __launch_bounds__(SR_THREADS) void ijb_search_kernel(const double* __restrict__ unit, int T, int D,
+                                                                const int32_t* __restrict__ probe_idx, int Q,
+                                                                const int32_t* __restrict__ gallery_idx, int G,
+                                                                const int32_t* __restrict__ mate, int k, double* __restrict__ top_score,
+                                                                int32_t* __restrict__ top_idx, double* __restrict__ mate_score,
+                                                                int32_t* __restrict__ mate_rank, double* __restrict__ best_nonmate) {
+  extern __shared__ __align__(16) unsigned char sr_lds[];
+  __shared__ int32_t s_mpos[SR_TQ];
+  double* sP = reinterpret_cast<double*>(sr_lds);        // [SR_TQ][SR_LD]
+  double* sG = sP + SR_TQ * SR_LD;                       // [SR_TG][SR_LD]
+  double* sLs = sG + SR_TG * SR_LD;                      // [SR_TQ][k] list scores
+  int32_t* sLi = reinterpret_cast<int32_t*>(sLs + SR_TQ * k);   // [SR_TQ][k] list positions
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double* sS = sP + w * 16 * SR_SLD;                     // [16][SR_SLD] of this wave, valid between the barriers after a tile
+  const int q0 = blockIdx.x * SR_TQ;                     // (the host keeps the grid inside int)
+
+  if (tid < SR_TQ) {
+    int m = -1;
+    if (q0 + tid < Q) {
+      m = mate[q0 + tid];
+      if (m < 0 || m >= G) m = -1;
+    }
+    s_mpos[tid] = m;
+  }
+  __syncthreads();
+
+  const int r0 = tid / SR_KC, cl = tid % SR_KC;
+  int prow[SR_PASSES], grow[SR_PASSES];
+#pragma unroll
+  for (int i = 0; i < SR_PASSES; ++i) {
+    const int q = q0 + r0 + SR_ROWS * i;
+    const int pi = q < Q ? probe_idx[q] : -1;
+    prow[i] = (pi >= 0 && pi < T) ? pi : -2;
+  }
+  auto tile_rows = [&](int t) {                          // t = -1: the mates of this workgroup's probes
+#pragma unroll
+    for (int i = 0; i < SR_PASSES; ++i) {
+      const int row = r0 + SR_ROWS * i;
+      int pos = t < 0 ? s_mpos[row] : t * SR_TG + row;
+      if (pos >= G) pos = -1;
+      int r = -2;
+      if (pos >= 0) {
+        const int gi = gallery_idx[pos];
+        r = (gi >= 0 && gi < T) ? gi : -1;
+      }
+      grow[i] = r;
+    }
+  };
+
+  // selection state of probe p = lane of this wave (lanes 0 .. 15)
+  const int my_row = w * 16 + (lane & 15);
+  const bool sel = lane < 16 && q0 + my_row < Q;
+  const int mpos = s_mpos[my_row];
+  double ms = qnan_f64(), thr_s = 0.0, bn_s = qnan_f64();
+  int thr_i = -1, bn_i = -1, cnt = 0, rank = 0;
+  double* Ls = sLs + my_row * k;
+  int32_t* Li = sLi + my_row * k;
+
+  const int n_tiles = (G + SR_TG - 1) / SR_TG;
+  const int n_chunks = (D + SR_KC - 1) / SR_KC;
+  double pv[SR_PASSES], gv[SR_PASSES];
+  tile_rows(-1);
+  sr_fetch(unit, D, prow, cl, pv);
+  sr_fetch(unit, D, grow, cl, gv);
+
+  for (int t = -1; t < n_tiles; ++t) {
+    f64x4_t acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = f64x4_t{0.0, 0.0, 0.0, 0.0};
+    for (int c = 0; c < n_chunks; ++c) {
+      __syncthreads();                                   // the chunk (or the score scratch) in LDS has been read
+#pragma unroll
+      for (int i = 0; i < SR_PASSES; ++i) {
+        sP[(r0 + SR_ROWS * i) * SR_LD + cl] = pv[i];
+        sG[(r0 + SR_ROWS * i) * SR_LD + cl] = gv[i];
+      }
+      __syncthreads();
+      if (c + 1 < n_chunks) {
+        sr_fetch(unit, D, prow, (c + 1) * SR_KC + cl, pv);
+        sr_fetch(unit, D, grow, (c + 1) * SR_KC + cl, gv);
+      } else if (t + 1 < n_tiles) {
+        tile_rows(t + 1);
+        sr_fetch(unit, D, prow, cl, pv);
+        sr_fetch(unit, D, grow, cl, gv);
+      }
+      const double* pa = sP + (w * 16 + (lane & 15)) * SR_LD + (lane >> 4);
+      const double* pb = sG + (lane & 15) * SR_LD + (lane >> 4);
+#pragma unroll
+      for (int kk = 0; kk < SR_KC / 4; ++kk) {
+        const double a = pa[4 * kk];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, pb[j * 16 * SR_LD + 4 * kk], acc[j], 0, 0, 0);
+      }
+    }
+    __syncthreads();                                     // every wave has read the last chunk: its place becomes the score scratch
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) sS[((lane >> 4) + 4 * r) * SR_SLD + 16 * j + (lane & 15)] = acc[j][r];
+    __syncthreads();
+    if (sel) {
+      const double* row = sS + lane * SR_SLD;
+      if (t < 0) {
+        ms = row[my_row];                                // row j of the mate tile is the mate of probe j
+      } else {
+        const int g0 = t * SR_TG;
+        const int n = min(SR_TG, G - g0);
+        for (int j = 0; j < n; ++j) {
+          const int pos = g0 + j;
+          double s = row[j];
+          if (s != s) s = qnan_f64();
+          if (pos != mpos) {
+            if (mpos >= 0 && rank_before(s, pos, ms, mpos)) ++rank;
+            if (bn_i < 0 || rank_before(s, pos, bn_s, bn_i)) { bn_s = s; bn_i = pos; }
+          }
+          if (cnt < k || rank_before(s, pos, thr_s, thr_i)) {
+            int i = cnt < k ? cnt : k - 1;
+            while (i > 0 && rank_before(s, pos, Ls[i - 1], Li[i - 1])) {
+              Ls[i] = Ls[i - 1];
+              Li[i] = Li[i - 1];
+              --i;
+            }
+            Ls[i] = s;
+            Li[i] = pos;
+            if (cnt < k) ++cnt;
+            thr_s = Ls[cnt - 1];
+            thr_i = Li[cnt - 1];
+          }
+        }
+      }
+    }
+  }
+
+  if (sel) {
+    const int q = q0 + my_row;
+    const int pi = probe_idx[q];
+    const bool ok = pi >= 0 && pi < T;
+    for (int i = 0; i < k; ++i) {
+      const bool have = ok && i < cnt;
+      top_score[(size_t)q * k + i] = have ? Ls[i] : qnan_f64();
+      top_idx[(size_t)q * k + i] = have ? Li[i] : -1;
+    }
+    const bool mated = ok && mpos >= 0;
+    mate_score[q] = mated ? (ms != ms ? qnan_f64() : ms) : qnan_f64();
+    mate_rank[q] = mated ? rank : -1;
+    best_nonmate[q] = (ok && bn_i >= 0) ? bn_s : qnan_f64();
+  }
+}
+
 }  // namespace
 
 extern "C" int lafs_ijb_align_flip_normalize(const uint8_t* src_u8, int64_t src_bytes, const int64_t* offsets, const int32_t* hw,
@@ -249,6 +434,34 @@ extern "C" int lafs_ijb_pair_scores(const double* unit, int n_templates, int D, 
   else
     hipLaunchKernelGGL(ijb_pair_kernel<false>, dim3((unsigned)blocks), dim3(PAIR_THREADS), 0, stream, unit, n_templates, D, idx1, idx2,
                        (size_t)n_pairs, scores);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int64_t lafs_ijb_search_workspace(int n_probes, int n_gallery, int k) {
+  (void)n_probes; (void)n_gallery; (void)k;
+  return 0;                                              // the running lists live in LDS; nothing is merged across workgroups
+}
+
+extern "C" int lafs_ijb_search(const double* unit, int n_templates, int D, const int32_t* probe_idx, int n_probes,
+                               const int32_t* gallery_idx, int n_gallery, const int32_t* mate, int k, double* top_score, int32_t* top_idx,
+                               double* mate_score, int32_t* mate_rank, double* best_nonmate, void* workspace, size_t workspace_bytes,
+                               hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(unit && probe_idx && gallery_idx && mate && top_score && top_idx && mate_score && mate_rank && best_nonmate, "bad operand");
+  LAFS_CHECK_ARG(n_templates > 0 && n_probes > 0 && n_gallery > 0, "n_templates, n_probes and n_gallery must be positive");
+  LAFS_CHECK_ARG(D >= 1 && D <= POOL_MAX_D, "D must be in [1, 1024]");
+  LAFS_CHECK_ARG(k >= 1 && k <= SR_MAX_K, "k must be in [1, 64]");
+  const size_t need = (size_t)lafs_ijb_search_workspace(n_probes, n_gallery, k);
+  LAFS_CHECK_ARG(workspace_bytes >= need && (need == 0 || workspace != nullptr), "workspace smaller than lafs_ijb_search_workspace()");
+  const size_t lds = (size_t)(SR_TQ + SR_TG) * SR_LD * sizeof(double) + (size_t)SR_TQ * k * (sizeof(double) + sizeof(int32_t));
+  {
+    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(ijb_search_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    if (e != hipSuccess) { lafs_set_error("lafs_ijb_search: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return (int)e; }
+  }
+  const unsigned blocks = (unsigned)(((size_t)n_probes + SR_TQ - 1) / SR_TQ);
+  hipLaunchKernelGGL(ijb_search_kernel, dim3(blocks), dim3(SR_THREADS), lds, stream, unit, n_templates, D, probe_idx, n_probes, gallery_idx,
+                     n_gallery, mate, k, top_score, top_idx, mate_score, mate_rank, best_nonmate);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }

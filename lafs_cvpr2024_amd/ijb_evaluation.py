@@ -12,6 +12,13 @@ The reference's switches use_norm_score = use_detector_score = use_flip_test = T
 built.  Only the 5-landmark form of Embedding.get is restated: its 68-landmark branch (:202-208) is never reached by the reference's
 own file format.  The model is evaluated as backbone.eval() runs it, without touching its state (see verification.py).
 
+1:N identification (`--protocol 1N`): the same pooled rows, searched instead of paired.
+    meta/<t>_1N_gallery_G1.csv, _G2.csv, _1N_probe_mixed.csv -> per gallery: lafs_ijb_search (every probe template against every gallery
+      template in float64 on the device; top-k, mate score, mate rank and best non-mate per probe; the score matrix is never stored)
+      -> cmc (closed-set rank-1/5/10) and tpir_at_fpir (open-set TPIR@FPIR) on the host -> one table row, means over G1 and G2.
+The reference stops at 1:1: the 1:N protocol has no counterpart in the reference; metric definitions are this project's, stated in the
+docstrings of cmc and tpir_at_fpir; the csv layout is restated from the public IJB-C protocol as remembered: PARITY UNPINNED.
+
 Single process only: data-parallel extraction is out of scope.
 
 Deliberate deviations from the reference:
@@ -27,9 +34,12 @@ Deliberate deviations from the reference:
     millions.
 """
 import argparse
+import csv
+import math
 import os
 import time
 from concurrent.futures import ThreadPoolExecutor
+from fractions import Fraction
 
 import numpy as np
 
@@ -39,6 +49,9 @@ ARCFACE_SRC = np.array([[30.2946, 51.6963], [65.5318, 51.5014], [48.0252, 71.736
 ARCFACE_SRC[:, 0] += 8.0                                                      # :144-150
 IMAGE_SIZE = 112
 MAX_WORKERS = 16
+CMC_RANKS = (1, 5, 10)
+FPIRS = (0.01, 0.1)
+MAX_TOP_K = 64                                                                # lafs_ijb_search's limit
 
 
 # ----------------------------------------------------------------------------------------------------------------- readers
@@ -103,6 +116,47 @@ def read_meta(image_path, target):
     if len(names) != len(names_t):
         raise ValueError(f"{meta}: {len(names_t)} rows of tid / mid but {len(names)} rows of landmarks")
     return dict(names=names, templates=templates, medias=medias, p1=p1, p2=p2, label=label, landmarks=lmk, faceness=faceness)
+
+
+def read_template_subject_csv(path):
+    """One `*_1N_*.csv` list -> (template ids int64 [T], subject ids int64 [T]), one row per template in order of first appearance.
+    Read with the csv module and keyed on the header names TEMPLATE_ID and SUBJECT_ID; other columns are ignored and the column order
+    is free.  The files list one row per image, so rows are deduplicated; a template listed with two subjects raises.  The layout is
+    restated from the public IJB-C protocol as remembered, UNPINNED: no file of the dataset was available to check it against."""
+    if not os.path.isfile(path):
+        raise ValueError(f"{path}: no such file")
+    seen = {}
+    with open(path, newline="") as f:
+        rd = csv.DictReader(f)
+        names = [n.strip() for n in (rd.fieldnames or [])]
+        for col in ("TEMPLATE_ID", "SUBJECT_ID"):
+            if col not in names:
+                raise ValueError(f"{path}: no column {col} in the header {names}")
+        rd.fieldnames = names
+        for row in rd:
+            try:
+                t, sid = int(row["TEMPLATE_ID"]), int(row["SUBJECT_ID"])
+            except (TypeError, ValueError):
+                raise ValueError(f"{path}:{rd.line_num}: TEMPLATE_ID and SUBJECT_ID must be integers, got "
+                                 f"{row['TEMPLATE_ID']!r}, {row['SUBJECT_ID']!r}") from None
+            if seen.setdefault(t, sid) != sid:
+                raise ValueError(f"{path}:{rd.line_num}: template {t} is listed with subjects {seen[t]} and {sid}")
+    if not seen:
+        raise ValueError(f"{path}: no rows")
+    return np.array(list(seen.keys()), dtype=np.int64), np.array(list(seen.values()), dtype=np.int64)
+
+
+def read_identification_lists(image_path, target):
+    """<image_path>/meta/<t>_1N_gallery_G1.csv, <t>_1N_gallery_G2.csv and <t>_1N_probe_mixed.csv for target 'IJBC' / 'IJBB'
+    -> dict(g1_tids, g1_sids, g2_tids, g2_sids, probe_tids, probe_sids).  File names and layout UNPINNED (read_template_subject_csv)."""
+    if target not in ("IJBC", "IJBB"):
+        raise ValueError("target must be IJBC or IJBB")
+    t = target.lower()
+    meta = os.path.join(image_path, "meta")
+    out = {}
+    for key, name in (("g1", f"{t}_1N_gallery_G1.csv"), ("g2", f"{t}_1N_gallery_G2.csv"), ("probe", f"{t}_1N_probe_mixed.csv")):
+        out[key + "_tids"], out[key + "_sids"] = read_template_subject_csv(os.path.join(meta, name))
+    return out
 
 
 # ----------------------------------------------------------------------------------------------------------------- geometry
@@ -248,6 +302,159 @@ def protocol(img_feats, faceness, templates, medias, p1, p2, flip=True, detector
     return scores.cpu().numpy(), sums.cpu().numpy(), uq
 
 
+# ----------------------------------------------------------------------------------------------------------------- 1:N
+def pool_templates(img_feats, faceness, templates, medias, flip=True, detector_score=True, device=None):
+    """protocol()'s pooling alone -> (unit rows float64 [T, D] on the device, unique_templates [T])."""
+    import torch
+    from .ops import _p, call
+    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    feats = torch.as_tensor(img_feats).to(device=dev, dtype=torch.float32).contiguous()
+    if feats.dim() != 2 or feats.shape[1] % 2:
+        raise ValueError("img_feats must be [N, 2D]: rows [emb(orig) | emb(flip)]")
+    N, D = feats.shape[0], feats.shape[1] // 2
+    order, media_start, template_start, uq = build_csr(templates, medias)
+    if len(order) != N or np.asarray(faceness).shape != (N,):
+        raise ValueError(f"{N} feature rows but {len(order)} template ids and faceness of shape {np.asarray(faceness).shape}")
+    T = len(uq)
+    score_w = torch.as_tensor(np.asarray(faceness, dtype=np.float32)).to(dev)
+    d_order, d_ms, d_ts = (torch.from_numpy(a).to(dev) for a in (order, media_start, template_start))
+    sums = torch.empty(T, D, device=dev, dtype=torch.float32)
+    unit = torch.empty(T, D, device=dev, dtype=torch.float64)
+    call("lafs_ijb_template_pool", _p(feats), 2 * D, _p(score_w), N, _p(d_order), _p(d_ms), len(media_start) - 1, _p(d_ts), T, D,
+         int(bool(flip)), int(bool(detector_score)), _p(sums), _p(unit))
+    return unit, uq
+
+
+def mates(gallery_sids, probe_sids):
+    """Position in the gallery of every probe's subject, -1: none -> int32 [Q].  Two gallery templates of one subject raise."""
+    gs, ps = np.asarray(gallery_sids), np.asarray(probe_sids)
+    if gs.ndim != 1 or ps.ndim != 1 or gs.size == 0 or ps.size == 0:
+        raise ValueError("gallery and probe subject ids must be one-dimensional and not empty")
+    order = np.argsort(gs, kind="mergesort")
+    sg = gs[order]
+    if np.any(sg[1:] == sg[:-1]):
+        raise ValueError(f"subjects with more than one gallery template: {np.unique(sg[1:][sg[1:] == sg[:-1]])[:8].tolist()}")
+    i = np.minimum(np.searchsorted(sg, ps), len(sg) - 1)
+    return np.where(sg[i] == ps, order[i], -1).astype(np.int32)
+
+
+def search(unit, probe_rows, gallery_rows, mate, k=10):
+    """lafs_ijb_search on pooled rows: unit f64 [T, D] on the device, probe_rows / gallery_rows int32 rows of it, mate int32 [Q]
+    positions in gallery_rows (-1: none).  -> dict of numpy arrays top_score / top_idx [Q, k], mate_score, mate_rank, best_nonmate [Q],
+    with the semantics of include/lafs_hip.h."""
+    import torch
+    from ._lib import lib
+    from .ops import _p, call
+    pr, gr, mt = (np.ascontiguousarray(a, dtype=np.int32) for a in (probe_rows, gallery_rows, mate))
+    if pr.ndim != 1 or gr.ndim != 1 or pr.size == 0 or gr.size == 0 or mt.shape != pr.shape:
+        raise ValueError("probe and gallery rows must be one-dimensional and not empty, mate of the probes' length")
+    if not 1 <= int(k) <= MAX_TOP_K:
+        raise ValueError(f"k must be in [1, {MAX_TOP_K}], got {k}")
+    if np.any((mt < -1) | (mt >= gr.size)):
+        raise ValueError("mate must hold positions of the gallery list, or -1")
+    if unit.dim() != 2 or unit.dtype != torch.float64 or not unit.is_contiguous():
+        raise ValueError("unit must be a contiguous float64 [T, D] tensor")
+    dev, (T, D), Q, G, k = unit.device, unit.shape, pr.size, gr.size, int(k)
+    d_pr, d_gr, d_mt = (torch.from_numpy(a).to(dev) for a in (pr, gr, mt))
+    top_score = torch.empty(Q, k, device=dev, dtype=torch.float64)
+    top_idx = torch.empty(Q, k, device=dev, dtype=torch.int32)
+    mate_score = torch.empty(Q, device=dev, dtype=torch.float64)
+    mate_rank = torch.empty(Q, device=dev, dtype=torch.int32)
+    best_nonmate = torch.empty(Q, device=dev, dtype=torch.float64)
+    need = int(lib().lafs_ijb_search_workspace(Q, G, k))
+    ws = torch.empty(max(need, 1), device=dev, dtype=torch.uint8) if need else None
+    call("lafs_ijb_search", _p(unit), T, D, _p(d_pr), Q, _p(d_gr), G, _p(d_mt), k, _p(top_score), _p(top_idx), _p(mate_score),
+         _p(mate_rank), _p(best_nonmate), _p(ws) if need else None, need)
+    return dict(top_score=top_score.cpu().numpy(), top_idx=top_idx.cpu().numpy(), mate_score=mate_score.cpu().numpy(),
+                mate_rank=mate_rank.cpu().numpy(), best_nonmate=best_nonmate.cpu().numpy())
+
+
+def identify(img_feats, faceness, templates, medias, gallery_tids, gallery_sids, probe_tids, probe_sids, k=10, flip=True,
+             detector_score=True, device=None):
+    """One gallery's searches on the device: pools like protocol(), then scores every probe template against every gallery template
+    (lafs_ijb_search).  A template id without images raises, as in 1:1; so do two gallery templates of one subject.
+    -> dict of numpy arrays: top_score f64 / top_idx i32 [Q, k] (positions in gallery_tids, -1 / NaN past the gallery's end),
+    mate_score f64 [Q], mate_rank i32 [Q] (0: a rank-1 hit, -1: no mate), best_nonmate f64 [Q], mate i32 [Q]."""
+    gt, pt = np.asarray(gallery_tids), np.asarray(probe_tids)
+    if gt.shape != np.asarray(gallery_sids).shape or pt.shape != np.asarray(probe_sids).shape:
+        raise ValueError("template and subject ids must be of one length")
+    mate = mates(gallery_sids, probe_sids)
+    unit, uq = pool_templates(img_feats, faceness, templates, medias, flip, detector_score, device)
+    out = search(unit, template_rows(uq, pt), template_rows(uq, gt), mate, k)
+    out["mate"] = mate
+    return out
+
+
+def cmc(mate_rank, ranks=CMC_RANKS):
+    """Closed-set identification rates: the share of the mated searches (mate_rank >= 0) with mate_rank < r, per r in ranks."""
+    mr = np.asarray(mate_rank)
+    mr = mr[mr >= 0]
+    if mr.size == 0:
+        raise ValueError("no mated searches")
+    return np.array([np.count_nonzero(mr < r) / mr.size for r in ranks], dtype=np.float64)
+
+
+def tpir_at_fpir(mate_score, mate_rank, nonmated_top, fpirs=FPIRS, rank=1):
+    """Open-set identification as the IJB-C paper defines it, restated (this project's reading; PARITY UNPINNED).  mate_score / mate_rank:
+    the mated searches; nonmated_top: the top score of every non-mated search.  A search alarms when its top score is > tau.  For an
+    FPIR f over the |N| non-mated searches tau is the (floor(f |N|) + 1)-th largest non-mated top score (f read as the decimal it
+    prints as, so 0.1 * 30 is 3), and -inf when that index exceeds |N|: the realised FPIR never exceeds f.  TPIR is the share of the
+    mated searches with mate_rank < rank and mate_score > tau.  NaN top scores never alarm (they sort below every number) and a NaN
+    mate score is never a hit.  -> (tpir float64 [len(fpirs)], tau float64 [len(fpirs)])."""
+    ms, mr, nt = np.asarray(mate_score, dtype=np.float64), np.asarray(mate_rank), np.asarray(nonmated_top, dtype=np.float64)
+    if ms.ndim != 1 or ms.shape != mr.shape or nt.ndim != 1:
+        raise ValueError("mate_score and mate_rank must be one-dimensional and of one length, nonmated_top one-dimensional")
+    if ms.size == 0:
+        raise ValueError("no mated searches")
+    if nt.size == 0:
+        raise ValueError("no non-mated searches")
+    if np.any(mr < 0):
+        raise ValueError("a mated search has no mate rank")
+    desc = np.sort(np.where(np.isnan(nt), -np.inf, nt))[::-1]
+    tpir, taus = [], []
+    for f in fpirs:
+        if not 0 <= f <= 1:
+            raise ValueError(f"an FPIR must be in [0, 1], got {f}")
+        m = math.floor(Fraction(repr(float(f))) * nt.size)                 # alarms allowed
+        tau = float(desc[m]) if m < nt.size else -np.inf
+        with np.errstate(invalid="ignore"):
+            tpir.append(np.count_nonzero((mr < rank) & (ms > tau)) / ms.size)
+        taus.append(tau)
+    return np.array(tpir, dtype=np.float64), np.array(taus, dtype=np.float64)
+
+
+def identification_metrics(res, ranks=CMC_RANKS, fpirs=FPIRS):
+    """One gallery's searches (identify's dict) -> dict(cmc, tpir, tau): a probe with a mate is a mated search, every other probe a
+    non-mated one."""
+    mated = res["mate"] >= 0
+    tpir, tau = tpir_at_fpir(res["mate_score"][mated], res["mate_rank"][mated], res["top_score"][~mated, 0], fpirs)
+    return dict(cmc=cmc(res["mate_rank"][mated], ranks), tpir=tpir, tau=tau)
+
+
+def evaluate_identification(img_feats, meta, lists, k=10, flip=True, detector_score=True, device=None, ranks=CMC_RANKS, fpirs=FPIRS):
+    """Every probe of lists (read_identification_lists) searched in G1 and in G2: mated in the gallery that holds its subject, non-mated
+    in the other, non-mated in both when neither does.  -> dict(G1=..., G2=... (identification_metrics), mean=dict(cmc, tpir),
+    searches=dict(G1=..., G2=... (identify's arrays)))."""
+    if k < max(ranks):
+        raise ValueError(f"k = {k} is smaller than the largest CMC rank {max(ranks)}")
+    out = {"searches": {}}
+    for g, key in (("G1", "g1"), ("G2", "g2")):
+        res = identify(img_feats, meta["faceness"], meta["templates"], meta["medias"], lists[key + "_tids"], lists[key + "_sids"],
+                       lists["probe_tids"], lists["probe_sids"], k, flip, detector_score, device)
+        out["searches"][g] = res
+        out[g] = identification_metrics(res, ranks, fpirs)
+    out["mean"] = dict(cmc=(out["G1"]["cmc"] + out["G2"]["cmc"]) / 2, tpir=(out["G1"]["tpir"] + out["G2"]["tpir"]) / 2)
+    return out
+
+
+def identification_row(method, target, mean, ranks=CMC_RANKS, fpirs=FPIRS):
+    """The 1:N table row as plain text, '%.2f' percentages like the 1:1 row."""
+    head = ["Methods"] + ["rank-%d" % r for r in ranks] + ["TPIR@FPIR=%s" % f for f in fpirs]
+    row = ["%s-%s" % (method, target)] + ["%.2f" % (100 * v) for v in list(mean["cmc"]) + list(mean["tpir"])]
+    w = [max(len(a), len(b)) for a, b in zip(head, row)]
+    return "\n".join(" | ".join(c.ljust(n) for c, n in zip(r, w)) for r in (head, row))
+
+
 # ----------------------------------------------------------------------------------------------------------------- extraction
 def _decode(path):
     from PIL import Image
@@ -365,7 +572,8 @@ def evaluate(img_feats, meta, flip=True, detector_score=True, device=None):
 
 # ----------------------------------------------------------------------------------------------------------------- entry point
 def main(argv=None):
-    """TAR@FAR of a saved fine-tune checkpoint (the `module.`-prefixed state dict train_largescale.py writes) on IJB-B / IJB-C."""
+    """TAR@FAR (--protocol 11) or rank-k and TPIR@FPIR (--protocol 1N) of a saved fine-tune checkpoint (the `module.`-prefixed state
+    dict train_largescale.py writes) on IJB-B / IJB-C."""
     import torch
     from . import train_largescale as tl
     from .vision_transformer import attach_arena
@@ -381,9 +589,12 @@ def main(argv=None):
     p.add_argument("--no_detector_score", action="store_true", help="use_detector_score = False")
     p.add_argument("--save_features", default="", type=str, help="write img_feats and faceness to this .npz")
     p.add_argument("--features", default="", type=str, help="skip the extraction: read img_feats from this .npz")
+    p.add_argument("--protocol", default="11", type=str, choices=["11", "1N"],
+                   help="11: template verification, TAR@FAR; 1N: identification against G1 and G2, rank-k and TPIR@FPIR")
     args = p.parse_args(argv)
     device = torch.device("cuda", torch.cuda.current_device())
     meta = read_meta(args.image_path, args.target)
+    lists = read_identification_lists(args.image_path, args.target) if args.protocol == "1N" else None
     t0 = time.time()
     if args.features:
         with np.load(args.features, allow_pickle=False) as z:
@@ -406,8 +617,20 @@ def main(argv=None):
         if args.save_features:
             np.savez(args.save_features, img_feats=feats.cpu().numpy(), faceness=meta["faceness"])
     t0 = time.time()
-    scores, fpr, tpr, cells = evaluate(feats, meta, not args.no_flip, not args.no_detector_score, device)
     save_path = os.path.join(args.result_dir, args.job)
+    if args.protocol == "1N":
+        res = evaluate_identification(feats, meta, lists, 10, not args.no_flip, not args.no_detector_score, device)
+        os.makedirs(save_path, exist_ok=True)
+        out = os.path.join(save_path, "%s_1N.npz" % args.target.lower())
+        arrays = {"probe_tids": lists["probe_tids"], "probe_sids": lists["probe_sids"]}
+        for g, key in (("G1", "g1"), ("G2", "g2")):
+            arrays.update({f"{g}_gallery_tids": lists[key + "_tids"], f"{g}_gallery_sids": lists[key + "_sids"]})
+            arrays.update({f"{g}_{name}": a for name, a in res["searches"][g].items()})
+        np.savez(out, **arrays)
+        print(f"[{args.target}] {2 * len(lists['probe_tids'])} searches in {time.time() - t0:.2f} s -> {out}")
+        print(identification_row(args.target.lower(), args.target, res["mean"]))
+        return
+    scores, fpr, tpr, cells = evaluate(feats, meta, not args.no_flip, not args.no_detector_score, device)
     os.makedirs(save_path, exist_ok=True)
     out = os.path.join(save_path, "%s.npy" % args.target.lower())
     np.save(out, scores)

@@ -5,6 +5,9 @@
     <dir>/meta/ijbc_face_tid_mid.txt         name tid mid
     <dir>/meta/ijbc_template_pair_label.txt  tid1 tid2 label
     <dir>/meta/ijbc_name_5pts_score.txt      name x1 y1 ... x5 y5 faceness
+    <dir>/meta/ijbc_1N_gallery_G1.csv        TEMPLATE_ID,SUBJECT_ID,FILENAME per image: templates 0-3
+    <dir>/meta/ijbc_1N_gallery_G2.csv        the same for templates 4-7
+    <dir>/meta/ijbc_1N_probe_mixed.csv       templates 8-15, and one row whose subject is in neither gallery
 
 for end-to-end runs of `python -m lafs_cvpr2024_amd.ijb_evaluation`.  Everything comes from closed forms of the image index (no random
 state), so the tests and the fixture generator rebuild the same images instead of committing them.
@@ -63,6 +66,22 @@ def dataset(n=40):
                 tid=TIDS[tj], mid=mid, p1=p1, p2=p2, label=label)
 
 
+SUBJECTS = 1000 + 7 * np.arange(8)                                # subject id of identity 0 .. 7
+UNKNOWN_SUBJECT = 9999
+
+
+def identification_lists(n=40):
+    """The 1:N lists over the templates that have images among the first n: G1 = templates 0-3, G2 = templates 4-7, probes = templates
+    8-15 (template j + 8 shows the identity of template j) plus template 0 under a subject that neither gallery holds.
+    -> dict(g1_tids, g1_sids, g2_tids, g2_sids, probe_tids, probe_sids), one entry per template."""
+    used = np.unique(np.arange(n) % N_TEMPLATES)
+    pick = lambda lo, hi: used[(used >= lo) & (used < hi)]
+    g1, g2, pr = pick(0, 4), pick(4, 8), pick(8, 16)
+    extra = used[:1] if len(pr) else used[:0]
+    return dict(g1_tids=TIDS[g1], g1_sids=SUBJECTS[g1 % 8], g2_tids=TIDS[g2], g2_sids=SUBJECTS[g2 % 8],
+                probe_tids=np.r_[TIDS[pr], TIDS[extra]], probe_sids=np.r_[SUBJECTS[pr % 8], [UNKNOWN_SUBJECT] * len(extra)])
+
+
 def images(n=40):
     ds = dataset(n)
     return [crop(i, int(ds["ident"][i])) for i in range(n)]
@@ -114,6 +133,13 @@ def make(root, n=40, target="ijbc"):
     with open(os.path.join(root, "meta", target + "_name_5pts_score.txt"), "w") as f:
         for i, name in enumerate(names):
             f.write("%s %s %.4f\n" % (name, " ".join("%.3f" % v for v in ds["lmk"][i].reshape(-1)), ds["faceness"][i]))
+    ls = identification_lists(n)
+    for key, fname in (("g1", "_1N_gallery_G1.csv"), ("g2", "_1N_gallery_G2.csv"), ("probe", "_1N_probe_mixed.csv")):
+        with open(os.path.join(root, "meta", target + fname), "w") as f:
+            f.write("TEMPLATE_ID,SUBJECT_ID,FILENAME\n")
+            for t, sid in zip(ls[key + "_tids"], ls[key + "_sids"]):                 # one row per image, as the dataset's lists have
+                for i in np.flatnonzero(ds["tid"] == t):
+                    f.write("%d,%d,%s\n" % (t, sid, names[i]))
     return ds
 
 

@@ -367,6 +367,39 @@ int lafs_scatter_cls(const float* src, const int32_t* cu_seqlens, int n_seq, int
                      hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * fViT: overlapping patch embedding and BatchNorm1d head  (face_pre_pro/ViT_face.py:1506-1613; csrc/unfold.hip)
+ * ------------------------------------------------------------------------------------------------ */
+/* nn.Unfold(kernel_size=k, stride, padding=pad) + transpose(1, 2) (face_pre_pro/ViT_face.py:1517,1582):
+ * img(f32) [B,3,S,S] -> patches(bf16) [B*n*n, ldp], n = floor((S + 2 pad - k) / stride) + 1 windows per side.  Column c k^2 + i k + j of
+ * row (b, wy, wx) = img[b, c, wy stride - pad + i, wx stride - pad + j], 0 for a tap outside the image; columns [3 k^2, ldp) are 0
+ * (ldp % 32 == 0: the K granule of lafs_gemm_nt).  Same bf16 rounding as lafs_patchify: (k, stride, pad) = (8, 8, 0), ldp = 192 gives
+ * its LAFS_PATCH_ORDER_CHW rows bit for bit.  The image needs no alignment; patches must be 16-byte aligned.  k >= 1, stride >= 1,
+ * 0 <= pad < k, n >= 1; one window row of the three channels (3 k ((n-1) stride + k) floats) must fit 64 KB of LDS. */
+int lafs_unfold_bf16(const float* img, int B, int S, int k, int stride, int pad, void* patches, int ldp, hipStream_t stream);
+/* The adjoint (autograd of :1582 when the image requires a gradient): dpatches(f32) [B*n*n, ld] (columns >= 3 k^2 ignored) ->
+ * dimg(f32) [B,3,S,S], WRITTEN: every pixel is the sum of the window entries that cover it, window rows then window columns ascending
+ * (no atomics, the same bits run to run); a pixel under no window is 0. */
+int lafs_fold_f32(const float* dpatches, int ld, int B, int S, int k, int stride, int pad, float* dimg, hipStream_t stream);
+/* dst(bf16)[r, c] = src(f32)[r, c] for c < cols, 0 for cols <= c < ldd (ldd % 8 == 0, dst 16-byte aligned): the Linear weight
+ * [D, 3 k^2] of :1521,1585 and ready-made 3-D patch vectors (:1583-1584) widened to the ldp columns of lafs_unfold_bf16. */
+int lafs_pad_cast_bf16(const float* src, int lds, int rows, int cols, void* dst, int ldd, hipStream_t stream);
+/* dst(f32)[r, c] = (accumulate ? dst[r, c] : 0) + src[r, c] for c < cols: the first 3 k^2 columns of the ldp-wide weight gradient
+ * into the [D, 3 k^2] gradient of :1521. */
+int lafs_add_cols_f32(const float* src, int lds, int rows, int cols, float* dst, int ldd, int accumulate, hipStream_t stream);
+/* nn.BatchNorm1d(D) on x f32 [n, D] (the mlp_head of :1530-1533,1604).  training != 0 (n >= 2): per column mean and biased variance
+ * (shifted two-pass sums, fixed order, no atomics), y = (x - mean) rstd gamma + beta with rstd = 1 / sqrt(var + eps); running_mean /
+ * running_var (both or neither) become (1 - momentum) old + momentum {mean, var n / (n - 1)}.  training == 0: mean = running_mean,
+ * rstd = 1 / sqrt(running_var + eps), nothing updated.  save_mean / save_rstd f32 [D] receive what y was formed with. */
+int lafs_bn1d_fwd(const float* x, int ldx, int n, int D, const float* gamma, const float* beta, float eps, float momentum,
+                  int training, float* running_mean, float* running_var, float* y, int ldy, float* save_mean, float* save_rstd,
+                  hipStream_t stream);
+/* Backward: xhat = (x - save_mean) save_rstd; dgamma = (accumulate ? dgamma : 0) + sum_r dy xhat, dbeta likewise + sum_r dy;
+ * dx = gamma rstd (dy - dbeta_batch / n - xhat dgamma_batch / n) in training, gamma rstd dy in eval (constant statistics). */
+int lafs_bn1d_bwd(const float* dy, int lddy, const float* x, int ldx, int n, int D, const float* save_mean, const float* save_rstd,
+                  const float* gamma, int training, float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
+                  hipStream_t stream);
+
+/* ------------------------------------------------------------------------------------------------
  * DINO head pieces  (vision_transformer.py:284-287, 299-300)
  * ------------------------------------------------------------------------------------------------ */
 /* y = x / max(||x||_2, 1e-12) row-wise: x f32 [rows, D] -> y bf16 (+ inv_norm f32 [rows]). */

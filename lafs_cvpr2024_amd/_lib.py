@@ -190,6 +190,12 @@ _PROTOS = {
     "lafs_unpatchify_f32": [vp, i32, i32, i32, vp],
     "lafs_patch_gather_fwd": [vp, vp, i32, i32, i32, vp],
     "lafs_patch_gather_bwd": [vp, vp, vp, i32, i32, i32, vp, vp],
+    "lafs_unfold_bf16": [vp, i32, i32, i32, i32, i32, vp, i32],
+    "lafs_fold_f32": [vp, i32, i32, i32, i32, i32, i32, vp],
+    "lafs_pad_cast_bf16": [vp, i32, i32, i32, vp, i32],
+    "lafs_add_cols_f32": [vp, i32, i32, i32, vp, i32, i32],
+    "lafs_bn1d_fwd": [vp, i32, i32, i32, vp, vp, f32, f32, i32, vp, vp, vp, i32, vp, vp],
+    "lafs_bn1d_bwd": [vp, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, i32],
 }
 _NO_STREAM = {
     "lafs_version": ([], i32),

@@ -1,0 +1,258 @@
+// fViT front end and head (face_pre_pro/ViT_face.py:1506-1613): overlapping patch embedding and the BatchNorm1d head.
+//   :1517,1582  nn.Unfold(kernel_size=k, stride, padding) + transpose   -> unfold_kernel (+ its adjoint fold_kernel)
+//   :1530-1533  mlp_head = BatchNorm1d(dim) on the cls rows             -> bn1d_fwd_kernel / bn1d_bwd_kernel
+// All four are HBM-bound glue: the window vectors leave as bf16 rows of ldp columns (3 k^2 padded to the MFMA GEMM's K granule of 32)
+// that lafs_gemm_nt consumes directly.  No atomics anywhere: every sum below runs in a fixed order.
+#include "common.hpp"
+#include "lafs_hip.h"
+
+namespace {
+
+// grid (window row wy, image b).  The k image rows of the three channels that window row covers are staged in LDS once, zero where
+// the window hangs over the image edge (scalar loads: with pad % 4 != 0 or S % 4 != 0 a row starts at an arbitrary float); then the
+// n finished rows of this window row -- contiguous in the output -- leave as 16-byte stores, consecutive lanes on consecutive chunks.
+// tile[c][i][x] at (c * k + i) * ldt + x, x = image column + pad; ldt is odd, so the k-strided walk of the writers spreads over the banks.
+__global__ __launch_bounds__(256) void unfold_kernel(const float* __restrict__ img, int S, int k, int stride, int pad, int n, int ldt,
+                                                     bf16_t* __restrict__ out, int ldp) {
+  extern __shared__ float tile[];
+  const int wy = blockIdx.x, b = blockIdx.y;
+  const int wl = (n - 1) * stride + k;                    // staged columns: image columns -pad .. wl - pad - 1
+  const int y0 = wy * stride - pad;
+  const int lane = threadIdx.x & 63;
+  for (int ci = threadIdx.x >> 6; ci < 3 * k; ci += 4) {  // one wave per staged row ci = c * k + i: the lanes walk along the image row
+    const int c = ci / k, i = ci - c * k;
+    const int y = y0 + i;
+    const bool row_in = y >= 0 && y < S;
+    const float* src = img + (((size_t)b * 3 + c) * S + (row_in ? y : 0)) * S;
+    for (int x = lane; x < wl; x += 64) {
+      const int xs = x - pad;
+      float v = 0.f;
+      if (row_in && xs >= 0 && xs < S) v = src[xs];
+      tile[ci * ldt + x] = v;
+    }
+  }
+  __syncthreads();
+  const int per = ldp >> 3, kk = k * k, K = 3 * kk;
+  bf16_t* dst = out + ((size_t)b * n + wy) * n * ldp;
+  for (int q = threadIdx.x; q < n * per; q += 256) {
+    const int wx = q / per, col0 = (q - wx * per) * 8;
+    int c = col0 / kk, r = col0 - c * kk;
+    int i = r / k, j = r - i * k;
+    const float* base = tile + wx * stride;
+    float v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      v[e] = (col0 + e < K) ? base[(c * k + i) * ldt + j] : 0.f;
+      if (++j == k) { j = 0; if (++i == k) { i = 0; ++c; } }
+    }
+    *reinterpret_cast<uint4*>(dst + (size_t)q * 8) =
+        make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
+  }
+}
+
+// the adjoint as a gather: one thread per pixel adds the window entries that cover it, window rows then window columns ascending
+__global__ __launch_bounds__(256) void fold_kernel(const float* __restrict__ dp, int ld, int B, int S, int k, int stride, int pad, int n,
+                                                   float* __restrict__ dimg) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)B * 3 * S * S) return;
+  const int x = (int)(t % S), y = (int)((t / S) % S), c = (int)((t / ((size_t)S * S)) % 3), b = (int)(t / ((size_t)3 * S * S));
+  const int py = y + pad, px = x + pad;                   // window w covers p  <=>  w * stride <= p < w * stride + k
+  const int wy0 = py >= k ? (py - k) / stride + 1 : 0, wy1 = min(n - 1, py / stride);
+  const int wx0 = px >= k ? (px - k) / stride + 1 : 0, wx1 = min(n - 1, px / stride);
+  float acc = 0.f;
+  for (int wy = wy0; wy <= wy1; ++wy)
+    for (int wx = wx0; wx <= wx1; ++wx)
+      acc += dp[(((size_t)b * n + wy) * n + wx) * ld + (c * k + (py - wy * stride)) * k + (px - wx * stride)];
+  dimg[t] = acc;
+}
+
+// src f32 [rows, cols] -> dst bf16 [rows, ldd], columns [cols, ldd) zero: one thread per 8 output columns
+__global__ __launch_bounds__(256) void pad_cast_kernel(const float* __restrict__ src, int lds_, int rows, int cols, bf16_t* __restrict__ dst,
+                                                       int ldd) {
+  const int per = ldd >> 3;
+  const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (q >= (size_t)rows * per) return;
+  const int r = (int)(q / per), c0 = (int)(q % per) * 8;
+  const float* s = src + (size_t)r * lds_;
+  float v[8];
+#pragma unroll
+  for (int e = 0; e < 8; ++e) v[e] = (c0 + e < cols) ? s[c0 + e] : 0.f;
+  *reinterpret_cast<uint4*>(dst + (size_t)r * ldd + c0) =
+      make_uint4(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]), pack_bf2(v[4], v[5]), pack_bf2(v[6], v[7]));
+}
+
+// dst[r, c] = (accumulate ? dst[r, c] : 0) + src[r, c] for c < cols: the first 3 k^2 columns of the padded weight gradient
+__global__ __launch_bounds__(256) void add_cols_kernel(const float* __restrict__ src, int lds_, int rows, int cols, float* __restrict__ dst,
+                                                       int ldd, int accumulate) {
+  const size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (size_t)rows * cols) return;
+  const int r = (int)(t / cols), c = (int)(t % cols);
+  const float v = src[(size_t)r * lds_ + c];
+  float* d = dst + (size_t)r * ldd + c;
+  *d = accumulate ? *d + v : v;
+}
+
+// ---- BatchNorm1d over the rows of x f32 [n, D].  One workgroup per 64 columns (lane = column: a wave reads 256 contiguous bytes of a
+// row), rows strided over the BN_WAVES waves; the waves' partial sums meet in LDS and are added in wave order.
+// Variance without cancellation: the column is shifted by its first row before it is summed (mean = x0 + sum(x - x0) / n: the sum is
+// of the spread, not of the level), and the squares are of (x - mean) in a second pass.
+constexpr int BN_WAVES = 8;
+
+__device__ __forceinline__ float bn_combine(float (*red)[64], float v, int w, int lane) {
+  __syncthreads();                                        // (the previous round's readers are done with `red`)
+  red[w][lane] = v;
+  __syncthreads();
+  float s = red[0][lane];
+#pragma unroll
+  for (int i = 1; i < BN_WAVES; ++i) s += red[i][lane];
+  return s;
+}
+
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_fwd_kernel(const float* __restrict__ x, int ldx, int n, int D,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                                 float momentum, int training, float* __restrict__ running_mean,
+                                                                 float* __restrict__ running_var, float* __restrict__ y, int ldy,
+                                                                 float* __restrict__ save_mean, float* __restrict__ save_rstd) {
+  __shared__ float red[BN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  const bool on = col < D;                                // (no early return: every lane reaches the barriers)
+  float mean = 0.f, rstd = 0.f;
+  if (training) {
+    const float x0 = on ? x[col] : 0.f;
+    float s = 0.f;
+    if (on) for (int r = w; r < n; r += BN_WAVES) s += x[(size_t)r * ldx + col] - x0;
+    s = bn_combine(red, s, w, lane);
+    mean = x0 + s / (float)n;
+    float q = 0.f;
+    if (on) for (int r = w; r < n; r += BN_WAVES) { const float d = x[(size_t)r * ldx + col] - mean; q = __builtin_fmaf(d, d, q); }
+    q = bn_combine(red, q, w, lane);
+    const float var = q / (float)n;
+    rstd = 1.0f / sqrtf(var + eps);
+    if (on && w == 0 && running_mean != nullptr) {
+      running_mean[col] = (1.0f - momentum) * running_mean[col] + momentum * mean;
+      running_var[col] = (1.0f - momentum) * running_var[col] + momentum * (var * ((float)n / (float)(n - 1)));
+    }
+  } else if (on) {
+    mean = running_mean[col];
+    rstd = 1.0f / sqrtf(running_var[col] + eps);
+  }
+  if (!on) return;
+  if (w == 0) { save_mean[col] = mean; save_rstd[col] = rstd; }
+  const float g = gamma[col], bt = beta[col];
+  for (int r = w; r < n; r += BN_WAVES) y[(size_t)r * ldy + col] = (x[(size_t)r * ldx + col] - mean) * rstd * g + bt;
+}
+
+// training: dx = gamma rstd (dy - mean(dy) - xhat mean(dy xhat));  eval (statistics are constants): dx = gamma rstd dy
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
+                                                                 int n, int D, const float* __restrict__ save_mean,
+                                                                 const float* __restrict__ save_rstd, const float* __restrict__ gamma,
+                                                                 int training, float* __restrict__ dx, int lddx, float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta, int accumulate) {
+  __shared__ float red[BN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  const bool on = col < D;
+  const float mean = on ? save_mean[col] : 0.f, rstd = on ? save_rstd[col] : 0.f;
+  float sb = 0.f, sg = 0.f;
+  if (on)
+    for (int r = w; r < n; r += BN_WAVES) {
+      const float d = dy[(size_t)r * lddy + col];
+      sb += d;
+      sg = __builtin_fmaf(d, (x[(size_t)r * ldx + col] - mean) * rstd, sg);
+    }
+  sb = bn_combine(red, sb, w, lane);
+  sg = bn_combine(red, sg, w, lane);
+  if (!on) return;
+  if (w == 0) {
+    dgamma[col] = accumulate ? dgamma[col] + sg : sg;
+    dbeta[col] = accumulate ? dbeta[col] + sb : sb;
+  }
+  const float gr = gamma[col] * rstd;
+  const float mb = training ? sb / (float)n : 0.f, mg = training ? sg / (float)n : 0.f;
+  for (int r = w; r < n; r += BN_WAVES) {
+    const float xh = (x[(size_t)r * ldx + col] - mean) * rstd;
+    dx[(size_t)r * lddx + col] = gr * (dy[(size_t)r * lddy + col] - mb - xh * mg);
+  }
+}
+
+}  // namespace
+
+static int unfold_windows(int S, int k, int stride, int pad) { return (S + 2 * pad - k) / stride + 1; }
+
+extern "C" int lafs_unfold_bf16(const float* img, int B, int S, int k, int stride, int pad, void* patches, int ldp, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(img && patches && B > 0 && B <= 65535 && S > 0, "bad operand");
+  LAFS_CHECK_ARG(k >= 1 && stride >= 1 && pad >= 0 && pad < k, "window needs k >= 1, stride >= 1, 0 <= pad < k");
+  LAFS_CHECK_ARG(S + 2 * pad >= k, "the padded image is smaller than one window");
+  const int n = unfold_windows(S, k, stride, pad);
+  LAFS_CHECK_ARG(n >= 1 && (long)3 * k * k <= ldp && ldp % 32 == 0, "ldp must be a multiple of 32 and hold the 3 k^2 window values");
+  LAFS_CHECK_ARG(((uintptr_t)patches & 15) == 0, "patches must be 16-byte aligned (16-byte row stores)");
+  const int ldt = ((n - 1) * stride + k) | 1;
+  const size_t lds_bytes = (size_t)3 * k * ldt * sizeof(float);
+  LAFS_CHECK_ARG(lds_bytes <= 65536, "3 k image-row strips must fit the 64 KB of LDS");
+  hipLaunchKernelGGL(unfold_kernel, dim3(n, B), dim3(256), lds_bytes, stream, img, S, k, stride, pad, n, ldt, (bf16_t*)patches, ldp);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_fold_f32(const float* dpatches, int ld, int B, int S, int k, int stride, int pad, float* dimg, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(dpatches && dimg && B > 0 && S > 0, "bad operand");
+  LAFS_CHECK_ARG(k >= 1 && stride >= 1 && pad >= 0 && pad < k, "window needs k >= 1, stride >= 1, 0 <= pad < k");
+  LAFS_CHECK_ARG(S + 2 * pad >= k, "the padded image is smaller than one window");
+  const int n = unfold_windows(S, k, stride, pad);
+  LAFS_CHECK_ARG(n >= 1 && (long)3 * k * k <= ld, "ld must hold the 3 k^2 window values");
+  const size_t total = (size_t)B * 3 * S * S;
+  LAFS_CHECK_ARG(total < ((size_t)1 << 31) * 256, "image batch too large");
+  hipLaunchKernelGGL(fold_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, dpatches, ld, B, S, k, stride, pad, n, dimg);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_pad_cast_bf16(const float* src, int lds, int rows, int cols, void* dst, int ldd, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(src && dst && rows > 0 && cols > 0 && lds >= cols, "bad operand");
+  LAFS_CHECK_ARG(ldd >= cols && ldd % 8 == 0 && ((uintptr_t)dst & 15) == 0, "ldd must be a multiple of 8 and dst 16-byte aligned");
+  const size_t total = (size_t)rows * (ldd / 8);
+  hipLaunchKernelGGL(pad_cast_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, lds, rows, cols, (bf16_t*)dst, ldd);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_add_cols_f32(const float* src, int lds, int rows, int cols, float* dst, int ldd, int accumulate, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(src && dst && rows > 0 && cols > 0 && lds >= cols && ldd >= cols, "bad operand");
+  const size_t total = (size_t)rows * cols;
+  hipLaunchKernelGGL(add_cols_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, stream, src, lds, rows, cols, dst, ldd, accumulate);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_bn1d_fwd(const float* x, int ldx, int n, int D, const float* gamma, const float* beta, float eps, float momentum,
+                             int training, float* running_mean, float* running_var, float* y, int ldy, float* save_mean, float* save_rstd,
+                             hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(x && gamma && beta && y && save_mean && save_rstd, "null operand");
+  LAFS_CHECK_ARG(n > 0 && D > 0 && D <= 2048 && ldx >= D && ldy >= D, "1 <= D <= 2048 and row strides >= D");
+  LAFS_CHECK_ARG(!training || n >= 2, "batch statistics need more than one row (nn.BatchNorm1d: Expected more than 1 value per channel when training)");
+  LAFS_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "running_mean and running_var come together");
+  LAFS_CHECK_ARG(training || running_mean != nullptr, "the eval forward normalises with the running statistics");
+  hipLaunchKernelGGL(bn1d_fwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, x, ldx, n, D, gamma, beta, eps, momentum,
+                     training ? 1 : 0, running_mean, running_var, y, ldy, save_mean, save_rstd);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_bn1d_bwd(const float* dy, int lddy, const float* x, int ldx, int n, int D, const float* save_mean, const float* save_rstd,
+                             const float* gamma, int training, float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
+                             hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(dy && x && save_mean && save_rstd && gamma && dx && dgamma && dbeta, "null operand");
+  LAFS_CHECK_ARG(n > 0 && D > 0 && D <= 2048 && lddy >= D && ldx >= D && lddx >= D, "1 <= D <= 2048 and row strides >= D");
+  LAFS_CHECK_ARG(!training || n >= 2, "batch statistics need more than one row");
+  hipLaunchKernelGGL(bn1d_bwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, dy, lddy, x, ldx, n, D, save_mean, save_rstd,
+                     gamma, training ? 1 : 0, dx, lddx, dgamma, dbeta, accumulate ? 1 : 0);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}

@@ -1,7 +1,8 @@
 """Drop-in surface of the reference's ``face_pre_pro/ViT_face.py`` for the symbols on the hot path
 (SURVEY.md section 8b): ``CosFace``, ``ViT_face_landmark_patch8`` (Part-fViT) and
 ``extract_patches_pytorch_gridsample`` -- same constructor / forward signatures and state_dict keys, running on the
-gfx950 HIP kernels.  Experiment variants the entry points never instantiate are not provided.
+gfx950 HIP kernels -- and for fViT, ``ViTs_face_overlap`` (the plain face transformer with released weights).  The other experiment
+variants the entry points never instantiate are not provided.
 """
 import math
 
@@ -395,3 +396,154 @@ class face_landmark_4simmin_glo_loc(nn.Module):
             return theta, x
         src = x if x_Aug is None else x_Aug
         return theta, extract_patches_pytorch_gridsample(src, theta[:, :num_land], patch_shape=self.patch_shape, num_landm=num_land)
+
+
+# ------------------------------------------------------------------------------------------------- fViT
+class _FViTFunction(torch.autograd.Function):
+    """One crop group of fViT as one autograd node: window embedding, trunk, BatchNorm1d head.  Parameter gradients are accumulated by
+    the kernels into the arena; the position slice and (when it asks for one) the input are differentiable."""
+
+    @staticmethod
+    def forward(ctx, model, hook, x, pos, geom):
+        save = any(ctx.needs_input_grad)
+        drop = model._sample_drop_scales(geom) if model.training else None
+        feat, st, _ = Fn.vit_forward(model._arena, model._spec, geom, [x.contiguous().float()], [pos.detach().contiguous()],
+                                     drop, save=save, dropout=model._next_dropout(), bn_training=model.training)
+        ctx.model, ctx.st = model, (st if save else None)
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        model, st = ctx.model, ctx.st
+        if not ctx.needs_input_grad[2]:
+            dpos = Fn.vit_backward(model._arena, model._spec, st, dfeat)
+            return None, None, None, dpos[0], None
+        dpos, dx = Fn.vit_backward(model._arena, model._spec, st, dfeat, want_dx=True)
+        return None, None, dx[0], dpos[0], None
+
+
+class ViTs_face_overlap(nn.Module):
+    """fViT (reference face_pre_pro/ViT_face.py:1506-1613): the Part-fViT transformer (pre-LN, bias-free qkv, scale dim**-0.5,
+    ``heads * 64`` inner width, DropPath on every residual branch) behind an OVERLAPPING patch embedding -- nn.Unfold(ac_patch_size,
+    stride patch_size, padding pad) + Linear, one lafs_unfold_bf16 launch + the embedding GEMM here -- and with a BatchNorm1d head on the
+    cls rows (lafs_bn1d_fwd / lafs_bn1d_bwd).  4-D images or 3-D [B, n, 3 * ac_patch_size**2] window vectors; a list of crops runs
+    one pass per run of equal-sided crops, so the batch statistics and the running-statistic updates are per group, in list order.
+    ``soft_split``, ``dropout`` and ``to_latent`` are kept as attributes for parity and never called; ``fc``, whose result the
+    reference discards (:1606-1607), is ignored.  ``drop_path_rate``: the reference hard-codes 0.1 in Residual_droppath."""
+
+    def __init__(self, *, loss_type, GPU_ID, num_class, image_size, patch_size, ac_patch_size, pad, dim, depth, heads, mlp_dim,
+                 pool='cls', channels=3, dim_head=64, dropout=0., emb_dropout=0., drop_path_rate=0.1):
+        super().__init__()
+        if pool != 'cls':
+            raise NotImplementedError("only cls pooling is on the hot path (the gather kernel reads the first row of every sequence)")
+        if channels != 3:
+            raise NotImplementedError("lafs_unfold_bf16 reads 3-channel images")
+        if dim_head != 64:
+            raise NotImplementedError("the attention kernels are specialised for head_dim 64")
+        if not (0.0 <= dropout < 1.0 and 0.0 <= emb_dropout < 1.0):
+            raise ValueError("dropout rates must be in [0, 1)")
+        if not (ac_patch_size >= 1 and patch_size >= 1 and 0 <= pad < ac_patch_size):
+            raise ValueError("the embedding window needs ac_patch_size >= 1, patch_size >= 1 and 0 <= pad < ac_patch_size")
+        num_patches = (image_size // patch_size) ** 2
+        if num_patches <= 16:                             # reference :1513 (MIN_NUM_PATCHES)
+            raise ValueError(f"your number of patches ({num_patches}) is way too small for attention to be effective (at least 16)")
+        self.patch_size, self.ac_patch_size, self.pad, self.num_patches = patch_size, ac_patch_size, pad, num_patches
+        self.soft_split = nn.Unfold(kernel_size=(ac_patch_size, ac_patch_size), stride=(patch_size, patch_size), padding=(pad, pad))
+        self.dim, self.depth, self.heads, self.mlp_dim = dim, depth, heads, mlp_dim
+        self.drop_path_rate = drop_path_rate
+        self.dropout_rate, self.emb_dropout_rate, self._drop_seed0, self._drop_step = float(dropout), float(emb_dropout), 0x5EED, 0
+        inner = heads * dim_head
+        self.pos_embedding = nn.Parameter(torch.randn(1, num_patches + 1, dim))
+        self.patch_to_embedding = nn.Linear(channels * ac_patch_size ** 2, dim)
+        self.cls_token = nn.Parameter(torch.randn(1, 1, dim))
+        self.dropout = nn.Dropout(emb_dropout)
+        self.transformer = _Holder()
+        layers = []
+        for _ in range(depth):
+            att = _Holder(); att.fn = _Holder(); att.fn.norm = nn.LayerNorm(dim); att.fn.fn = _Holder()
+            att.fn.fn.to_qkv = nn.Linear(dim, inner * 3, bias=False)
+            att.fn.fn.to_out = nn.Sequential(nn.Linear(inner, dim), nn.Dropout(dropout))
+            ff = _Holder(); ff.fn = _Holder(); ff.fn.norm = nn.LayerNorm(dim); ff.fn.fn = _Holder()
+            ff.fn.fn.net = nn.Sequential(nn.Linear(dim, mlp_dim), nn.GELU(), nn.Dropout(dropout), nn.Linear(mlp_dim, dim), nn.Dropout(dropout))
+            layers.append(nn.ModuleList([att, ff]))
+        self.transformer.layers = nn.ModuleList(layers)
+        self.pool = pool
+        self.to_latent = nn.Identity()
+        self.mlp_head = nn.Sequential(nn.BatchNorm1d(dim))
+        self.loss_type, self.pred, self.GPU_ID, self.fc = loss_type, None, GPU_ID, None     # (no loss module: commented out at :1539-1549)
+        self._arena, self._spec, self._hook = None, None, None
+
+    _sample_drop_scales = ViT_face_landmark_patch8._sample_drop_scales
+    _next_dropout = ViT_face_landmark_patch8._next_dropout
+
+    def _bind_arena(self, arena, prefix):
+        from dataclasses import replace
+        ViT_face_landmark_patch8._bind_arena(self, arena, prefix)           # the same transformer, the same block naming
+        bn = self.mlp_head[0]
+        if bn.momentum is None or not bn.track_running_stats or not bn.affine:
+            raise NotImplementedError("lafs_bn1d_fwd implements nn.BatchNorm1d's defaults: affine, running statistics, a fixed momentum")
+        self._spec = replace(self._spec, patch_order=_lib.PATCH_ORDER_CHW, window=(self.ac_patch_size, self.patch_size, self.pad),
+                             head="batchnorm", bn_mean="mlp_head.0.running_mean", bn_var="mlp_head.0.running_var",
+                             bn_eps=float(bn.eps), bn_momentum=float(bn.momentum))
+
+    def forward(self, x, return_before_head=False, patch_drop=0., for_fea=False):
+        """(reference :1550-1573)  A tensor or a list of crops; consecutive crops of equal side form one group."""
+        if for_fea:
+            return self.forward_features(x, patch_drop=patch_drop)
+        if not isinstance(x, list):
+            x = [x]
+        h, z, start = None, None, 0
+        while start < len(x):
+            end = start + 1
+            while end < len(x) and x[end].shape[-1] == x[start].shape[-1]:
+                end += 1
+            _h = self.forward_features(torch.cat(x[start:end]) if end - start > 1 else x[start], patch_drop=patch_drop)
+            _z = self.forward_head(_h)
+            h, z = (_h, _z) if h is None else (torch.cat((h, _h)), torch.cat((z, _z)))
+            patch_drop, start = 0., end
+        return (h, z) if return_before_head else z
+
+    def forward_head(self, x):
+        return self.pred(x) if self.pred is not None else x
+
+    def forward_features(self, img, label=None, mask=None, patch_drop=None):
+        """(reference :1578-1613)  One group: [B, 3, S, S] images or [B, n, 3 k^2] window vectors -> BatchNorm1d(cls) f32 [B, dim].
+        The position table is sliced ``[:, :n + 1]``, not resampled (:1590)."""
+        if mask is not None:
+            raise NotImplementedError("attention masks are not on the hot path (the packed attention kernels take none)")
+        if label is not None:
+            raise NotImplementedError("the reference builds no loss module for this class (its construction is commented out at "
+                                      ":1539-1549), so its label branch cannot run there either")
+        if patch_drop is not None and patch_drop > 0:
+            raise NotImplementedError("patch_drop > 0 leaves a non-square number of tokens, which the packed geometry cannot describe yet")
+        if self._arena is None:
+            attach_arena(self)
+        self._arena.ensure_fresh()
+        k, stride, pad = self.ac_patch_size, self.patch_size, self.pad
+        n_img = img.shape[0]
+        if img.dim() == 4:
+            if img.shape[1] != 3 or img.shape[-1] != img.shape[-2]:
+                raise ValueError(f"expected square 3-channel images, got {tuple(img.shape)}")
+            side = img.shape[-1]
+            r = ops.unfold_windows(side, k, stride, pad) if side + 2 * pad >= k else 0
+        elif img.dim() == 3:
+            r = int(math.isqrt(img.shape[1]))
+            if r * r != img.shape[1] or img.shape[2] != 3 * k * k:
+                raise ValueError(f"expected [B, n, {3 * k * k}] window vectors with a square n, got {tuple(img.shape)}")
+            side = (r - 1) * stride + k - 2 * pad         # a side that unfolds into r x r windows
+        else:
+            raise ValueError(f"expected a 4-D image batch or 3-D window vectors, got {img.dim()} dimensions")
+        n = r * r
+        if n < 1:
+            raise ValueError(f"a {side}-pixel image is smaller than one {k}-pixel window")
+        if n > self.num_patches:
+            raise ValueError(f"the input unfolds into {n} windows, the position table holds {self.num_patches} "
+                             f"((image_size // patch_size) ** 2): build the model with a larger image_size")
+        bn = self.mlp_head[0]
+        if self.training and n_img < 2:                   # what nn.BatchNorm1d raises (torch/nn/functional.py _verify_batch_size)
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([n_img, self.dim])}")
+        geom = Fn.geometry([(n_img, side)], img.device, window=(k, stride, pad))
+        emb = _FViTFunction.apply(self, self._hook, img, self.pos_embedding[0, :n + 1], geom)
+        if self.training:
+            bn.num_batches_tracked += 1
+        return emb

@@ -32,11 +32,12 @@ class PackedGeometry:
     seq_start: list = field(default_factory=list)     # first sequence index of each group
     cu_seqlens: torch.Tensor = None
     row2seq: torch.Tensor = None
+    window: tuple = None                # (k, stride, pad) of an overlapping embedding (fViT's nn.Unfold); None: side // patch per side
 
     def __post_init__(self):
         cu, r2s, tok, seq = [0], [], 0, 0
-        for n_img, side in self.groups:
-            n = (side // self.patch) ** 2 + 1
+        for gi, (n_img, side) in enumerate(self.groups):
+            n = self.npatch(gi) + 1
             self.tok_start.append(tok)
             self.seq_start.append(seq)
             for _ in range(n_img):
@@ -50,16 +51,20 @@ class PackedGeometry:
         self.row2seq = torch.cat(r2s).to(self.device)
 
     def npatch(self, gi):
-        return (self.groups[gi][1] // self.patch) ** 2
+        side = self.groups[gi][1]
+        if self.window is not None:
+            k, stride, pad = self.window
+            return ops.unfold_windows(side, k, stride, pad) ** 2
+        return (side // self.patch) ** 2
 
 
 _GEOM_CACHE = {}
 
 
-def geometry(groups, device, patch=8):
-    key = (tuple(groups), str(device), patch)
+def geometry(groups, device, patch=8, window=None):
+    key = (tuple(groups), str(device), patch) if window is None else (tuple(groups), str(device), patch, tuple(window))
     if key not in _GEOM_CACHE:
-        _GEOM_CACHE[key] = PackedGeometry(tuple(groups), patch, device)
+        _GEOM_CACHE[key] = PackedGeometry(tuple(groups), patch, device, window=None if window is None else tuple(window))
     return _GEOM_CACHE[key]
 
 
@@ -108,7 +113,7 @@ def make_trunk_desc(arena, spec: TrunkSpec, geom: PackedGeometry, drop_scales=No
     if 1 < len(geom.groups) <= 4:                        # one attention launch per crop resolution
         d.n_groups = len(geom.groups)
         for gi, (n_img, side) in enumerate(geom.groups):
-            d.group_n_seq[gi], d.group_max_len[gi] = n_img, (side // geom.patch) ** 2 + 1
+            d.group_n_seq[gi], d.group_max_len[gi] = n_img, geom.npatch(gi) + 1
     ctx = getattr(arena, "ctx", None) or _lib.default_ctx(arena.master.device)
     d.ctx = ctx.handle
     d._keep = (blocks, drop_scales, geom, arena, dropout_step, ctx)
@@ -134,21 +139,37 @@ class ViTSpec:
     final_g: str = "norm.weight"
     final_b: str = "norm.bias"
     pos: str = "pos_embed"             # position table: resampled per crop size (DINO ViT) or sliced [:n+1] (Part-fViT)
+    # embedding window (k, stride, pad): (8, 8, 0) is the non-overlapping lafs_patchify path; anything else is fViT's nn.Unfold +
+    # Linear (face_pre_pro/ViT_face.py:1517,1582-1585) through lafs_unfold_bf16 with nn.Unfold's (c, i, j) column order
+    window: tuple = (8, 8, 0)
+    # head on the cls rows: "layernorm" (final_g / final_b, trunk.ln_eps) or "batchnorm" (fViT's BatchNorm1d, :1530-1533: final_g /
+    # final_b are its weight / bias, bn_mean / bn_var the names of its running buffers on the arena's module)
+    head: str = "layernorm"
+    bn_mean: str = "mlp_head.0.running_mean"
+    bn_var: str = "mlp_head.0.running_var"
+    bn_eps: float = 1e-5
+    bn_momentum: float = 0.1
+
+    @property
+    def overlapping(self):
+        return tuple(self.window) != (8, 8, 0)
 
 
 class ViTState:
     """Buffers kept between forward and backward of one packed ViT pass."""
-    __slots__ = ("geom", "desc", "ws", "x_in", "patches", "cls_rows", "stats", "feat", "dropout", "bwd_done")
+    __slots__ = ("geom", "desc", "ws", "x_in", "patches", "cls_rows", "stats", "feat", "dropout", "bwd_done", "bn_training", "in_dims")
 
 
 EMB_DROP_SITE = 0x40000000          # seed offset of the embedding dropout (the trunk sites use seed + 3*layer + {0,1,2})
 
 
 def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, drop_scales=None, save=True,
-                ws=None, x_in=None, x_out=None, dropout=None, wgrad_overwrite=False, wgrad_workgroups=0, wgrad_defer=False):
+                ws=None, x_in=None, x_out=None, dropout=None, wgrad_overwrite=False, wgrad_workgroups=0, wgrad_defer=False,
+                bn_training=False):
     """imgs: list of fp32 NCHW tensors (one per group); pos_tokens: list of fp32 [npatch+1, D] per group.
     dropout: None or (p_trunk, p_embedding, seed[, step]): element dropout of Part-fViT (counter-based masks, see lafs_hip.h);
     `step`: a DEVICE float tensor whose value x 7919 is added to the seed inside the kernels (graph-captured steps).
+    bn_training (BatchNorm1d head only): batch statistics over the n_seq cls rows + running-statistic update, else running statistics.
     Returns (feat f32 [n_seq, D], state)."""
     D = spec.trunk.dim
     dev = imgs[0].device
@@ -166,10 +187,25 @@ def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, dr
     if x_out is None:
         x_out = torch.empty(geom.n_tok, D, device=dev, dtype=f32)
     st.patches = []
-    wpe = arena.bf(pre + spec.w_patch).view(D, -1)
+    st.in_dims = [img.dim() for img in imgs]
+    if spec.overlapping:                                  # bf16 copy of the Linear weight [D, 3 k^2], zero-padded to the ldp columns
+        k, stride, pad = spec.window                      # of the window rows; re-made from the master on every forward
+        if geom.window != tuple(spec.window):
+            raise _lib.LafsHipError(f"geometry built for window {geom.window}, the model embeds with {tuple(spec.window)}")
+        ldp = ops.unfold_ld(k)
+        wpe = ops.pad_cast_bf16(arena.view(arena.master, pre + spec.w_patch).view(D, 3 * k * k), ldp)
+    else:
+        wpe = arena.bf(pre + spec.w_patch).view(D, -1)
     for gi, img in enumerate(imgs):
         n_img, np_ = geom.groups[gi][0], geom.npatch(gi)
-        if img.dim() == 3:                                # already '(p1 p2 c)' patch vectors [n_img, n, 192] (3-D input path)
+        if spec.overlapping:
+            if img.dim() == 3:                            # ready window vectors [n_img, n, 3 k^2] (reference :1583-1584): only padded
+                if img.shape[-1] != 3 * k * k or img.shape[1] != np_:
+                    raise _lib.LafsHipError(f"patch vectors {tuple(img.shape)}: expected [{n_img}, {np_}, {3 * k * k}]")
+                pt = ops.pad_cast_bf16(img.reshape(-1, 3 * k * k).contiguous().float(), ldp)
+            else:
+                pt = ops.unfold(img, k, stride, pad, ldp=ldp)
+        elif img.dim() == 3:                              # already '(p1 p2 c)' patch vectors [n_img, n, 192] (3-D input path)
             pt = ops.scale_cast_bf16(img.reshape(-1, img.shape[-1]).contiguous().float())
         else:
             pt = ops.patchify(img, spec.patch_order)
@@ -183,9 +219,20 @@ def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, dr
     call("lafs_trunk_forward", C.byref(st.desc), _p(st.x_in), _p(x_out), _p(st.ws), 1 if save else 0)
     st.cls_rows = torch.empty(geom.n_seq, D, device=dev, dtype=f32)
     call("lafs_gather_cls", _p(x_out), D, _p(geom.cu_seqlens), geom.n_seq, D, _p(st.cls_rows))
-    _, feat, st.stats = ops.layernorm_fwd(st.cls_rows, arena.view(arena.master, pre + spec.final_g),
-                                          arena.view(arena.master, pre + spec.final_b), spec.trunk.ln_eps,
-                                          want_bf16=False, want_f32=True)
+    st.bn_training = bool(bn_training)
+    if spec.head == "batchnorm":
+        if len(geom.groups) != 1:                         # (the statistics are per crop resolution: reference :1561-1563)
+            raise _lib.LafsHipError("the BatchNorm1d head takes one crop resolution per pass (its batch statistics are per group)")
+        rm, rv = arena.module.get_buffer(pre + spec.bn_mean), arena.module.get_buffer(pre + spec.bn_var)
+        feat, mean, rstd = ops.bn1d_fwd(st.cls_rows, arena.view(arena.master, pre + spec.final_g),
+                                        arena.view(arena.master, pre + spec.final_b), spec.bn_eps, spec.bn_momentum, st.bn_training, rm, rv)
+        st.stats = (mean, rstd)
+    elif spec.head == "layernorm":
+        _, feat, st.stats = ops.layernorm_fwd(st.cls_rows, arena.view(arena.master, pre + spec.final_g),
+                                              arena.view(arena.master, pre + spec.final_b), spec.trunk.ln_eps,
+                                              want_bf16=False, want_f32=True)
+    else:
+        raise _lib.LafsHipError(f"unknown head kind {spec.head!r}")
     st.feat = feat
     return feat, st, x_out
 
@@ -249,9 +296,13 @@ def vit_backward_begin(arena, spec: ViTSpec, st: ViTState, dfeat, g_buf=None):
     geom, D, pre = st.geom, spec.trunk.dim, spec.prefix
     dev = dfeat.device
     gv = lambda n: arena.view(arena.grad, pre + n)
-    dcls_rows = torch.empty(geom.n_seq, D, device=dev, dtype=f32)
-    ops.layernorm_bwd(dfeat.contiguous(), st.cls_rows, st.stats, arena.view(arena.master, pre + spec.final_g), dcls_rows,
-                      gv(spec.final_g), gv(spec.final_b), accumulate=False)
+    if spec.head == "batchnorm":
+        dcls_rows = ops.bn1d_bwd(dfeat.contiguous().float(), st.cls_rows, st.stats[0], st.stats[1], arena.view(arena.master, pre + spec.final_g),
+                                 st.bn_training, gv(spec.final_g), gv(spec.final_b), accumulate=True)
+    else:
+        dcls_rows = torch.empty(geom.n_seq, D, device=dev, dtype=f32)
+        ops.layernorm_bwd(dfeat.contiguous(), st.cls_rows, st.stats, arena.view(arena.master, pre + spec.final_g), dcls_rows,
+                          gv(spec.final_g), gv(spec.final_b), accumulate=False)
     g = g_buf if g_buf is not None else torch.empty(geom.n_tok, D, device=dev, dtype=f32)
     ops.zero_(g)
     call("lafs_scatter_cls", _p(dcls_rows), _p(geom.cu_seqlens), geom.n_seq, D, _p(g), D)
@@ -295,9 +346,13 @@ def vit_backward_end(arena, spec: ViTSpec, st: ViTState, g, want_dx=False, dpos_
     if p_emb > 0:                                         # backward of the embedding dropout: the same mask on the gradient
         call("lafs_dropout_f32", _p(g), D, geom.n_tok, D, float(p_emb), (dseed + EMB_DROP_SITE) & 0xFFFFFFFF, _p(dstep))
     wt = None
+    K3 = 3 * spec.window[0] ** 2 if spec.overlapping else 192
+    ldp = ops.unfold_ld(spec.window[0]) if spec.overlapping else 192
     if want_dx:                                           # W_patch^T bf16 [192, D]: B operand of dP = dTok @ W_patch
-        wt = torch.empty(192, D, device=dev, dtype=bf16)
-        call("lafs_transpose_cast_bf16", _p(arena.view(arena.master, pre + spec.w_patch)), D, 192, _p(wt), D)
+        wt = torch.empty(ldp, D, device=dev, dtype=bf16)  # (overlapping: [ldp, D], the rows behind 3 k^2 zero like the pad columns)
+        if ldp != K3:
+            ops.zero_(wt)
+        call("lafs_transpose_cast_bf16", _p(arena.view(arena.master, pre + spec.w_patch)), D, K3, _p(wt), D)
     for gi in range(len(geom.groups)):
         n_img, np_ = geom.groups[gi][0], geom.npatch(gi)
         rows = g[geom.tok_start[gi]: geom.tok_start[gi] + n_img * (np_ + 1)]
@@ -312,13 +367,25 @@ def vit_backward_end(arena, spec: ViTSpec, st: ViTState, g, want_dx=False, dpos_
         call("lafs_embed_bwd", _p(rows), D, n_img, np_, D, _p(gp), _p(dp), _p(gv(spec.cls)), _p(ws))
         # (capped to EMBED_WGRAD_CUS workgroups: the output is two 192 x 192 tiles, and the default plan -- as many token slices as fill
         # the chip -- would fold 128 slice images, 38 MB, for a 295 KB gradient)
-        prob = [(gp, st.patches[gi], gv(spec.w_patch).view(D, -1), True, gv(spec.b_patch))]
+        # overlapping windows: gp^T @ patches over the ldp columns into a scratch image, whose first 3 k^2 columns are then added to the
+        # arena's gradient (the pad columns of the patches are zero, so are the scratch's)
+        dw = arena.scratch(("embed_dw", D, ldp), D * ldp)[:D * ldp].view(D, ldp) if ldp != K3 else gv(spec.w_patch).view(D, -1)
+        prob = [(gp, st.patches[gi], dw, ldp == K3, gv(spec.b_patch))]
         items, Mp = ops._wgrad_items(prob)
-        wws = arena.scratch(("embed_wgrad", Mp, D), max(int(_lib.lib().lafs_wgrad_group_workspace_bytes(items, 1, Mp, EMBED_WGRAD_CUS)), 16) // 4)
+        wws = arena.scratch(("embed_wgrad", Mp, D) + ((ldp,) if ldp != K3 else ()), max(int(_lib.lib().lafs_wgrad_group_workspace_bytes(items, 1, Mp, EMBED_WGRAD_CUS)), 16) // 4)
         ops.wgrad_group(prob, workspace=wws, max_workgroups=EMBED_WGRAD_CUS)
+        if ldp != K3:
+            ops.add_cols(dw, gv(spec.w_patch).view(D, K3), accumulate=True)
         dpos.append(dp)
         if want_dx:
-            dx.append(ops.gemm_nt(gp, wt, _lib.EPI_F32).view(n_img, np_, 192))
+            dxp = ops.gemm_nt(gp, wt, _lib.EPI_F32)
+            if not spec.overlapping:
+                dx.append(dxp.view(n_img, np_, 192))
+            elif st.in_dims[gi] == 3:
+                dx.append(dxp.view(n_img, np_, ldp)[:, :, :K3])
+            else:
+                k, stride, pad = spec.window
+                dx.append(ops.fold(dxp, n_img, geom.groups[gi][1], k, stride, pad))
     return (dpos, dx) if want_dx else dpos
 
 

@@ -319,6 +319,75 @@ def patchify(img, order=_lib.PATCH_ORDER_CHW):
     return out
 
 
+def unfold_windows(S, k, stride, pad):
+    """Windows per side of nn.Unfold(kernel_size=k, stride=stride, padding=pad) on an S x S image."""
+    return (S + 2 * pad - k) // stride + 1
+
+
+def unfold_ld(k):
+    """Row stride of the window vectors: 3 k^2 rounded up to the K granule (32) of lafs_gemm_nt."""
+    return (3 * k * k + 31) // 32 * 32
+
+
+def unfold(img, k, stride, pad, out=None, ldp=None):
+    """nn.Unfold + transpose as bf16 rows [B n n, ldp] (lafs_unfold_bf16); columns >= 3 k^2 are zero."""
+    _chk(img, torch.float32, "img")
+    B, _, S, _ = img.shape
+    n = unfold_windows(S, k, stride, pad)
+    ldp = unfold_ld(k) if ldp is None else ldp
+    if out is None:
+        out = torch.empty(B * max(n, 0) ** 2, ldp, device=img.device, dtype=bf16)
+    call("lafs_unfold_bf16", _p(img.contiguous()), B, S, k, stride, pad, _p(out), ldp)
+    return out
+
+
+def fold(dpatches, B, S, k, stride, pad):
+    """The adjoint of `unfold` on f32 rows [B n n, ld] -> f32 [B, 3, S, S] (lafs_fold_f32: gather form, deterministic)."""
+    _chk(dpatches, torch.float32, "dpatches")
+    out = torch.empty(B, 3, S, S, device=dpatches.device, dtype=torch.float32)
+    call("lafs_fold_f32", _p(dpatches), _ld(dpatches), B, S, k, stride, pad, _p(out))
+    return out
+
+
+def pad_cast_bf16(src, ldd):
+    """f32 [rows, cols] -> bf16 [rows, ldd] with a zero tail (lafs_pad_cast_bf16)."""
+    _chk(src, torch.float32, "src")
+    rows, cols = src.shape
+    out = torch.empty(rows, ldd, device=src.device, dtype=bf16)
+    call("lafs_pad_cast_bf16", _p(src), _ld(src), rows, cols, _p(out), ldd)
+    return out
+
+
+def add_cols(src, dst, accumulate=True):
+    """dst[:, :cols] (+)= src[:, :cols], cols = dst.shape[1] (lafs_add_cols_f32)."""
+    _chk(src, torch.float32, "src"); _chk(dst, torch.float32, "dst")
+    rows, cols = dst.shape
+    call("lafs_add_cols_f32", _p(src), _ld(src), rows, cols, _p(dst), _ld(dst), 1 if accumulate else 0)
+    return dst
+
+
+def bn1d_fwd(x, gamma, beta, eps, momentum, training, running_mean, running_var):
+    """nn.BatchNorm1d on f32 [n, D] (lafs_bn1d_fwd).  Returns (y, save_mean, save_rstd); training updates the running buffers in place."""
+    _chk(x, torch.float32, "x")
+    n, D = x.shape
+    y = torch.empty(n, D, device=x.device, dtype=torch.float32)
+    mean = torch.empty(D, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(D, device=x.device, dtype=torch.float32)
+    call("lafs_bn1d_fwd", _p(x), _ld(x), n, D, _p(gamma), _p(beta), float(eps), float(momentum), 1 if training else 0,
+         _p(running_mean), _p(running_var), _p(y), D, _p(mean), _p(rstd))
+    return y, mean, rstd
+
+
+def bn1d_bwd(dy, x, mean, rstd, gamma, training, dgamma, dbeta, accumulate=True):
+    """Backward of bn1d_fwd (lafs_bn1d_bwd): returns dx; dgamma / dbeta are accumulated into or overwritten."""
+    _chk(dy, torch.float32, "dy"); _chk(x, torch.float32, "x")
+    n, D = x.shape
+    dx = torch.empty(n, D, device=x.device, dtype=torch.float32)
+    call("lafs_bn1d_bwd", _p(dy), _ld(dy), _p(x), _ld(x), n, D, _p(mean), _p(rstd), _p(gamma), 1 if training else 0, _p(dx), D,
+         _p(dgamma), _p(dbeta), 1 if accumulate else 0)
+    return dx
+
+
 def dino_head_loss(zn_s, zn_t, wn_s, wn_t, center, ncrops, K, student_temp, teacher_temp, grad, loss=None, colsum=None, ws=None,
                    dev_temps=None, grad_scale=1.0):
     """DINOHead's last layer of both networks + DINO loss + centre row sums with the logits never stored (csrc/dino_head_loss.hip).

@@ -148,9 +148,24 @@ int lafs_gemm_nt(const lafs_gemm_nt_args* args, hipStream_t stream);
  * 3 = the tiled kernel in its 128x384 / 12-wave form (whole N per workgroup: long reductions onto N = 384 whose tiles fit one
  * round of the chip), 4 = the tiled kernel with 160-row tiles (long reductions whose 128-row tiles would spill into one more
  * round of the 512 workgroup slots than 160-row ones need), 5 = the 256x256 one-workgroup-per-CU kernel (gemm_big.hip).
- * Mirrors lafs_gemm_nt's own decisions, including its operand-format and validation order; a request that breaks the alignment
- * contract above (which lafs_gemm_nt refuses) gives a negative code here too, not a route. */
+ * This is lafs_gemm_nt's own decision, not a restatement of it: both run the same plan.  A request lafs_gemm_nt refuses -- for
+ * any reason: a null operand, K % 32, alignment, the fp16 rule, the dropout ranges, a missing epilogue operand, a biased K split --
+ * gives the same negative code here, not a route, and sets lafs_last_error().  No device is needed and nothing is dereferenced. */
 int lafs_gemm_nt_route(const lafs_gemm_nt_args* args);
+/* The whole plan of a request, from the same call: what lafs_gemm_nt would launch.  Returns 0 and fills *out, or the negative code
+ * lafs_gemm_nt would return (then *out is untouched).
+ *   route            as lafs_gemm_nt_route
+ *   tile_m, tile_n   output rows x columns of a workgroup's tile (tiled kernel: 128 / 160 / 256 x 128 / 384; K-resident: one work
+ *                    item, 128 x 64; one-workgroup-per-CU kernel: 160 / 176 / 192 / 256 x 256)
+ *   stage_k          k-depth of a pipeline stage (32 or 64; K-resident: 384, a stage holds weight rows over the whole K)
+ *   threads          threads per workgroup
+ *   f16              1: the fp16 instantiation (operand_f16)
+ *   k_slices         K slices (> 1 only for ATOMIC_F32 / F32 with splits: lafs_gemm_nt_slices)
+ *   workgroups       workgroups launched, over all K slices */
+typedef struct lafs_gemm_nt_plan_info {
+  int route, tile_m, tile_n, stage_k, threads, f16, k_slices, workgroups;
+} lafs_gemm_nt_plan_info;
+int lafs_gemm_nt_plan(const lafs_gemm_nt_args* args, lafs_gemm_nt_plan_info* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Fused MLP of a ViT-S block (csrc/mlp_fused.hip): two chained GEMMs, the hidden-wide intermediate never leaves the chip.

@@ -26,6 +26,10 @@ class GemmNTArgs(C.Structure):
                 ("ctx", C.c_void_p)]
 
 
+class GemmNTPlanInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("route", "tile_m", "tile_n", "stage_k", "threads", "f16", "k_slices", "workgroups")]
+
+
 class MlpArgs(C.Structure):
     _fields_ = [("X", C.c_void_p), ("ldx", C.c_int), ("Wa", C.c_void_p), ("ldwa", C.c_int), ("Wb", C.c_void_p), ("ldwb", C.c_int),
                 ("M", C.c_int), ("H", C.c_int), ("mode", C.c_int), ("bias_a", C.c_void_p), ("bias_b", C.c_void_p),
@@ -201,6 +205,7 @@ _NO_STREAM = {
     "lafs_version": ([], i32),
     "lafs_gemm_nt_slices": ([i32, i32], i32),
     "lafs_gemm_nt_route": ([C.POINTER(GemmNTArgs)], i32),
+    "lafs_gemm_nt_plan": ([C.POINTER(GemmNTArgs), C.POINTER(GemmNTPlanInfo)], i32),
     "lafs_mlp_fused_supported": ([i32, i32, i32], i32),
     "lafs_mlp_fused_ln_parts": ([i32], i32),
     "lafs_ctx_create": ([i32], vp),

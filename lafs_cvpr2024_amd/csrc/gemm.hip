@@ -17,8 +17,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "lafs_hip.h"
-#include "gemm_kres.hpp"
-#include "gemm_big.hpp"
+#include "gemm_plan.hpp"
 #include "ctx.hpp"
 
 namespace {
@@ -96,7 +95,7 @@ __device__ __forceinline__ int xcd_tile(int b, int n) {
 // full 128-byte cache lines per row piece).
 template <int BK> __device__ __forceinline__ int nt_swzk(int row) { return BK == 32 ? nt_swz(row) : (row & 7); }
 
-// WN = wave columns: 2 -> 128-wide tiles (default), 6 -> 384-wide (128x384, 12 waves: see launch_nt).
+// WN = wave columns: 2 -> 128-wide tiles (default), 6 -> 384-wide (128x384, 12 waves: see plan_tiled).
 // F16: operands (and a 16-bit output / residual) are IEEE fp16 instead of bf16 -- the trainable landmark CNN's plan
 // (landmark_train.py); instantiated for the plain, activation and fp32 epilogues on 128x128 tiles only.
 template <int EPI, int WM, int BK, int WN = 2, bool F16 = false, int MB = 4>
@@ -635,79 +634,6 @@ __global__ __launch_bounds__(256) void sum_slices_kernel(const float* __restrict
   reinterpret_cast<float4*>(out)[i] = acc;
 }
 
-// 128x384 / 12-wave tiles (the whole N per workgroup) when the tiles fit one round of one workgroup per CU: see launch_nt
-// 160-row tiles (MB = 5) instead of 128-row ones where they save a round of workgroup slots.  The tiled kernel keeps two workgroups per
-// CU, so a launch costs whole rounds of 512 tiles: tools/lab/t_quant.py measures the staircase (fc1 input gradient of ViT-S, N = 384,
-// K = 1536: 1023 tiles 50.8 us, 1035 tiles 63.4 us; Part-fViT N = 768, K = 2048: 2046 tiles 122 us, 2052 tiles 135 us).  A 160-row
-// tile costs ~1.2x a 128-row one (1.25x the MFMAs, 1.125x the staging): taken when rounds(160) x 1.2 < rounds(128).
-// LAFS_OPT_NT_TALL = 0 switches it off (A/B).
-bool tall_tile_shape(const lafs_ctx* cx, int M, int N, int splits) {
-  if (!lafs_ctx_opt(cx, LAFS_OPT_NT_TALL) || splits != 1) return false;
-  const long tn = ceil_div(N, 128);
-  const long r128 = ceil_div((long)ceil_div(M, 128) * tn, 512L), r160 = ceil_div((long)ceil_div(M, 160) * tn, 512L);
-  return 6 * r160 < 5 * r128;
-}
-
-bool wide_tile_shape(const lafs_ctx* cx, int M, int N, int splits) {
-  const int mt = ceil_div(M, 128);
-  return lafs_ctx_opt(cx, LAFS_OPT_NT_WIDE) && splits == 1 && N % 384 == 0 && mt * (N / 384) >= 160 && mt * (N / 384) <= 256;
-}
-
-template <int EPI>
-int launch_nt(const NTArgs& a, int splits, const lafs_ctx* cx, hipStream_t s) {
-  // Shape heuristics from tools/bench_kernels.py on MI355X (ViT-S/B shapes):
-  //  * wide outputs (N >= 1024) on many rows: 256x128 tiles (less L2->LDS traffic per flop, 16 resident waves/CU);
-  //  * long reductions (K >= 640): 64-deep stages (full 128-byte lines per row piece) in a 2-stage ring, 128x128 tiles.
-  const int tn = ceil_div(a.N, 128);
-  const long t2 = (long)ceil_div(a.M, 128) * tn * splits, t4 = (long)ceil_div(a.M, 256) * tn * splits;
-  //  * 256x256 tiles (16 waves, one workgroup per CU, half the operand re-reads of 128x128) win 6-9 % on the isolated ViT-S
-  //    fc1 forward / GELU' dgrad (141 -> 128 us, 138 -> 129 us) but LOSE in the real step (21.3 -> 21.5 ms: a 16-wave
-  //    workgroup owns the CU while the weight-gradient stream wants to share it).
-  if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_ACT || EPI == EPI_F32) {
-    if (a.f16) {                                     // fp16 operands (landmark CNN training plan): 128x128 tiles, no K split
-      const bool bk = (a.klen % 64 == 0) && a.klen >= 640;
-      if (bk) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 2, true>), dim3((unsigned)t2, 1, 1), dim3(256), 0, s, a);
-      else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 32, 2, true>), dim3((unsigned)t2, 1, 1), dim3(256), 0, s, a);
-      LAFS_LAUNCH_CHECK();
-      return LAFS_OK;
-    }
-  }
-  const bool bk64 = (a.klen % 64 == 0) && a.klen >= 640 && (splits == 1 || a.K % 64 == 0);    // K = 704 / 768 (ViT-B) included: 5-15 % over 32-deep stages
-  const int wm = (!bk64 && a.N >= 1024 && a.M >= 4096) ? 4 : 2;
-  //  * persistent tiles (one residency wave of workgroups walking the tiles, the next tile's first ring stages in flight during
-  //    the epilogue) were measured on the C2 shapes: within +-2 % of the one-tile-per-workgroup launch in isolation (fc1 135 vs
-  //    133 us) and 0.2 ms SLOWER per step (18.45 vs 18.23 ms): resident workgroups keep the side streams' kernels off the CUs.
-  // Long reductions onto N = 384 (fc2 forward, fc1 / qkv input gradients of ViT-S): 128x384 tiles, 12 waves -- the whole N per
-  // workgroup, so the A rows are staged once instead of three times and a wave issues 5.3 instead of 8 LDS-DMA instructions per
-  // 32 MFMAs (DESIGN.md section 6: the staging cost is issue time in the wave)
-  // ... when its tiles fit ONE round of one workgroup per CU: 197 tiles (teacher, M = 25216) run 12-17 % faster than on the
-  // 128x128 kernel; 345 tiles (student: a second round of 89) are slower, and so is a split into whole rounds here + the rest on
-  // the 128x128 kernel (fc2 forward 92-98 against 83-86 us).  LAFS_OPT_NT_WIDE = 0 switches it off (A/B).
-  if constexpr (EPI == EPI_BF16 || EPI == EPI_RESID_F32) {
-    const int mt = ceil_div(a.M, 128);
-    if (bk64 && wide_tile_shape(cx, a.M, a.N, splits)) {
-      hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 6>), dim3((unsigned)(mt * (a.N / 384)), 1, 1), dim3(768), 0, s, a);
-      LAFS_LAUNCH_CHECK();
-      return LAFS_OK;
-    }
-  }
-  if constexpr (EPI == EPI_BF16 || EPI == EPI_BF16_GELU || EPI == EPI_RESID_F32 || EPI == EPI_DGELU_BF16) {
-    if (bk64 && wm == 2 && tall_tile_shape(cx, a.M, a.N, splits)) {
-      hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64, 2, false, 5>), dim3((unsigned)(ceil_div(a.M, 160) * tn), 1, 1), dim3(256), 0, s, a);
-      LAFS_LAUNCH_CHECK();
-      return LAFS_OK;
-    }
-  }
-  if (wm == 4) {
-    hipLaunchKernelGGL((gemm_nt_kernel<EPI, 4, 32>), dim3((unsigned)t4 / splits, 1, splits), dim3(512), 0, s, a);
-  } else {
-    if (bk64) hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 64>), dim3((unsigned)t2 / splits, 1, splits), dim3(256), 0, s, a);
-    else hipLaunchKernelGGL((gemm_nt_kernel<EPI, 2, 32>), dim3((unsigned)t2 / splits, 1, splits), dim3(256), 0, s, a);
-  }
-  LAFS_LAUNCH_CHECK();
-  return LAFS_OK;
-}
-
 // length of one K slice when K is split `splits` ways (a multiple of the stage depth; the last slice takes the remainder)
 int ksplit_len(int K, int splits) {
   const int ksteps = K / 32;
@@ -717,16 +643,91 @@ int ksplit_len(int K, int splits) {
   return klen;
 }
 
-}  // namespace
+// The instantiations gemm_nt_kernel<EPI, WM, BK, WN, F16, MB> exists in, in the order launch_nt names them.  Every epilogue has the
+// three plain ones; the others only where nt_has() says so.
+enum NtInst { NT_F16_64, NT_F16_32, NT_WIDE, NT_TALL, NT_256x32, NT_128x64, NT_128x32, NT_INST_COUNT };
+constexpr struct { int wm, bk, wn, f16, mb; } kNtInst[NT_INST_COUNT] = {
+    {2, 64, 2, 1, 4}, {2, 32, 2, 1, 4},                          // fp16 operands (landmark CNN training plan): 128x128 tiles
+    {2, 64, 6, 0, 4}, {2, 64, 2, 0, 5},                          // 128x384 on 12 waves; 160x128
+    {4, 32, 2, 0, 4}, {2, 64, 2, 0, 4}, {2, 32, 2, 0, 4}};       // 256x128; 128x128 on 64- and 32-deep stages
+constexpr bool nt_has(int epi, int inst) {
+  return inst == NT_F16_64 || inst == NT_F16_32 ? (epi == EPI_BF16 || epi == EPI_BF16_ACT || epi == EPI_F32)
+       : inst == NT_WIDE ? (epi == EPI_BF16 || epi == EPI_RESID_F32)
+       : inst == NT_TALL ? (epi == EPI_BF16 || epi == EPI_BF16_GELU || epi == EPI_RESID_F32 || epi == EPI_DGELU_BF16) : true;
+}
 
-extern "C" int lafs_gemm_nt_slices(int K, int splits) { return K >= 32 ? ceil_div(K, ksplit_len(K, splits)) : 1; }
+// The tiled kernel's share of the plan: instantiation, K slices and grid of a validated request the other two kernels left.
+// Shape heuristics from tools/bench_kernels.py on MI355X (ViT-S/B shapes):
+//  * wide outputs (N >= 1024) on many rows: 256x128 tiles (less L2->LDS traffic per flop, 16 resident waves/CU);
+//  * long reductions (K >= 640): 64-deep stages (full 128-byte lines per row piece) in a 2-stage ring, 128x128 tiles.
+//  * 256x256 tiles (16 waves, one workgroup per CU, half the operand re-reads of 128x128) win 6-9 % on the isolated ViT-S
+//    fc1 forward / GELU' dgrad (141 -> 128 us, 138 -> 129 us) but LOSE in the real step (21.3 -> 21.5 ms: a 16-wave
+//    workgroup owns the CU while the weight-gradient stream wants to share it).
+//  * persistent tiles (one residency wave of workgroups walking the tiles, the next tile's first ring stages in flight during
+//    the epilogue) were measured on the C2 shapes: within +-2 % of the one-tile-per-workgroup launch in isolation (fc1 135 vs
+//    133 us) and 0.2 ms SLOWER per step (18.45 vs 18.23 ms): resident workgroups keep the side streams' kernels off the CUs.
+void plan_tiled(const lafs_gemm_nt_args* g, NtPlan* p) {
+  const int e = g->epilogue, M = g->M, N = g->N, K = g->K;
+  const int klen = (e == EPI_ATOMIC_F32 || (e == EPI_F32 && g->splits > 1)) ? ksplit_len(K, g->splits) : K;
+  const int slices = ceil_div(K, klen), tn = ceil_div(N, 128), mt = ceil_div(M, 128);
+  const bool bk64 = (klen % 64 == 0) && klen >= 640 && (slices == 1 || K % 64 == 0);    // K = 704 / 768 (ViT-B) included: 5-15 % over 32-deep stages
+  // Long reductions onto N = 384 (fc2 forward, fc1 / qkv input gradients of ViT-S): 128x384 tiles, 12 waves -- the whole N per
+  // workgroup, so the A rows are staged once instead of three times and a wave issues 5.3 instead of 8 LDS-DMA instructions per
+  // 32 MFMAs (DESIGN.md section 6: the staging cost is issue time in the wave)
+  // ... when its tiles fit ONE round of one workgroup per CU: 197 tiles (teacher, M = 25216) run 12-17 % faster than on the
+  // 128x128 kernel; 345 tiles (student: a second round of 89) are slower, and so is a split into whole rounds here + the rest on
+  // the 128x128 kernel (fc2 forward 92-98 against 83-86 us).  LAFS_OPT_NT_WIDE = 0 switches it off (A/B).
+  const bool wide = lafs_ctx_opt(g->ctx, LAFS_OPT_NT_WIDE) && N % 384 == 0 && mt * (N / 384) >= 160 && mt * (N / 384) <= 256;
+  // 160-row tiles (MB = 5) instead of 128-row ones where they save a round of workgroup slots.  The tiled kernel keeps two workgroups
+  // per CU, so a launch costs whole rounds of 512 tiles: tools/lab/t_quant.py measures the staircase (fc1 input gradient of ViT-S,
+  // N = 384, K = 1536: 1023 tiles 50.8 us, 1035 tiles 63.4 us; Part-fViT N = 768, K = 2048: 2046 tiles 122 us, 2052 tiles 135 us).
+  // A 160-row tile costs ~1.2x a 128-row one (1.25x the MFMAs, 1.125x the staging): taken when rounds(160) x 1.2 < rounds(128).
+  // LAFS_OPT_NT_TALL = 0 switches it off (A/B).
+  const long r128 = ceil_div((long)mt * tn, 512L), r160 = ceil_div((long)ceil_div(M, 160) * tn, 512L);
+  const bool tall = lafs_ctx_opt(g->ctx, LAFS_OPT_NT_TALL) && 6 * r160 < 5 * r128;
+  // (validated: fp16 operands come without a K split; and the epilogues that split have no wide or tall instantiation)
+  const int inst = g->operand_f16 ? (bk64 ? NT_F16_64 : NT_F16_32)
+                 : bk64 && wide && nt_has(e, NT_WIDE) ? NT_WIDE
+                 : bk64 && tall && nt_has(e, NT_TALL) ? NT_TALL
+                 : bk64 ? NT_128x64 : (N >= 1024 && M >= 4096) ? NT_256x32 : NT_128x32;
+  const auto& k = kNtInst[inst];
+  const int tile_m = k.wm * k.mb * 16, tile_n = k.wn * 64;
+  p->inst = inst; p->klen = klen;
+  p->info = {/*route*/ inst == NT_WIDE ? 3 : inst == NT_TALL ? 4 : 0, tile_m, tile_n, /*stage_k*/ k.bk, /*threads*/ k.wm * k.wn * 64, k.f16,
+             slices, ceil_div(M, tile_m) * ceil_div(N, tile_n) * slices};
+}
+
+template <int EPI, int INST>
+int launch_inst(const NTArgs& a, const NtPlan& p, hipStream_t s) {
+  constexpr auto k = kNtInst[INST];
+  const unsigned slices = p.info.k_slices;
+  hipLaunchKernelGGL((gemm_nt_kernel<EPI, k.wm, k.bk, k.wn, k.f16 != 0, k.mb>), dim3(p.info.workgroups / slices, 1, slices), dim3(k.wm * k.wn * 64), 0, s, a);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+// (EPI, planned instantiation) -> launch; `if constexpr` keeps the forms nt_has() denies an epilogue from being instantiated for it
+template <int EPI>
+int launch_nt(const NTArgs& a, const NtPlan& p, hipStream_t s) {
+  switch (p.inst) {
+    case NT_F16_64: if constexpr (nt_has(EPI, NT_F16_64)) return launch_inst<EPI, NT_F16_64>(a, p, s); break;
+    case NT_F16_32: if constexpr (nt_has(EPI, NT_F16_32)) return launch_inst<EPI, NT_F16_32>(a, p, s); break;
+    case NT_WIDE: if constexpr (nt_has(EPI, NT_WIDE)) return launch_inst<EPI, NT_WIDE>(a, p, s); break;
+    case NT_TALL: if constexpr (nt_has(EPI, NT_TALL)) return launch_inst<EPI, NT_TALL>(a, p, s); break;
+    case NT_256x32: return launch_inst<EPI, NT_256x32>(a, p, s);
+    case NT_128x64: return launch_inst<EPI, NT_128x64>(a, p, s);
+    case NT_128x32: return launch_inst<EPI, NT_128x32>(a, p, s);
+  }
+  lafs_set_error("lafs_gemm_nt: epilogue %d has no instantiation %d", EPI, p.inst);
+  return LAFS_EINVAL;
+}
 
 // Every kernel behind lafs_gemm_nt moves its operands in 16-byte pieces (LDS-DMA of A / B, one vector load or store per column
 // group of C / C2 / resid / the GELU' aux): a base address or row stride that breaks that is refused, never launched.  (ATOMIC_F32
 // adds element by element, and the BF16_ACT residual is read element by element: those two only need their element size.)
 // Returns the reason, or nullptr when the request keeps the contract of lafs_hip.h.
-static bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
-static const char* nt_alignment_error(const lafs_gemm_nt_args* g) {
+bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+const char* nt_alignment_error(const lafs_gemm_nt_args* g) {
   if (g->lda % 8 != 0 || g->ldb % 8 != 0) return "lda/ldb must be multiples of 8 elements (16-byte rows)";
   if (!al16(g->A) || !al16(g->B)) return "A and B must be 16-byte aligned";
   if (g->epilogue != LAFS_EPI_ATOMIC_F32 && !al16(g->C)) return "C must be 16-byte aligned";
@@ -737,25 +738,9 @@ static const char* nt_alignment_error(const lafs_gemm_nt_args* g) {
   return nullptr;
 }
 
-extern "C" int lafs_gemm_nt_route(const lafs_gemm_nt_args* g) {
-  if (g == nullptr) return 0;
-  if (nt_alignment_error(g) != nullptr) return LAFS_ESHAPE;   // lafs_gemm_nt refuses it: no kernel runs
-  if (lafs_kres_eligible(g)) return 1;
-  if (lafs_big_eligible(g)) return 5;               // wide long-K shapes: 192x256 tiles, one persistent workgroup per CU (gemm_big.hip)
-  if (g->operand_f16) return 0;                     // fp16 operands (landmark CNN plan): launch_nt takes the 128x128 fp16 kernel first
-  const int splits = (g->epilogue == LAFS_EPI_ATOMIC_F32 || g->epilogue == LAFS_EPI_F32) && g->splits > 1 ? g->splits : 1;
-  // the tiled kernel's 128x384 form (launch_nt): plain / residual epilogue, 64-deep stages (K % 64 == 0, K >= 640), no K split
-  const bool bk64 = g->K % 64 == 0 && g->K >= 640;
-  if ((g->epilogue == LAFS_EPI_BF16 || g->epilogue == LAFS_EPI_RESID_F32) && bk64 && wide_tile_shape(g->ctx, g->M, g->N, splits)) return 3;
-  // ... and its 160-row form where that saves a round of workgroup slots (plain, GELU, residual and GELU' epilogues)
-  if ((g->epilogue == LAFS_EPI_BF16 || g->epilogue == LAFS_EPI_BF16_GELU || g->epilogue == LAFS_EPI_RESID_F32 || g->epilogue == LAFS_EPI_DGELU_BF16) &&
-      bk64 && tall_tile_shape(g->ctx, g->M, g->N, splits))
-    return 4;
-  return 0;
-}
-
-extern "C" int lafs_gemm_nt(const lafs_gemm_nt_args* g, hipStream_t stream) {
-  LAFS_CLEAR_ERROR();
+// The one place a lafs_gemm_nt request is judged: first the whole contract of lafs_hip.h (a refusal sets lafs_last_error and
+// returns a negative code), then which kernel runs it and how.  No device call: lafs_gemm_nt_route / _plan run it without a GPU.
+int plan(const lafs_gemm_nt_args* g, NtPlan* p) {
   LAFS_CHECK_ARG(g != nullptr && g->A && g->B && (g->C || (g->epilogue == LAFS_EPI_BF16_GELU && g->C2)), "null operand");
   LAFS_CHECK_ARG(g->M > 0 && g->N > 0 && g->K > 0, "empty problem");
   LAFS_CHECK_ARG(g->K % 32 == 0, "K must be a multiple of 32");
@@ -763,58 +748,72 @@ extern "C" int lafs_gemm_nt(const lafs_gemm_nt_args* g, hipStream_t stream) {
     lafs_set_error("%s:%d: %s", __FILE__, __LINE__, why);
     return LAFS_ESHAPE;
   }
-  NTArgs a;
-  a.A = (const bf16_t*)g->A; a.B = (const bf16_t*)g->B;
-  a.M = g->M; a.N = g->N; a.K = g->K; a.lda = g->lda; a.ldb = g->ldb;
-  a.C = g->C; a.ldc = g->ldc; a.C2 = g->C2; a.ldc2 = g->ldc2;
-  a.bias = g->bias; a.resid = g->resid; a.ldr = g->ldr;
-  a.seq_scale = g->seq_scale; a.row2seq = g->row2seq;
-  a.aux = (const bf16_t*)g->aux; a.ldaux = g->ldaux; a.pos = g->pos; a.npatch = g->npatch;
-  a.drop = make_drop(g->drop_p, g->drop_seed, g->drop_step, (unsigned)g->drop_row0 * (unsigned)g->N);
-  a.act = g->act;
-  a.f16 = g->operand_f16 ? 1 : 0;
-  LAFS_CHECK_ARG(!a.f16 || ((g->epilogue == LAFS_EPI_BF16 || g->epilogue == LAFS_EPI_BF16_ACT || g->epilogue == LAFS_EPI_F32) && g->splits <= 1),
-                 "fp16 operands: plain / activation / fp32 epilogue, no K split");
+  const int e = g->epilogue;
+  LAFS_CHECK_ARG(!g->operand_f16 || (nt_has(e, NT_F16_32) && g->splits <= 1), "fp16 operands: plain / activation / fp32 epilogue, no K split");
   LAFS_CHECK_ARG(g->drop_p >= 0.f && g->drop_p < 1.f, "drop_p must be in [0, 1)");
   LAFS_CHECK_ARG(!(g->drop_p > 0.f) || ((long)g->M + g->drop_row0) * g->N < 4294967296L, "dropout needs (row0 + M) * N < 2^32");
   LAFS_CHECK_ARG(g->drop_row0 >= 0, "drop_row0 must be >= 0");
-  if (lafs_kres_eligible(g)) return lafs_kres_launch(g, stream);   // K = 384 streaming shapes of the ViT-S trunk (gemm_kres.hip)
-  if (lafs_big_eligible(g)) {                                      // wide long-K shapes of the Part-fViT trunk (gemm_big.hip)
-    LAFS_CHECK_ARG(g->epilogue != LAFS_EPI_RESID_F32 || g->seq_scale == nullptr || g->row2seq != nullptr, "seq_scale needs row2seq");
-    return lafs_big_launch(g, stream);
-  }
-  int splits = 1;
-  a.klen = g->K;
-  if (g->epilogue == LAFS_EPI_ATOMIC_F32 || (g->epilogue == LAFS_EPI_F32 && g->splits > 1)) {
-    LAFS_CHECK_ARG(g->epilogue == LAFS_EPI_ATOMIC_F32 || g->bias == nullptr, "a K-split F32 GEMM takes no bias (it would be added per slice)");
-    a.klen = ksplit_len(g->K, g->splits);
-    splits = ceil_div(g->K, a.klen);
-  }
-  const bool vec_ok = (g->ldc % 8 == 0) || g->C == nullptr;
-  LAFS_CHECK_ARG(vec_ok, "ldc must be a multiple of 8 elements");
-  switch (g->epilogue) {
-    case LAFS_EPI_BF16: return launch_nt<EPI_BF16>(a, 1, g->ctx, stream);
-    case LAFS_EPI_BF16_GELU:
-      LAFS_CHECK_ARG(g->C2 != nullptr && g->ldc2 % 8 == 0, "GELU epilogue needs C2");
-      return launch_nt<EPI_BF16_GELU>(a, 1, g->ctx, stream);
+  LAFS_CHECK_ARG(!(e == LAFS_EPI_F32 && g->splits > 1) || g->bias == nullptr, "a K-split F32 GEMM takes no bias (it would be added per slice)");
+  LAFS_CHECK_ARG(g->ldc % 8 == 0 || g->C == nullptr, "ldc must be a multiple of 8 elements");
+  switch (e) {
+    case LAFS_EPI_BF16: case LAFS_EPI_F32: case LAFS_EPI_ATOMIC_F32: break;
+    case LAFS_EPI_BF16_GELU: LAFS_CHECK_ARG(g->C2 != nullptr && g->ldc2 % 8 == 0, "GELU epilogue needs C2"); break;
     case LAFS_EPI_RESID_F32:
       LAFS_CHECK_ARG(g->resid != nullptr && g->ldr % 4 == 0, "residual epilogue needs resid");
       LAFS_CHECK_ARG(g->seq_scale == nullptr || g->row2seq != nullptr, "seq_scale needs row2seq");
-      return launch_nt<EPI_RESID_F32>(a, 1, g->ctx, stream);
-    case LAFS_EPI_F32: return launch_nt<EPI_F32>(a, splits, g->ctx, stream);
-    case LAFS_EPI_DGELU_BF16:
-      LAFS_CHECK_ARG(g->aux != nullptr, "dGELU epilogue needs aux (pre-activation)");
-      return launch_nt<EPI_DGELU_BF16>(a, 1, g->ctx, stream);
-    case LAFS_EPI_ATOMIC_F32: return launch_nt<EPI_ATOMIC_F32>(a, splits, g->ctx, stream);
-    case LAFS_EPI_BF16_ACT:
-      LAFS_CHECK_ARG(g->act >= 0 && g->act <= LAFS_ACT_HSIGMOID, "unknown activation");
-      return launch_nt<EPI_BF16_ACT>(a, 1, g->ctx, stream);
-    case LAFS_EPI_EMBED_F32:
-      LAFS_CHECK_ARG(g->pos != nullptr && g->npatch > 0 && g->M % g->npatch == 0, "embed epilogue needs pos/npatch");
-      return launch_nt<EPI_EMBED_F32>(a, 1, g->ctx, stream);
-    default:
-      lafs_set_error("lafs_gemm_nt: unknown epilogue %d", g->epilogue);
-      return LAFS_EINVAL;
+      break;
+    case LAFS_EPI_DGELU_BF16: LAFS_CHECK_ARG(g->aux != nullptr, "dGELU epilogue needs aux (pre-activation)"); break;
+    case LAFS_EPI_BF16_ACT: LAFS_CHECK_ARG(g->act >= 0 && g->act <= LAFS_ACT_HSIGMOID, "unknown activation"); break;
+    case LAFS_EPI_EMBED_F32: LAFS_CHECK_ARG(g->pos != nullptr && g->npatch > 0 && g->M % g->npatch == 0, "embed epilogue needs pos/npatch"); break;
+    default: lafs_set_error("lafs_gemm_nt: unknown epilogue %d", e); return LAFS_EINVAL;      // (the one refusal that is not LAFS_ESHAPE)
+  }
+  *p = NtPlan{};
+  if (lafs_kres_eligible(g, p)) return LAFS_OK;            // K = 384 streaming shapes of the ViT-S trunk (gemm_kres.hip)
+  if (lafs_big_eligible(g, p)) return LAFS_OK;             // wide long-K shapes of the Part-fViT trunk (gemm_big.hip)
+  plan_tiled(g, p);
+  return LAFS_OK;
+}
+
+}  // namespace
+
+extern "C" int lafs_gemm_nt_slices(int K, int splits) { return K >= 32 ? ceil_div(K, ksplit_len(K, splits)) : 1; }
+
+extern "C" int lafs_gemm_nt_plan(const lafs_gemm_nt_args* g, lafs_gemm_nt_plan_info* out) {
+  LAFS_CHECK_ARG(out != nullptr, "null plan");
+  NtPlan p;
+  const int rc = plan(g, &p);
+  if (rc == LAFS_OK) *out = p.info;
+  return rc;
+}
+
+extern "C" int lafs_gemm_nt_route(const lafs_gemm_nt_args* g) {
+  NtPlan p;
+  const int rc = plan(g, &p);
+  return rc == LAFS_OK ? p.info.route : rc;
+}
+
+extern "C" int lafs_gemm_nt(const lafs_gemm_nt_args* g, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  NtPlan p;
+  if (const int rc = plan(g, &p)) return rc;
+  if (p.info.route == 1) return lafs_kres_launch(g, p, stream);
+  if (p.info.route == 5) return lafs_big_launch(g, p, stream);
+  NTArgs a;
+  a.A = (const bf16_t*)g->A; a.B = (const bf16_t*)g->B; a.M = g->M; a.N = g->N; a.K = g->K; a.lda = g->lda; a.ldb = g->ldb; a.klen = p.klen;
+  a.C = g->C; a.ldc = g->ldc; a.C2 = g->C2; a.ldc2 = g->ldc2;
+  a.bias = g->bias; a.resid = g->resid; a.ldr = g->ldr; a.seq_scale = g->seq_scale; a.row2seq = g->row2seq;
+  a.aux = (const bf16_t*)g->aux; a.ldaux = g->ldaux; a.pos = g->pos; a.npatch = g->npatch;
+  a.drop = make_drop(g->drop_p, g->drop_seed, g->drop_step, (unsigned)g->drop_row0 * (unsigned)g->N);
+  a.act = g->act; a.f16 = g->operand_f16 ? 1 : 0;
+  switch (g->epilogue) {
+    case LAFS_EPI_BF16: return launch_nt<EPI_BF16>(a, p, stream);
+    case LAFS_EPI_BF16_GELU: return launch_nt<EPI_BF16_GELU>(a, p, stream);
+    case LAFS_EPI_RESID_F32: return launch_nt<EPI_RESID_F32>(a, p, stream);
+    case LAFS_EPI_F32: return launch_nt<EPI_F32>(a, p, stream);
+    case LAFS_EPI_DGELU_BF16: return launch_nt<EPI_DGELU_BF16>(a, p, stream);
+    case LAFS_EPI_ATOMIC_F32: return launch_nt<EPI_ATOMIC_F32>(a, p, stream);
+    case LAFS_EPI_BF16_ACT: return launch_nt<EPI_BF16_ACT>(a, p, stream);
+    default: return launch_nt<EPI_EMBED_F32>(a, p, stream);          // (plan() refused every other value)
   }
 }
 

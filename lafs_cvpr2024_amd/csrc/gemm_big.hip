@@ -29,7 +29,7 @@
 #include <type_traits>
 #include "common.hpp"
 #include "ctx.hpp"
-#include "gemm_big.hpp"
+#include "gemm_plan.hpp"
 
 namespace {
 
@@ -383,10 +383,9 @@ using GeoFive = Geo<5, 8, 2, 2>;           // 160 x 256, one wave per SIMD: 158 
 using GeoSlim = Geo<11, 4, 1, 4>;          // 176 x 256, one wave per SIMD, a wave owns 176 x 64: 251 row tiles of the 44 160-row batches
 
 template <int EPI, bool TWO, typename G>
-int launch(BArgs a, hipStream_t s) {
+int launch(BArgs a, int grid, hipStream_t s) {
   a.tiles_m = ceil_div(a.M, G::BTM); a.tiles_n = ceil_div(a.N, G::BTN);
-  const int tiles = a.tiles_m * a.tiles_n;
-  a.grid = tiles >= 256 ? 256 : tiles;
+  a.grid = grid;
   a.swizzle = (a.grid % 8 == 0) ? 1 : 0;
   hipLaunchKernelGGL((gemm_big_kernel<EPI, TWO, G>), dim3(a.grid), dim3(G::NTH), 0, s, a);
   LAFS_LAUNCH_CHECK();
@@ -412,14 +411,11 @@ inline long fill_permille(int M, int N, int btm, int btn) {
 // round is emptier than ~15 % (M = 25 216, N = 768: 1.55 rounds).  Only the winning combination is routed here by default.
 // geometry of a request: 1 = 192 x 256, 2 = 256 x 256 (two waves per SIMD), 3 = 176 x 256, 4 = 160 x 256.  Unforced, the one-wave-per-SIMD tile
 // whose rounds of one tile per CU are fuller (44 160 x 768: 690 tiles of 192 rows = 2.70 rounds, 753 of 176 rows = 2.94)
-static long geo_fill(const lafs_gemm_nt_args* g, int geo) {
-  return geo == 4 ? fill_permille(g->M, g->N, GeoFive::BTM, GeoFive::BTN) : geo == 3 ? fill_permille(g->M, g->N, GeoSlim::BTM, GeoSlim::BTN)
-       : geo == 2 ? fill_permille(g->M, g->N, GeoTwo::BTM, GeoTwo::BTN) : fill_permille(g->M, g->N, GeoOne::BTM, GeoOne::BTN);
-}
-static long geo_tiles(const lafs_gemm_nt_args* g, int geo) {
-  const int btm = geo == 4 ? GeoFive::BTM : geo == 3 ? GeoSlim::BTM : geo == 2 ? GeoTwo::BTM : GeoOne::BTM;
-  return (long)ceil_div(g->M, btm) * ceil_div(g->N, 256);
-}
+static_assert(GeoOne::BTN == 256 && GeoTwo::BTN == 256 && GeoFive::BTN == 256 && GeoSlim::BTN == 256, "every geometry is 256 columns wide");
+static_assert(GeoOne::NTH == 256 && GeoFive::NTH == 256 && GeoSlim::NTH == 256 && GeoTwo::NTH == 512, "threads per workgroup");
+static int geo_btm(int geo) { return geo == 4 ? GeoFive::BTM : geo == 3 ? GeoSlim::BTM : geo == 2 ? GeoTwo::BTM : GeoOne::BTM; }
+static long geo_fill(const lafs_gemm_nt_args* g, int geo) { return fill_permille(g->M, g->N, geo_btm(geo), 256); }
+static long geo_tiles(const lafs_gemm_nt_args* g, int geo) { return (long)ceil_div(g->M, geo_btm(geo)) * ceil_div(g->N, 256); }
 static int big_geometry(const lafs_gemm_nt_args* g) {
   const int o = lafs_ctx_opt(g->ctx, LAFS_OPT_NT_BIG);
   if (o >= 2) return o <= 5 ? o - 1 : 1;
@@ -428,46 +424,54 @@ static int big_geometry(const lafs_gemm_nt_args* g) {
   if (geo_fill(g, 4) > geo_fill(g, best) + 30) best = 4;
   return best;
 }
+// the plan of a request on geometry `geo`: one workgroup per CU, or per tile where there are fewer (tools/lab/lab_big.cpp runs the
+// kernel through this on shapes lafs_big_eligible would not take)
+static void big_plan(const lafs_gemm_nt_args* g, int geo, NtPlan* p) {
+  const long tiles = geo_tiles(g, geo);
+  p->geo = geo;
+  p->info = {/*route*/ 5, /*tile_m*/ geo_btm(geo), /*tile_n*/ 256, /*stage_k*/ BK, /*threads*/ geo == 2 ? 512 : 256,
+             /*f16*/ 0, /*k_slices*/ 1, /*workgroups*/ (int)(tiles >= 256 ? 256 : tiles)};
+}
 
-bool lafs_big_eligible(const lafs_gemm_nt_args* g) {
-  if (!lafs_ctx_opt(g->ctx, LAFS_OPT_NT_BIG)) return false;
+bool lafs_big_eligible(const lafs_gemm_nt_args* g, NtPlan* p) {
+  const int opt = lafs_ctx_opt(g->ctx, LAFS_OPT_NT_BIG);
+  if (!opt) return false;
   const int e = g->epilogue;
   if (!(e == LAFS_EPI_BF16 || e == LAFS_EPI_BF16_GELU || e == LAFS_EPI_RESID_F32 || e == LAFS_EPI_DGELU_BF16)) return false;
   if (g->splits > 1 || g->operand_f16) return false;
   if (g->K % BK != 0 || g->K < 512 || g->N < 512 || g->N % 8 != 0 || g->M < 8192) return false;
-  if (g->lda % 8 != 0 || g->ldb % 8 != 0 || (g->C != nullptr && g->ldc % 8 != 0)) return false;
-  if (e == LAFS_EPI_BF16_GELU && (g->C2 == nullptr || g->ldc2 % 8 != 0)) return false;
-  if (e == LAFS_EPI_RESID_F32 && (g->resid == nullptr || g->ldr % 4 != 0 || g->C == nullptr)) return false;
-  if (e == LAFS_EPI_DGELU_BF16 && (g->aux == nullptr || g->ldaux % 8 != 0 || g->C == nullptr)) return false;
-  if (e == LAFS_EPI_BF16 && g->C == nullptr) return false;
+  // (the operands' presence, strides and alignment are the contract plan() has checked; this limit is the kernel's own)
   if ((long)g->M * g->lda * 2 >= (1L << 32) || (long)g->N * g->ldb * 2 >= (1L << 32)) return false;     // 32-bit operand offsets
-  if (lafs_ctx_opt(g->ctx, LAFS_OPT_NT_BIG) >= 2) return true;
-  // Which epilogues (same box, tools/lab/t_big_ab.py, us tiled -> here): the plain one; the GELU pair that saves gelu'(u) (VALU-bound:
-  // 283 -> 230 at 44 160 x 2048 x 768, 129 -> 119 at 25 216 rows); GELU' (224 -> 206-212, 111 -> 104); residual + DropPath scale only
-  // from three rounds on (44 160 rows: fc2 forward 209 -> 173, projection 122 -> 96; a tie at 25 216 rows = 2 rounds).  The GELU pair
-  // that writes u, and the forward-only GELU, stay tiled (not measured).  How full: >= 84 % of the rounds' outputs useful; 12-stage
-  // tiles (K = 768) expose the ring's fill and the epilogue at every tile change and need >= 4 rounds, or 3 that are >= 88 % full
-  // (25 216 x 704 x 768 in 2 rounds: 33.5-33.9 us against 31.9 tiled; 25 216 x 2112 x 768 in 5 rounds: 84.7 against 94.0).
   const int geo = big_geometry(g);
-  const long fill = geo_fill(g, geo);
-  const long rounds = (geo_tiles(g, geo) + 255) / 256;
-  const bool epi_ok = e == LAFS_EPI_BF16 || e == LAFS_EPI_DGELU_BF16 || (e == LAFS_EPI_RESID_F32 && rounds >= 3) ||
-                      (e == LAFS_EPI_BF16_GELU && g->C != nullptr && g->act == LAFS_GELU_SAVE_GRAD);
-  return epi_ok && fill >= 840 && (g->K >= 1024 || rounds >= 4 || (rounds >= 3 && fill >= 880));
+  if (opt < 2) {                                            // (a forced geometry takes every shape and epilogue the kernel covers)
+    // Which epilogues (same box, tools/lab/t_big_ab.py, us tiled -> here): the plain one; the GELU pair that saves gelu'(u) (VALU-bound:
+    // 283 -> 230 at 44 160 x 2048 x 768, 129 -> 119 at 25 216 rows); GELU' (224 -> 206-212, 111 -> 104); residual + DropPath scale only
+    // from three rounds on (44 160 rows: fc2 forward 209 -> 173, projection 122 -> 96; a tie at 25 216 rows = 2 rounds).  The GELU pair
+    // that writes u, and the forward-only GELU, stay tiled (not measured).  How full: >= 84 % of the rounds' outputs useful; 12-stage
+    // tiles (K = 768) expose the ring's fill and the epilogue at every tile change and need >= 4 rounds, or 3 that are >= 88 % full
+    // (25 216 x 704 x 768 in 2 rounds: 33.5-33.9 us against 31.9 tiled; 25 216 x 2112 x 768 in 5 rounds: 84.7 against 94.0).
+    const long fill = geo_fill(g, geo);
+    const long rounds = (geo_tiles(g, geo) + 255) / 256;
+    const bool epi_ok = e == LAFS_EPI_BF16 || e == LAFS_EPI_DGELU_BF16 || (e == LAFS_EPI_RESID_F32 && rounds >= 3) ||
+                        (e == LAFS_EPI_BF16_GELU && g->C != nullptr && g->act == LAFS_GELU_SAVE_GRAD);
+    if (!(epi_ok && fill >= 840 && (g->K >= 1024 || rounds >= 4 || (rounds >= 3 && fill >= 880)))) return false;
+  }
+  big_plan(g, geo, p);
+  return true;
 }
 
 template <typename G>
-static int big_launch_geo(const lafs_gemm_nt_args* g, const BArgs& a, hipStream_t stream) {
+static int big_launch_geo(const lafs_gemm_nt_args* g, const BArgs& a, int grid, hipStream_t stream) {
   switch (g->epilogue) {
-    case LAFS_EPI_BF16: return launch<LAFS_EPI_BF16, false, G>(a, stream);
+    case LAFS_EPI_BF16: return launch<LAFS_EPI_BF16, false, G>(a, grid, stream);
     case LAFS_EPI_BF16_GELU:
-      return g->C != nullptr ? launch<LAFS_EPI_BF16_GELU, true, G>(a, stream) : launch<LAFS_EPI_BF16_GELU, false, G>(a, stream);
-    case LAFS_EPI_RESID_F32: return launch<LAFS_EPI_RESID_F32, false, G>(a, stream);
-    default: return launch<LAFS_EPI_DGELU_BF16, false, G>(a, stream);
+      return g->C != nullptr ? launch<LAFS_EPI_BF16_GELU, true, G>(a, grid, stream) : launch<LAFS_EPI_BF16_GELU, false, G>(a, grid, stream);
+    case LAFS_EPI_RESID_F32: return launch<LAFS_EPI_RESID_F32, false, G>(a, grid, stream);
+    default: return launch<LAFS_EPI_DGELU_BF16, false, G>(a, grid, stream);
   }
 }
 
-int lafs_big_launch(const lafs_gemm_nt_args* g, hipStream_t stream) {
+int lafs_big_launch(const lafs_gemm_nt_args* g, const NtPlan& p, hipStream_t stream) {
   BArgs a = {};
   a.A = (const bf16_t*)g->A; a.B = (const bf16_t*)g->B; a.M = g->M; a.N = g->N; a.K = g->K; a.lda = g->lda; a.ldb = g->ldb;
   a.C = g->C; a.ldc = g->ldc; a.C2 = g->C2; a.ldc2 = g->ldc2;
@@ -475,7 +479,7 @@ int lafs_big_launch(const lafs_gemm_nt_args* g, hipStream_t stream) {
   a.aux = (const bf16_t*)g->aux; a.ldaux = g->ldaux;
   a.drop = make_drop(g->drop_p, g->drop_seed, g->drop_step, (unsigned)g->drop_row0 * (unsigned)g->N);
   a.act = g->act;
-  const int geo = big_geometry(g);
-  return geo == 2 ? big_launch_geo<GeoTwo>(g, a, stream) : geo == 3 ? big_launch_geo<GeoSlim>(g, a, stream)
-       : geo == 4 ? big_launch_geo<GeoFive>(g, a, stream) : big_launch_geo<GeoOne>(g, a, stream);
+  const int grid = p.info.workgroups;
+  return p.geo == 2 ? big_launch_geo<GeoTwo>(g, a, grid, stream) : p.geo == 3 ? big_launch_geo<GeoSlim>(g, a, grid, stream)
+       : p.geo == 4 ? big_launch_geo<GeoFive>(g, a, grid, stream) : big_launch_geo<GeoOne>(g, a, grid, stream);
 }

@@ -27,7 +27,7 @@
 //     epilogue's memory operations are a compile-time count per item).
 #include <stdlib.h>
 #include "common.hpp"
-#include "gemm_kres.hpp"
+#include "gemm_plan.hpp"
 #include "ctx.hpp"
 
 namespace {
@@ -365,7 +365,7 @@ int launch(const KArgs& a, int grid, hipStream_t s) {
 
 }  // namespace
 
-bool lafs_kres_eligible(const lafs_gemm_nt_args* g) {
+bool lafs_kres_eligible(const lafs_gemm_nt_args* g, NtPlan* p) {
   // LAFS_OPT_KRES_MASK = bit mask of the epilogues routed here (1 plain, 2 GELU, 4 residual, 8 GELU'); 0 = tiled kernel everywhere.
   // Default 15 (whole step, one box, tools/lab/ab_env.sh: 16.95 ms against 17.22 with mask 7 and 17.57 with 0).
   const int mask = lafs_ctx_opt(g->ctx, LAFS_OPT_KRES_MASK);
@@ -374,17 +374,24 @@ bool lafs_kres_eligible(const lafs_gemm_nt_args* g) {
   if (!(mask & bit)) return false;
   if (g->splits > 1 || g->operand_f16) return false;
   if (g->K != KK || g->N % 64 != 0 || g->N > MAXN || g->N < 64 || g->M < 2048) return false;
-  if (!(e == LAFS_EPI_BF16 || e == LAFS_EPI_BF16_GELU || e == LAFS_EPI_RESID_F32 || e == LAFS_EPI_DGELU_BF16)) return false;
   if (g->drop_p > 0.f) return false;
-  if (g->lda % 8 != 0 || g->ldb % 8 != 0 || g->ldc % 8 != 0) return false;
-  if (e == LAFS_EPI_BF16_GELU && (g->C2 == nullptr || g->ldc2 % 8 != 0)) return false;
-  if (e == LAFS_EPI_RESID_F32 && (g->resid == nullptr || g->ldr % 4 != 0)) return false;
-  if (e == LAFS_EPI_DGELU_BF16 && (g->aux == nullptr || g->ldaux % 8 != 0)) return false;
-  if (e != LAFS_EPI_BF16_GELU && g->C == nullptr) return false;
+  // (the operands' presence, strides and alignment are the contract plan() has checked -- all but the stride of an absent C, which
+  // the contract leaves free: a GELU request without u keeps the kernel it always had)
+  if (g->C == nullptr && g->ldc % 8 != 0) return false;
+  // two 4-wave workgroups per CU: one residency wave of equal item runs (at least ~4 items each, or the reload of the
+  // resident operand per run stops being amortised)
+  const int items = ((g->M + 127) / 128) * (g->N / 64);
+  const int min_items = lafs_ctx_opt(g->ctx, LAFS_OPT_KRES_MIN_ITEMS);      // lab knob
+  const int g_comm_cus = lafs_ctx_opt(g->ctx, LAFS_OPT_COMM_CUS);
+  int grid = 512;
+  while (grid > 8 && items / grid < min_items) grid >>= 1;
+  if (g_comm_cus > 0 && grid > 2 * (256 - g_comm_cus)) grid = (2 * (256 - g_comm_cus)) & ~7;     // CUs left to RCCL (LAFS_OPT_COMM_CUS)
+  // an item is 128 rows x 64 columns; a ring stage holds 32 weight rows over the whole K
+  p->info = {/*route*/ 1, /*tile_m*/ 128, /*tile_n*/ 64, /*stage_k*/ KK, /*threads*/ NTH, /*f16*/ 0, /*k_slices*/ 1, /*workgroups*/ grid};
   return true;
 }
 
-int lafs_kres_launch(const lafs_gemm_nt_args* g, hipStream_t stream) {
+int lafs_kres_launch(const lafs_gemm_nt_args* g, const NtPlan& p, hipStream_t stream) {
   const int e = g->epilogue;
   KArgs a;
   a.A = (const bf16_t*)g->A; a.B = (const bf16_t*)g->B; a.M = g->M; a.N = g->N; a.lda = g->lda; a.ldb = g->ldb;
@@ -394,16 +401,8 @@ int lafs_kres_launch(const lafs_gemm_nt_args* g, hipStream_t stream) {
   a.aux = (const bf16_t*)g->aux; a.ldaux = g->ldaux;
   a.cbn = g->N / 64;
   a.save_grad = (g->act == LAFS_GELU_SAVE_GRAD && (e == LAFS_EPI_BF16_GELU || e == LAFS_EPI_DGELU_BF16)) ? 1 : 0;
-
-  const int mus = (g->M + 127) / 128;
-  a.items = mus * a.cbn;
-  // two 4-wave workgroups per CU: one residency wave of equal item runs (at least ~4 items each, or the reload of the
-  // resident operand per run stops being amortised)
-  const int min_items = lafs_ctx_opt(g->ctx, LAFS_OPT_KRES_MIN_ITEMS);      // lab knob
-  const int g_comm_cus = lafs_ctx_opt(g->ctx, LAFS_OPT_COMM_CUS);
-  int grid = 512;
-  while (grid > 8 && a.items / grid < min_items) grid >>= 1;
-  if (g_comm_cus > 0 && grid > 2 * (256 - g_comm_cus)) grid = (2 * (256 - g_comm_cus)) & ~7;     // CUs left to RCCL (LAFS_OPT_COMM_CUS)
+  a.items = ((g->M + 127) / 128) * a.cbn;
+  const int grid = p.info.workgroups;
   switch (e) {
     case LAFS_EPI_BF16: return launch<LAFS_EPI_BF16, true>(a, grid, stream);
     case LAFS_EPI_BF16_GELU:

@@ -136,7 +136,7 @@ def _nt_grid():
     add("wm4-gelu_u<4,32>", EPI_BF16_GELU, 4097, 1024, 64, route=0)
     add("wm4-ksplit-f32-K96x2<4,32>", EPI_F32, 4100, 1028, 96, splits=2, route=0)
     add("wm4-atomic-splits3<4,32>", EPI_ATOMIC_F32, 4100, 1024, 96, splits=3, route=0)
-    # ... and on both sides of its thresholds (the route is 0 on either side: only the values can tell)
+    # ... and on both sides of its thresholds (the route is 0 on either side: the values tell, and test_host_logic.py reads the plan)
     add("wm4-threshold-M4096-N1024<4,32>", EPI_BF16, 4096, 1024, 96, route=0)
     add("wm4-threshold-M4095-N1024<2,32>", EPI_BF16, 4095, 1024, 96, route=0)
     add("wm4-threshold-M4096-N1016<2,32>", EPI_BF16, 4096, 1016, 96, route=0)

@@ -193,7 +193,7 @@ def test_gemm_route_selection_on_the_benchmark_shapes():
 
     B16, GELU, RES, DG = _lib.EPI_BF16, _lib.EPI_BF16_GELU, _lib.EPI_RESID_F32, _lib.EPI_DGELU_BF16
     # ViT-S step (C2): two row chains of 25 216 / 18 944 rows
-    assert route(25216, 1152, 384, B16) in (1, 2) and route(18944, 1536, 384, GELU) in (1, 2)        # K = 384: K-resident
+    assert route(25216, 1152, 384, B16) == 1 and route(18944, 1536, 384, GELU) == 1                  # K = 384: K-resident
     assert route(25216, 384, 1536, RES) == 3 and route(25216, 384, 1152, B16) == 3                    # 197 wide tiles: one round
     assert route(18944, 384, 1536, RES) == 0 and route(18944, 384, 1536, B16) == 0                    # 444 tiles: one round of 128x128
     assert route(44160, 384, 1536, B16) == 4                                                          # merged rows: 1035 -> 828 tiles
@@ -211,3 +211,211 @@ def test_gemm_route_selection_on_the_benchmark_shapes():
     assert route(44160, 2048, 768, GELU, act=1) == 5 and route(25216, 2048, 768, GELU, act=1) == 5 and route(44160, 2048, 768, GELU) != 5
     assert route(18944, 768, 2048, B16) == 0                                                          # 888 tiles: 2 rounds either way
     assert route(1024, 768, 2048, B16) == 0
+
+
+# ------------------------------------------------------------------------------------------------ lafs_gemm_nt's plan (host logic)
+def _plan_lib():
+    import os
+    from lafs_cvpr2024_amd import _lib
+    if not os.path.isfile(_lib.LIB_PATH):                   # pragma: no cover
+        pytest.skip("library not built")
+    return _lib, _lib.lib()                                 # (a library that is there but does not load is a failure, not a skip)
+
+
+def _fake(off_bytes=0):
+    return (1 << 20) + off_bytes                            # (never dereferenced: the plan reads shapes, strides, presence and alignment)
+
+
+def _nt_args(_lib, M, N, K, epi, **kw):
+    """A complete, contract-keeping request on fake 16-byte aligned pointers; kw overrides any field."""
+    a = _lib.GemmNTArgs()
+    a.M, a.N, a.K, a.epilogue, a.splits = M, N, K, epi, 1
+    a.lda, a.ldb, a.ldc, a.ldc2, a.ldr, a.ldaux = K, K, N, N, N, N
+    a.A = a.B = a.C = _fake()
+    if epi == _lib.EPI_BF16_GELU:
+        a.C2 = _fake()
+    if epi == _lib.EPI_RESID_F32:
+        a.resid = _fake()
+    if epi == _lib.EPI_DGELU_BF16:
+        a.aux = _fake()
+    if epi == _lib.EPI_EMBED_F32:
+        a.pos, a.npatch = _fake(), 1
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def _plan(_lib, h, a):
+    """(status, plan, route query) of one request."""
+    import ctypes as C
+    info = _lib.GemmNTPlanInfo()
+    return int(h.lafs_gemm_nt_plan(C.byref(a), C.byref(info))), info, int(h.lafs_gemm_nt_route(C.byref(a)))
+
+
+def _case_args(_lib, c, ctx):
+    """The request tests/test_gpu_gemm.py builds for case c: column slices of wider buffers (gemm_cases.inp / Out), so every row
+    stride exceeds the logical width and the bases sit 16 or 32 bytes into an aligned row."""
+    import gemm_cases as gc
+    M, N, K, epi = c["M"], c["N"], c["K"], c["epi"]
+    ld = lambda off, w, pad: (off + w + pad + 7) // 8 * 8
+    a = _lib.GemmNTArgs()
+    a.M, a.N, a.K, a.epilogue, a.splits, a.act = M, N, K, epi, c["splits"], 1 if c["form"] == "save" else c["act"]
+    a.A, a.B, a.lda, a.ldb = _fake(16), _fake(16), ld(8, K, 8), ld(8, K, 8)
+    a.C, a.ldc = _fake(32 if epi in gc.F32_EPIS else 16), ld(8, N, 8)
+    a.operand_f16 = 1 if c["half"] else 0
+    if c["bias"]:
+        a.bias = _fake()
+    if c["drop_p"] > 0:
+        a.drop_p, a.drop_seed, a.drop_row0 = c["drop_p"], 1, c["drop_row0"]
+        a.drop_step = None if c["drop_step"] is None else _fake()
+    if epi == gc.EPI_DGELU_BF16 or (epi == gc.EPI_BF16_ACT and c["aux"]):
+        a.aux, a.ldaux = _fake(16), ld(8, N, 16)
+    if epi == gc.EPI_RESID_F32:
+        a.resid, a.ldr = (a.C, a.ldc) if c["alias"] else (_fake(16), ld(4, N, 4))
+        if c["scale"] is not None:
+            a.seq_scale, a.row2seq = _fake(), _fake()
+    if epi == gc.EPI_EMBED_F32:
+        a.pos, a.npatch = _fake(), c["npatch"]
+    if epi == gc.EPI_BF16_GELU:
+        a.C2, a.ldc2 = _fake(32), ld(16, N, 8)
+        if c["form"] == "noC":
+            a.C = None
+    a.ctx = ctx
+    return a
+
+
+class _Contexts:
+    """lafs_ctx handles by option set.  lafs_ctx_create needs a device: without one every non-default option set is None."""
+
+    def __init__(self, h):
+        self.h, self.made = h, {}
+
+    def get(self, opts):
+        key = tuple(sorted(opts.items()))
+        if key not in self.made:
+            ctx = self.h.lafs_ctx_create(0) if torch.cuda.is_available() else None
+            for k, v in (opts.items() if ctx else ()):
+                assert self.h.lafs_ctx_set(ctx, k, v) == 0
+            self.made[key] = ctx
+        return self.made[key]
+
+    def close(self):
+        for ctx in self.made.values():
+            if ctx:
+                self.h.lafs_ctx_destroy(ctx)
+
+
+def test_gemm_plan_runs_the_route_and_instantiation_every_grid_case_names():
+    """tests/test_gpu_gemm.py holds `every route and instantiation` to fp64: here the plan lafs_gemm_nt itself runs (lafs_gemm_nt_plan)
+    is held to what each case id says it is meant for -- the route, and where the id ends in <WM,BK[,WN[,F16[,MB]]]> (defaults WN 2,
+    F16 false, MB 4) the tile (WM*MB*16 x WN*64), the stage depth BK, the WM*WN*64 threads and the fp16 flag; a forced gemm_big
+    geometry by its tile rows.  Cases with LAFS_OPT_* values need a context, which needs a device: without one they are passed over,
+    30 of the grid's cases at the most (those whose `opts` is set) -- never a case on default options."""
+    import re
+    import gemm_cases as gc
+    _lib, h = _plan_lib()
+    ctxs = _Contexts(h)
+    n_opts = sum(c["opts"] is not None for c in gc.NT_CASES)
+    assert n_opts == 30
+    passed_over, tagged = 0, 0
+    try:
+        for c in gc.NT_CASES:
+            ctx = None
+            if c["opts"] is not None:
+                ctx = ctxs.get(c["opts"])
+                if ctx is None:
+                    passed_over += 1
+                    continue
+            rc, p, route = _plan(_lib, h, _case_args(_lib, c, ctx))
+            assert rc == 0, (c["id"], rc, h.lafs_last_error())
+            assert c["route"] is not None and p.route == route == c["route"], (c["id"], p.route, route)
+            assert p.workgroups > 0 and p.workgroups % p.k_slices == 0, c["id"]
+            assert p.k_slices == (len(gc.nt_slices(c["K"], c["splits"])) if c["epi"] in (gc.EPI_F32, gc.EPI_ATOMIC_F32) else 1), c["id"]
+            tag = re.search(r"<([^>]*)>$", c["id"])
+            if tag:
+                assert c["route"] in (0, 3, 4), c["id"]         # (the tags name instantiations of the tiled kernel)
+                t = tag.group(1).split(",") + ["2", "false", "4"][len(tag.group(1).split(",")) - 2:]
+                wm, bk, wn, f16, mb = int(t[0]), int(t[1]), int(t[2]), t[3] == "true", int(t[4])
+                got = (p.tile_m, p.tile_n, p.stage_k, p.threads, bool(p.f16))
+                assert got == (wm * mb * 16, wn * 64, bk, wm * wn * 64, f16), (c["id"], got)
+                tagged += 1
+            forced = re.search(r"NT_BIG([2-5])", c["id"])
+            if forced:
+                assert (p.tile_m, p.tile_n) == ({2: 192, 3: 256, 4: 176, 5: 160}[int(forced.group(1))], 256), (c["id"], p.tile_m)
+    finally:
+        ctxs.close()
+    assert passed_over <= n_opts and (passed_over == 0 or not torch.cuda.is_available())
+    assert tagged >= 235                                    # (every tagged case on default options; 249 with a device)
+
+
+def test_gemm_route_and_plan_refuse_what_lafs_gemm_nt_refuses():
+    """Both queries run lafs_gemm_nt's own validation: every refusal gives the same negative code from both and sets lafs_last_error.
+    The third request is the one the K-resident path used to launch (seq_scale read through a NULL row2seq): it is tested only here."""
+    _lib, h = _plan_lib()
+    F32, RES, GELU, B16 = _lib.EPI_F32, _lib.EPI_RESID_F32, _lib.EPI_BF16_GELU, _lib.EPI_BF16
+    no_r2s = dict(seq_scale=_fake(), row2seq=None)
+    cases = [
+        ("K must be a multiple of 32", _nt_args(_lib, 128, 128, 48, B16)),
+        ("null operand", _nt_args(_lib, 128, 128, 64, B16, A=None)),
+        ("seq_scale needs row2seq", _nt_args(_lib, 2100, 192, 384, RES, **no_r2s)),              # K-resident shape
+        ("seq_scale needs row2seq", _nt_args(_lib, 44160, 768, 2048, RES, **no_r2s)),            # gemm_big shape
+        ("seq_scale needs row2seq", _nt_args(_lib, 257, 136, 96, RES, **no_r2s)),                # tiled shape
+        ("GELU epilogue needs C2", _nt_args(_lib, 128, 128, 64, GELU, C2=None)),
+        ("takes no bias", _nt_args(_lib, 128, 128, 128, F32, splits=2, bias=_fake())),
+        ("fp16 operands", _nt_args(_lib, 128, 128, 64, RES, operand_f16=1)),
+        ("drop_p must be in", _nt_args(_lib, 128, 128, 64, RES, drop_p=1.0)),
+        ("ldc must be a multiple of 8", _nt_args(_lib, 128, 120, 64, B16, ldc=124)),
+    ]
+    import ctypes as C
+    empty = _nt_args(_lib, 0, 128, 64, B16)
+    for why, a in cases:
+        # (the queries leave the text of an earlier refusal standing on success: a different refusal in front of each query, so that
+        # the text read after it can only be its own)
+        for query in (lambda r: h.lafs_gemm_nt_route(C.byref(r)), lambda r: h.lafs_gemm_nt_plan(C.byref(r), C.byref(_lib.GemmNTPlanInfo()))):
+            assert query(empty) < 0 and "empty problem" in h.lafs_last_error().decode()
+            rc = int(query(a))
+            text = h.lafs_last_error().decode()
+            assert rc == -2 and why in text and "empty problem" not in text, (why, rc, text)
+    # the same shapes with row2seq are routed: the refusals above are about the missing operand, not the shapes
+    with_r2s = dict(seq_scale=_fake(), row2seq=_fake())
+    assert [_plan(_lib, h, _nt_args(_lib, M, N, K, RES, **with_r2s))[2] for M, N, K in ((2100, 192, 384), (44160, 768, 2048), (257, 136, 96))] == [1, 5, 0]
+    # an unknown epilogue keeps its own code and text
+    rc, _, route = _plan(_lib, h, _nt_args(_lib, 128, 128, 64, 11))
+    assert rc == route == -1 and "unknown epilogue 11" in h.lafs_last_error().decode()
+
+
+def test_gemm_route_equals_the_plans_route_on_random_requests():
+    """lafs_gemm_nt_route has no logic of its own: on seeded random requests -- valid and broken, every epilogue, K splits, fp16, and
+    option sets where a context can be made -- it returns the plan's route, or the plan's negative code."""
+    import random
+    _lib, h = _plan_lib()
+    rnd = random.Random(20240611)
+    ctxs = _Contexts(h)
+    opt_sets = [{}, {_lib.OPT_KRES_MASK: 0}, {_lib.OPT_NT_WIDE: 0}, {_lib.OPT_NT_TALL: 0}, {_lib.OPT_NT_BIG: 0}, {_lib.OPT_NT_BIG: 3}, {_lib.OPT_NT_BIG: 5}]
+    seen, refused = set(), 0
+    try:
+        for _ in range(600):
+            M = rnd.choice([rnd.randint(1, 300), rnd.randint(1, 9000), rnd.choice([2048, 4096, 8192, 16400, 18944, 20500, 25216, 26048, 44160])])
+            N = rnd.choice([rnd.randint(1, 2200), rnd.choice([64, 192, 384, 384, 384, 500, 512, 768, 1016, 1024, 1152, 1536, 2048, 2112])])
+            K = rnd.choice([32 * rnd.randint(1, 70)] * 5 + [rnd.choice([96, 384, 512, 640, 704, 768, 1024, 1344, 1536, 2048])] * 10 + [48])
+            epi = rnd.choice(list(range(8)) * 4 + [9])
+            a = _nt_args(_lib, M, N, K, epi, ldc=(N + 7) // 8 * 8, ldc2=(N + 7) // 8 * 8, ldr=(N + 3) // 4 * 4, ldaux=(N + 7) // 8 * 8)
+            a.splits = rnd.choice([1, 1, 2, 3, 1000]) if epi in (_lib.EPI_F32, _lib.EPI_ATOMIC_F32) else rnd.choice([1] * 9 + [2])
+            a.operand_f16 = int(rnd.random() < 0.1)
+            a.act = rnd.randint(0, 1) if epi in (_lib.EPI_BF16_GELU, _lib.EPI_DGELU_BF16) else rnd.randint(0, 4)
+            a.drop_p = rnd.choice([0.0] * 8 + [0.1, 1.0])
+            a.bias = rnd.choice([None, _fake()])
+            if epi == _lib.EPI_RESID_F32:
+                a.seq_scale, a.row2seq = rnd.choice([(None, None), (_fake(), _fake()), (_fake(), None)])
+            if epi == _lib.EPI_BF16_GELU and rnd.random() < 0.3:
+                a.C = None
+            if rnd.random() < 0.1:                          # break one more thing
+                setattr(a, *rnd.choice([("A", None), ("B", _fake(4)), ("lda", K + 4), ("C", _fake(8)), ("ldc", 124), ("drop_row0", -1), ("M", 0)]))
+            a.ctx = ctxs.get(rnd.choice(opt_sets))
+            rc, p, route = _plan(_lib, h, a)
+            assert rc <= 0 and route == (p.route if rc == 0 else rc), (M, N, K, epi, rc, route, p.route)
+            seen.add(route if rc == 0 else "refused")
+            refused += rc < 0
+    finally:
+        ctxs.close()
+    assert {0, 1, 3, 4, 5, "refused"} <= seen and 60 <= refused <= 300, (seen, refused)

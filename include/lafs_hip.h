@@ -285,7 +285,7 @@ int lafs_colsum_bf16_acc(const void* X, int ldx, int M, int N, float* out, hipSt
  * LayerNorm  (vision_transformer.py:99,103,156 eps 1e-6; face_pre_pro/ViT_face.py:117 eps 1e-5)
  * ------------------------------------------------------------------------------------------------ */
 /* y(bf16)[r,:] = (x(f32)[r,:] - mean) * rstd * gamma + beta ; stats(f32)[r] = {mean, rstd}.
- * y_f32 (optional, may be NULL) receives the same result in fp32.  D % 4 == 0, D <= 2048. */
+ * y_f32 (optional, may be NULL) receives the same result in fp32.  D % 4 == 0, D <= 2048; ldx, ldy, ldyf multiples of 4. */
 int lafs_layernorm_fwd(const float* x, int ldx, const float* gamma, const float* beta, float eps,
                        void* y_bf16, int ldy, float* y_f32, int ldyf, float* stats, int rows, int D,
                        hipStream_t stream);
@@ -293,7 +293,9 @@ int lafs_layernorm_fwd(const float* x, int ldx, const float* gamma, const float*
  *   dx = LN'(dy);  g_io(f32)[r,:] = (accumulate ? g_io : 0) + dx
  *   dgamma(f32)[D] += sum_r dy*xhat ; dbeta(f32)[D] += sum_r dy
  *   gb_out(bf16, optional)[r,:] = bf16(seq_scale[row2seq[r]] * g_io[r,:])  -- the DropPath-scaled gradient fed to
- *   the previous residual branch's GEMMs (seq_scale NULL -> scale 1). */
+ *   the previous residual branch's GEMMs (seq_scale NULL -> scale 1).
+ * Row strides of the operands in use -- ldx, ldg, lddyf (with dy_f32) or lddy (without), ldgb (with gb_out) -- must be multiples
+ * of 4, as for the forward (vector loads and stores); anything else is refused (LAFS_ESHAPE). */
 int lafs_layernorm_bwd(const void* dy_bf16, int lddy, const float* dy_f32, int lddyf, const float* x, int ldx,
                        const float* stats, const float* gamma, float* g_io, int ldg, int accumulate,
                        void* gb_out, int ldgb, const float* seq_scale, const int32_t* row2seq,
@@ -311,7 +313,7 @@ typedef struct lafs_ln_fold_item {
 int lafs_layernorm_bwd_parts(int rows, int D);
 int lafs_layernorm_bwd_fold(const lafs_ln_fold_item* items, int n_items, int D, hipStream_t stream);
 
-/* gb(bf16)[r,:] = bf16(seq_scale[row2seq[r]] * g(f32)[r,:])  (seq_scale NULL -> plain cast). */
+/* gb(bf16)[r,:] = bf16(seq_scale[row2seq[r]] * g(f32)[r,:])  (seq_scale NULL -> plain cast).  D, ldg and ldgb must be multiples of 4. */
 int lafs_scale_cast_bf16(const float* g, int ldg, void* gb, int ldgb, const float* seq_scale,
                          const int32_t* row2seq, int rows, int D,
                          float drop_p, uint32_t drop_seed, const float* drop_step, int drop_row0, hipStream_t stream);

@@ -500,6 +500,9 @@ extern "C" int lafs_layernorm_bwd(const void* dy_bf16, int lddy, const float* dy
   LAFS_CHECK_ARG((dy_bf16 || dy_f32) && x && stats && gamma && g_io && ((dgamma && dbeta) || part_out), "null operand");
   LAFS_CHECK_ARG(rows > 0 && D > 0 && D % 4 == 0 && D <= 256 * MAXI, "D must be a multiple of 4 and <= 2048");
   LAFS_CHECK_ARG(seq_scale == nullptr || row2seq != nullptr, "seq_scale needs row2seq");
+  // (x, g_io and dy_f32 are read as float4, dy as uint2, gb_out is written as uint2: the strides of the operands in use)
+  LAFS_CHECK_ARG(ldx % 4 == 0 && ldg % 4 == 0 && (dy_f32 ? lddyf % 4 == 0 : lddy % 4 == 0) && (gb_out == nullptr || ldgb % 4 == 0),
+                 "row strides must be multiples of 4");
   const int ni = ceil_div(D, 256);
   const dim3 grid(lafs_layernorm_bwd_parts(rows, D));
   if (dy_f32 == nullptr && D % 128 == 0 && D <= 512 && rows >= 4096) {      // two rows per wave (see ln_bwd2_kernel); same grid, same slots
@@ -536,6 +539,7 @@ extern "C" int lafs_scale_cast_bf16(const float* g, int ldg, void* gb, int ldgb,
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(g && gb && rows > 0 && D > 0 && D % 4 == 0, "bad operand");
   LAFS_CHECK_ARG(seq_scale == nullptr || row2seq != nullptr, "seq_scale needs row2seq");
+  LAFS_CHECK_ARG(ldg % 4 == 0 && ldgb % 4 == 0, "row strides must be multiples of 4");
   const size_t total = (size_t)rows * (D / 4);
   int blocks = (int)((total + 255) / 256);
   if (blocks > 4096) blocks = 4096;

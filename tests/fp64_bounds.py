@@ -1,12 +1,14 @@
-"""The fp64 oracle of the kernel tests: plain fp64 restatements of the GEMM family's operations that carry, next to every value, a
+"""The fp64 oracle of the kernel tests: plain fp64 restatements of the GEMM family's, the LayerNorm family's and the arena step's
+operations that carry, next to every value, a
 bound on how far the kernel's value may lie from it, element by element (never normalised by a tensor's maximum).
 
 The reference rounds to 16 bits exactly where include/lafs_hip.h says the kernel stores 16 bits, and nowhere else.  Where the kernel
 stores a 16-bit value the bound is the distance to the neighbouring 16-bit values its unrounded value can reach (`flip`): 0 where no
 rounding boundary lies within reach, so most 16-bit outputs must match the reference exactly.
 
-Shared by tests/test_gpu_mlp_fused.py, tests/test_gpu_gemm.py, tests/test_gpu_wgrad.py and tests/test_oracle_gemm_host.py (which shows
-on the CPU that the bounds are tight enough to mean something and that seeded faults fail them).  Everything here runs on whatever
+Shared by tests/test_gpu_mlp_fused.py, tests/test_gpu_gemm.py, tests/test_gpu_wgrad.py, tests/test_gpu_layernorm.py, tests/test_gpu_optim.py
+and the two CPU modules tests/test_oracle_gemm_host.py and tests/test_oracle_rowops_host.py (which show that the bounds are tight
+enough to mean something and that seeded faults fail them).  Everything here runs on whatever
 device its arguments live on.  The case grids, input distributions and guarded buffers of the GEMM modules are in tests/gemm_cases.py."""
 import math
 
@@ -191,6 +193,198 @@ def nt_reference(epi, A, B, bias=None, res=None, s=None, drop=None, aux=None, po
             z, ze = z + aux, ze + U * (z + aux).abs()
         return {"C": flip(*act(z, ze, act_kind), r16) + (True,)}
     raise ValueError(epi)
+
+
+# ------------------------------------------------------------------------------------------------ row operations (LayerNorm)
+# rsqrtf: no accuracy table of the device library ships with the toolchain, so the allowance is a measurement --
+# tests/test_gpu_layernorm.py::test_rsqrtf_allowance feeds lafs_layernorm_fwd rows (-a, -a, a, a) with 11-bit a (mean 0, variance a^2
+# and the fp32 sum a^2 + eps all exact up to the one rounding the reference repeats) and compares rstd with the fp64 value: the worst
+# of 40 000 arguments over [1e-6, 1e6] was 0.82 ulp on the MI355X.  Allowed here: 2 ulp = 4 u relative.
+RSQ_REL = 4 * U
+# powf: 1 ulp (the figure of HIP's published math-API table) = 2 u relative; cannot be measured apart from the kernel
+POW_REL = 2 * U
+
+
+def f32c(v):
+    """The fp32 value of a Python constant, widened: the operand a kernel holds for a literal or a float argument."""
+    return float(torch.tensor(v, dtype=f32))
+
+
+def sum_depth(D):
+    """Most fp32 additions a term of a LayerNorm row sum passes through: a lane adds its <= 32 values (4 per 256-column chunk, or per
+    128-column chunk in the two-rows-per-wave kernels) in sequence, a butterfly over <= 64 lanes follows.  A sum of D terms of any
+    sign is then off by at most depth u sum|terms|."""
+    return min(32, 4 * -(-D // 128)) + 6
+
+
+def rsqrt_iv(v, ve):
+    """rsqrtf of a positive value known to within ve: the fp64 value and the widest distance to what the interval's ends give
+    (exact, not first order: infinite where the interval reaches 0), plus the RSQ_REL allowance of the instruction."""
+    r = v.rsqrt()
+    re = torch.maximum((v - ve).clamp_min(0).rsqrt() - r, r - (v + ve).rsqrt())
+    return r, re + RSQ_REL * (r + re)
+
+
+def ln_fwd(x, gamma, beta, eps):
+    """lafs_layernorm_fwd on exact fp32 rows x [R, D] (eps: the fp32 value): {"y": fp32 output, "y16": its bf16 store, "mean",
+    "rstd"}, each (reference, bound).
+    mean:  a sum of D terms of depth sum_depth(D), one division
+    var:   two-pass -- sum (x - mean')^2 = sum (x - mean)^2 + D dm^2 for the kernel's mean' = mean + dm, so the mean's error enters
+           squared; every term rounds three times (difference, square, product / fma) before the sum of depth sum_depth; / D; + eps
+    rstd:  rsqrt_iv
+    y:     (x - mean') rstd' gamma + beta: the difference and the product round, the last product and sum round once each (or once
+           together as an fma)"""
+    D = x.shape[1]
+    dep = sum_depth(D)
+    m = x.mean(1, keepdim=True)
+    me = dep * U * x.abs().mean(1, keepdim=True) + U * m.abs()
+    c = x - m
+    var = (c * c).mean(1, keepdim=True)
+    ve = me * me + (dep + 4) * U * (var + me * me) + U * (var + eps)
+    r, re = rsqrt_iv(var + eps, ve)
+    xh = c * r
+    he = (r + re) * me + c.abs() * re + 2 * U * (c.abs() + me) * (r + re)
+    y = xh * gamma + beta
+    ye = gamma.abs() * he + U * (xh * gamma).abs() + U * y.abs()
+    return {"y": (y, ye), "y16": flip(y, ye), "mean": (m, me), "rstd": (r, re)}
+
+
+def ln_bwd(dy, x, mean, rstd, gamma, g_old=None, s=None, drop=None, dgamma_old=None, dbeta_old=None):
+    """lafs_layernorm_bwd on exact operands (dy: the bf16 or fp32 gradient widened; mean, rstd [R, 1]: the fp32 statistics the kernel
+    is handed): {"g": the gradient stream (g_old + dx, or dx), "gb": its scaled / dropped-out bf16 copy, "dgamma", "dbeta"}.
+    xhat = (x - mean) rstd rounds twice; d = dy gamma once; the row means m1 = mean(d), m2 = mean(d xhat) are sums of depth
+    sum_depth(D) over terms that carry those errors, then a division; dx = rstd (d - m1 - xhat m2): three roundings inside, one
+    outside; the accumulate add rounds once; gb: the scale and the dropout factor round once each before the 16-bit store.
+    dgamma / dbeta: `colsum` over the rows with the old value as one more term (any order: slots or atomics), plus the three
+    roundings each term dy xhat carries."""
+    D = x.shape[1]
+    dep = sum_depth(D)
+    xh = (x - mean) * rstd
+    xhe = 2 * U * xh.abs()
+    d = dy * gamma
+    de = U * d.abs()
+    m1 = d.mean(1, keepdim=True)
+    m1e = (de.sum(1, keepdim=True) + dep * U * d.abs().sum(1, keepdim=True)) / D + U * m1.abs()
+    p = d * xh
+    pe = de * xh.abs() + d.abs() * xhe + U * p.abs()
+    m2 = p.mean(1, keepdim=True)
+    m2e = (pe.sum(1, keepdim=True) + dep * U * p.abs().sum(1, keepdim=True)) / D + U * m2.abs()
+    dx = rstd * (d - m1 - xh * m2)
+    dxe = rstd * (de + m1e + xh.abs() * m2e + xhe * (m2.abs() + m2e) + 3 * U * (d.abs() + m1.abs() + (xh * m2).abs())) + U * dx.abs()
+    g, ge = (dx, dxe) if g_old is None else (g_old + dx, dxe + U * (g_old + dx).abs())
+    f = torch.ones_like(g) if s is None else s.expand_as(g)
+    if drop is not None:
+        f = f * drop
+    out = {"g": (g, ge), "gb": flip(f * g, f.abs() * ge + 2 * U * (f * g).abs())}
+    a = dy * xh
+    z = torch.zeros(1, D, dtype=f64, device=x.device)
+    v, e = colsum(torch.cat([a, z if dgamma_old is None else dgamma_old[None]]))
+    out["dgamma"] = (v, e + 3 * U * a.abs().sum(0))
+    out["dbeta"] = colsum(torch.cat([dy, z if dbeta_old is None else dbeta_old[None]]))
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ the arena step (optim.hip)
+CHUNK = 1024
+SEG_DECAY, SEG_LAST_LAYER, SEG_TRAINABLE, SEG_LOW_DECAY = 1, 2, 4, 8                                                        # LAFS_SEG_*
+HP_LR, HP_WD, HP_BETA1, HP_BETA2, HP_EPS, HP_CLIP, HP_EMA_M, HP_FREEZE_LAST, HP_GRAD_SCALE, HP_WD_LOW = range(10)            # LAFS_HP_*
+
+
+def sumsq(grad, chunk_seg, n_seg, gs):
+    """lafs_grad_sumsq: per tensor sum (gs g)^2 over its chunks (grad [n_chunks, 1024] fp64).  Same-sign terms, so the worst-case form
+    of `colsum` -- but over the depth of the kernel's fixed summation tree instead of the element count: a square rounds (1), a lane
+    adds 16 of them, a 64-lane butterfly (6); then a thread adds ceil(chunks / 256) chunk sums, a butterfly (6), four wave sums (3),
+    and gs multiplies twice (2)."""
+    cs = (grad * grad).sum(1)
+    ss = torch.zeros(n_seg, dtype=f64, device=grad.device).index_add_(0, chunk_seg.long(), cs)
+    nc = torch.bincount(chunk_seg.long(), minlength=n_seg).double()
+    depth = 1 + 16 + 6 + torch.ceil(nc / 256) + 6 + 3 + 2
+    v = ss * gs * gs
+    return v, depth * U * v
+
+
+def clip_scale(ss, sse, clip, gs):
+    """The gradient factor of clip_adamw_ema_kernel per tensor: gs, times coef = clip / (sqrtf(ss) + 1e-6f) where coef < 1.  Returns
+    (factor, bound, knife): sqrtf, the add and the division round once each on top of what ss carries.  Where the fp64 coefficient
+    lies within its bound of 1 (`knife`) the kernel may take either branch, and the bound covers both."""
+    if not clip > 0:
+        return torch.full_like(ss, gs), torch.zeros_like(ss), torch.zeros_like(ss, dtype=torch.bool)
+    n = ss.sqrt()
+    ne = torch.maximum((ss + sse).sqrt() - n, n - (ss - sse).clamp_min(0).sqrt()) + U * n
+    den = n + f32c(1e-6)
+    dene = ne + U * den
+    coef = clip / den
+    ce = clip / (den - dene) - coef + U * coef
+    knife = (coef - 1).abs() <= ce
+    ref = gs * coef.clamp_max(1.0)
+    e = gs * ce + U * ref
+    e = torch.where(coef - ce >= 1, torch.zeros_like(e), e)
+    e = torch.where(knife, gs * (ce + (coef - 1).abs()) + U * gs, e)
+    return ref, e, knife
+
+
+def adamw_ema(p, g, m, v, t, chunk_seg, flags, step, ss, sse, hp):
+    """One lafs_clip_adamw_ema launch on fp64 copies of its fp32 state ([n_chunks, 1024] each; t: the teacher, or None), restated
+    after torch.optim.AdamW (decoupled decay, bias corrections, eps outside the root) with utils.clip_gradients per tensor and the
+    teacher EMA.  hp: the fp32 hyper-parameter vector widened -- the operands the kernel has.  step: seg_step before the launch.
+    Returns {"param", "m", "v", "teacher", "param16", "teacher16"} as (reference, bound), "seg_step" (exact) and "knife" (how many
+    tensors' clip branch is undecided).  Every fp32 operation of the kernel rounds once (u times its result), errors are carried
+    forward by the first-order terms written out below and by exact intervals through the divisions and roots; powf is allowed
+    POW_REL, so bc = 1 - beta^t is off by POW_REL beta^t -- at t = 1 and beta2 = 0.999 that is 1000 x POW_REL of bc2 itself, which
+    the bound then carries into the update.  Where sqrt(v) / sqrt(bc2) is comparable to eps the denominator's interval is wide
+    relative to itself and the bound widens through the quotient."""
+    lr, wd, b1, b2, eps, clip, em, frz, gs, wdl = (float(hp[i]) for i in range(10))
+    fl = flags.long()
+    upd_s = ((fl & SEG_TRAINABLE) != 0) & ~(((fl & SEG_LAST_LAYER) != 0) & (frz != 0))
+    new_step = step.long() + upd_s.long()
+    cs = chunk_seg.long()
+    col = lambda x: x[cs][:, None]
+    upd = col(upd_s)
+    wd_s = ((fl & SEG_DECAY) != 0).double() * wd
+    wd_s[(fl & SEG_LOW_DECAY) != 0] = wdl
+    gsc_s, gsce_s, knife = clip_scale(ss, sse, clip, gs)
+    tt = new_step.double().clamp_min(1)
+    o1, o2, oem = f32c(1.0) - b1, f32c(1.0) - b2, f32c(1.0) - em          # (1 - beta: exact in fp32 for beta in [0.5, 1])
+    pw1, pw2 = b1 ** tt, b2 ** tt
+    bc1, bc2 = 1 - pw1, 1 - pw2
+    bc1e, bc2e = POW_REL * pw1 + U * bc1, POW_REL * pw2 + U * bc2
+    ssz = lr / bc1
+    ssze = lr / (bc1 - bc1e) - ssz + U * ssz
+    isb, isbe = rsqrt_iv(bc2, bc2e)
+    dec = 1 - lr * wd_s
+    dece = U * lr * wd_s + U * dec
+    gsc, gsce, ssz, ssze, isb, isbe, dec, dece = (col(x) for x in (gsc_s, gsce_s, ssz, ssze, isb, isbe, dec, dece))
+    gg = g * gsc
+    gge = g.abs() * gsce + U * gg.abs()
+    p1 = p * dec
+    p1e = p.abs() * dece + U * p1.abs()
+    mn = m * b1 + gg * o1
+    mne = o1 * gge + 2 * U * ((m * b1).abs() + (gg * o1).abs()) + U * mn.abs()
+    vn = v * b2 + gg * gg * o2
+    vne = o2 * (2 * gg.abs() * gge + gge * gge) + 3 * U * (v * b2 + gg * gg * o2) + U * vn
+    sv = vn.sqrt()
+    sve = torch.maximum((vn + vne).sqrt() - sv, sv - (vn - vne).clamp_min(0).sqrt()) + U * sv
+    den = sv * isb + eps
+    dene = sve * (isb + isbe) + sv * isbe + U * sv * isb + U * den
+    num = ssz * mn
+    nume = ssze * mn.abs() + (ssz + ssze) * mne + U * num.abs()
+    q = num / den
+    qe = (num.abs() + nume) / (den - dene) - q.abs() + U * q.abs()
+    pn = p1 - q
+    pne = p1e + qe + U * pn.abs()
+    z = torch.zeros_like(p)
+    out = {"seg_step": new_step, "knife": int(knife[upd_s].sum())}
+    P, Pe = torch.where(upd, pn, p), torch.where(upd, pne, z)
+    out["param"] = (P, Pe)
+    out["m"] = (torch.where(upd, mn, m), torch.where(upd, mne, z))
+    out["v"] = (torch.where(upd, vn, v), torch.where(upd, vne, z))
+    out["param16"] = flip(P, Pe)
+    if t is not None:
+        tn = t * em + oem * P
+        tne = oem * Pe + 2 * U * ((t * em).abs() + (oem * P).abs()) + U * tn.abs()
+        out["teacher"] = (tn, tne)
+        out["teacher16"] = flip(tn, tne)
+    return out
 
 
 # ------------------------------------------------------------------------------------------------ checks

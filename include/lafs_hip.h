@@ -62,12 +62,21 @@ enum {
   LAFS_OPT_NT_TALL = 5,        /* tiled GEMM: 160-row tiles where they save a round of workgroup slots (default 1) */
   LAFS_OPT_COMM_CUS = 6,       /* data-parallel runs: CUs left to the collective library's kernels by the K-resident GEMM (default 0) */
   LAFS_OPT_NT_BIG = 7,         /* tiled GEMM: one-workgroup-per-CU 192x256 / 176x256 tiles for the wide long-K shapes (default 1; 2-4 force a geometry) */
-  LAFS_OPT_MLP_FUSED = 8,      /* trunk passes: the block's MLP as ONE launch (lafs_mlp_fused) where it applies (dim 384, no element dropout): bit mask
-                                  1 forward-only pass, 2 saving forward, 4 backward input gradients, 8 LayerNorm 2 inside the fused forward, 16 its backward inside the fused backward,
-                                  32 (lab) one MLP launch over all row chains, 64 the NEXT block's LayerNorm 1 in the fused forward's epilogue (bit-identical
-                                  to its launch), 128 / 256 the attention branch's output projection + residual in FRONT of the fused forward of the
-                                  forward-only / the saving pass.  Default 79 = 1 + 2 + 4 + 8 + 64: step A/B in DESIGN.md section 6 */
+  LAFS_OPT_MLP_FUSED = 8,      /* trunk passes: the block's MLP as ONE launch (lafs_mlp_fused) where it applies (dim 384, no element dropout):
+                                  a mask of LAFS_MLP_FUSED_* bits (default LAFS_MLP_FUSED_DEFAULT); lafs_trunk_plan reports what they come to */
   LAFS_OPT_COUNT = 9
+};
+enum {                                 /* bits of LAFS_OPT_MLP_FUSED */
+  LAFS_MLP_FUSED_FWD = 1,              /* the forward-only pass runs fc1 -> GELU -> fc2 -> residual as one launch */
+  LAFS_MLP_FUSED_FWD_SAVE = 2,         /* the saving forward does, and writes gelu'(u) and gelu(u) for the backward */
+  LAFS_MLP_FUSED_BWD = 4,              /* the backward's two MLP input-gradient GEMMs are one launch */
+  LAFS_MLP_FUSED_LN2 = 8,              /* LayerNorm 2 inside the fused forward (no launch, no round trip of its output) */
+  LAFS_MLP_FUSED_LN2_BWD = 16,         /* LayerNorm 2's backward inside the fused backward */
+  LAFS_MLP_FUSED_MERGE_CHAINS = 32,    /* (lab) the row chains meet in front of every MLP: one launch over all rows; switches NEXT_LN1 off */
+  LAFS_MLP_FUSED_NEXT_LN1 = 64,        /* the fused forward also writes the NEXT block's LayerNorm 1 (bit-identical to its launch) */
+  LAFS_MLP_FUSED_PROJ_FWD = 128,       /* forward-only pass: the attention branch's output projection + residual in FRONT of the fused forward */
+  LAFS_MLP_FUSED_PROJ_FWD_SAVE = 256,  /* the same in the saving forward (both need LN2 and inner == dim) */
+  LAFS_MLP_FUSED_DEFAULT = 1 + 2 + 4 + 8 + 64   /* = 79: step A/B in DESIGN.md section 6 */
 };
 lafs_ctx* lafs_ctx_create(int device);
 void lafs_ctx_destroy(lafs_ctx* ctx);
@@ -558,11 +567,39 @@ typedef struct lafs_trunk_desc {
   lafs_ctx* ctx;                      /* side streams / events / options of these passes (NULL: caller's stream only, default options) */
 } lafs_trunk_desc;
 
-/* Bytes of activation workspace for a forward with (1) / without (0) saving activations for backward. */
+/* Bytes of activation workspace for a forward with (1) / without (0) saving activations for backward.  The LayerNorm backward's
+ * gamma / beta slot buffers are sized for four row chains whatever LAFS_OPT_ROW_CHAINS says: the option may change on a live
+ * context after the workspace was sized. */
 int64_t lafs_trunk_workspace_bytes(const lafs_trunk_desc* d, int save_for_backward);
-/* Number of independent chains of launches (row ranges of the token batch, one stream each) the trunk passes of this descriptor
- * run as: 2 when there are two crop-resolution groups of >= 4096 full-length rows each (csrc/engine.hip:
- * row_ranges), else 1.  Tests assert the route they mean to cover. */
+/* What the trunk passes of this descriptor launch (csrc/engine.hip: plan): the ONE decision lafs_trunk_forward (with this
+ * save_for_backward), lafs_trunk_backward and its LayerNorm fold read.  Host logic only: no HIP call, so with ctx == NULL it runs
+ * without a device.  LAFS_OK, or the descriptor's refusal (text in lafs_last_error()).  Tests assert the route they mean to cover.
+ * Launch counts are not part of it: they follow from lafs_gemm_nt_plan and from lafs_mlp_fused's own unit sizes. */
+enum { LAFS_ATTN_ONE_LAUNCH = 0,       /* one attention launch over all sequences with max_len (n_groups <= 1) */
+       LAFS_ATTN_PER_GROUP = 1,        /* one launch per crop-resolution group, on the row range's stream */
+       LAFS_ATTN_PER_GROUP_FORKED = 2  /* one range, side streams: the second and later groups' launches on the first side stream */ };
+typedef struct lafs_trunk_range_plan {
+  int row0, rows;                      /* token rows [row0, row0 + rows) */
+  int group, seq0, n_seq;              /* (first) sequence group, first sequence, sequences */
+  int stream;                          /* 0: the caller's; i: the context's side stream i - 1.  Also the range's LayerNorm slot */
+  int fwd_fused;                       /* forward: the MLP is one lafs_mlp_fused launch (else two GEMMs), with ... */
+  int fwd_ln2_inside;                  /* ... LayerNorm 2 inside (not launched), */
+  int fwd_next_ln1;                    /* ... the next block's LayerNorm 1 written by it: LayerNorm 1 of blocks 1.. is not launched, */
+  int fwd_proj_inside;                 /* ... the attention projection + residual in front (their GEMM is not launched) */
+  int bwd_fused;                       /* backward: the MLP input gradients are one launch (else two GEMMs), with ... */
+  int bwd_ln2_inside;                  /* ... LayerNorm 2's backward inside (its gamma / beta slots fit the workspace's) */
+  int ln1_parts, ln2_parts;            /* gamma / beta partial slots the backward of each norm writes (lafs_layernorm_bwd_fold adds them) */
+} lafs_trunk_range_plan;
+typedef struct lafs_trunk_plan_info {
+  int n_ranges;                        /* independent chains of launches: 2 (4: half groups) with side streams, LAFS_OPT_ROW_CHAINS >= 2 (4)
+                                          and two crop-resolution groups of >= 4096 full-length rows each, else 1 */
+  int attention;                       /* LAFS_ATTN_* */
+  int mlp_merged;                      /* forward: the ranges meet in front of every MLP, which is ONE launch over `whole` */
+  lafs_trunk_range_plan range[4];      /* [n_ranges]; with mlp_merged their fwd_* describe the merged launch */
+  lafs_trunk_range_plan whole;         /* all rows as one range (= range[0] when n_ranges == 1) */
+} lafs_trunk_plan_info;
+int lafs_trunk_plan(const lafs_trunk_desc* d, int save_for_backward, lafs_trunk_plan_info* out);
+/* The plan's n_ranges; -1 for a refused descriptor. */
 int lafs_trunk_row_ranges(const lafs_trunk_desc* d);
 /* x_in(f32) [n_tok, dim] -> x_out(f32) [n_tok, dim]: residual stream after the last block.  With
  * save_for_backward != 0 x_in must stay untouched until lafs_trunk_backward has run (it is layer 0's saved input)

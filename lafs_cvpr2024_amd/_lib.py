@@ -76,6 +76,15 @@ class TrunkDesc(C.Structure):
                 ("dropout_step", C.c_void_p), ("wgrad_overwrite", C.c_int), ("wgrad_defer", C.c_int), ("ctx", C.c_void_p)]
 
 
+class TrunkRangePlan(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("row0", "rows", "group", "seq0", "n_seq", "stream", "fwd_fused", "fwd_ln2_inside", "fwd_next_ln1",
+                                       "fwd_proj_inside", "bwd_fused", "bwd_ln2_inside", "ln1_parts", "ln2_parts")]
+
+
+class TrunkPlanInfo(C.Structure):
+    _fields_ = [("n_ranges", C.c_int), ("attention", C.c_int), ("mlp_merged", C.c_int), ("range", TrunkRangePlan * 4), ("whole", TrunkRangePlan)]
+
+
 EPI_BF16, EPI_BF16_GELU, EPI_RESID_F32, EPI_F32, EPI_DGELU_BF16, EPI_ATOMIC_F32, EPI_EMBED_F32, EPI_BF16_ACT = range(8)
 ACT_NONE, ACT_RELU, ACT_HSWISH, ACT_HSIGMOID = range(4)
 MLP_FWD, MLP_FWD_SAVE, MLP_BWD = range(3)
@@ -87,6 +96,11 @@ HP_COUNT = 16
 # parameter row of lafs_mix_normalize / lafs_margin_softmax_ce_mix_bf16 (enum LAFS_MIX_* of lafs_hip.h)
 MIX_LAM, MIX_CUT, MIX_YL, MIX_YH, MIX_XL, MIX_XH, MIX_WORDS = range(7)
 OPT_SIDE_STREAMS, OPT_ROW_CHAINS, OPT_KRES_MASK, OPT_KRES_MIN_ITEMS, OPT_NT_WIDE, OPT_NT_TALL, OPT_COMM_CUS, OPT_NT_BIG, OPT_MLP_FUSED = range(9)
+# bits of OPT_MLP_FUSED (enum LAFS_MLP_FUSED_* of lafs_hip.h); the LAFS_MLP_FUSED environment variable takes their sum as an integer
+(MLP_FUSED_FWD, MLP_FUSED_FWD_SAVE, MLP_FUSED_BWD, MLP_FUSED_LN2, MLP_FUSED_LN2_BWD, MLP_FUSED_MERGE_CHAINS, MLP_FUSED_NEXT_LN1,
+ MLP_FUSED_PROJ_FWD, MLP_FUSED_PROJ_FWD_SAVE) = (1 << i for i in range(9))
+MLP_FUSED_DEFAULT = MLP_FUSED_FWD | MLP_FUSED_FWD_SAVE | MLP_FUSED_BWD | MLP_FUSED_LN2 | MLP_FUSED_NEXT_LN1
+ATTN_ONE_LAUNCH, ATTN_PER_GROUP, ATTN_PER_GROUP_FORKED = range(3)
 
 vp, i32, i64, f32, u32 = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
 
@@ -220,6 +234,7 @@ _NO_STREAM = {
     "lafs_dino_loss_workspace": ([i32, i32, i32], i64),
     "lafs_dino_head_loss_workspace": ([i32, i32, i32], i64),
     "lafs_trunk_workspace_bytes": ([C.POINTER(TrunkDesc), i32], i64),
+    "lafs_trunk_plan": ([C.POINTER(TrunkDesc), i32, C.POINTER(TrunkPlanInfo)], i32),
     "lafs_trunk_row_ranges": ([C.POINTER(TrunkDesc)], i32),
     "lafs_layernorm_bwd_parts": ([i32, i32], i32),
     "lafs_ijb_search_workspace": ([i32, i32, i32], i64),

@@ -17,7 +17,7 @@ def header_symbols():
 def test_header_declares_the_documented_surface():
     syms = header_symbols()
     for must in ("lafs_gemm_nt", "lafs_gemm_tn_acc", "lafs_layernorm_fwd", "lafs_layernorm_bwd", "lafs_attention_fwd", "lafs_attention_bwd",
-                 "lafs_dino_loss_fwd_bwd", "lafs_clip_adamw_ema", "lafs_trunk_forward", "lafs_trunk_backward", "lafs_patchify",
+                 "lafs_dino_loss_fwd_bwd", "lafs_clip_adamw_ema", "lafs_trunk_forward", "lafs_trunk_backward", "lafs_trunk_plan", "lafs_patchify",
                  "lafs_margin_softmax_ce", "lafs_patch_gather_fwd", "lafs_mixup_normalize", "lafs_center_ema", "lafs_last_error"):
         assert must in syms
 

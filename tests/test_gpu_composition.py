@@ -139,13 +139,19 @@ def test_benchmark_composition_vit_small_droppath_against_the_oracle(B):
     assert eng._graphs is not None and len(eng._graphs) == 1                       # one captured graph, as in the benchmark
     chains, rows, routes = _routes(eng)
     assert chains == 2, chains
-    # the block's MLP runs fused (engine.hip mlp_fused_on): forward-only, saving and backward passes, LayerNorm 2 and the next
-    # block's LayerNorm 1 inside, for both row chains -- not quietly as two GEMM launches
+    # the block's MLP runs fused: forward-only, saving and backward passes, LayerNorm 2 and the next block's LayerNorm 1 inside, for
+    # both row chains -- not quietly as two GEMM launches.  The engine's own answer (lafs_trunk_plan: the plan its passes run)
     h, d = _lib.lib(), eng._st["vit"].desc
     fused = h.lafs_ctx_get(d.ctx, _lib.OPT_MLP_FUSED)
-    assert fused & (1 | 2 | 4 | 8 | 64) == 1 | 2 | 4 | 8 | 64, fused
-    assert all(h.lafs_mlp_fused_supported(d.dim, d.mlp, R) == 1 for R in rows) and (d.dim, d.mlp) == (384, 1536), (d.dim, d.mlp, rows)
-    assert d.dropout_p == 0.0
+    assert fused & _lib.MLP_FUSED_DEFAULT == _lib.MLP_FUSED_DEFAULT and (d.dim, d.mlp, d.dropout_p) == (384, 1536, 0.0), fused
+    for save in (0, 1):
+        p = _lib.TrunkPlanInfo()
+        assert h.lafs_trunk_plan(C.byref(d), save, C.byref(p)) == 0, h.lafs_last_error()
+        assert (p.n_ranges, p.attention, p.mlp_merged) == (2, _lib.ATTN_PER_GROUP, 0), (p.n_ranges, p.attention, p.mlp_merged)
+        assert (p.range[0].row0, p.range[1].row0) == (0, rows[0]) and (p.range[0].rows, p.range[1].rows) == rows
+        for r in (p.range[0], p.range[1]):
+            assert (r.fwd_fused, r.fwd_ln2_inside, r.fwd_next_ln1, r.fwd_proj_inside) == (1, 1, 1, 0), (save, r.rows)
+            assert (r.bwd_fused, r.bwd_ln2_inside) == (1, 0), (save, r.rows)
     for name in ("qkv", "fc1", "proj", "dgelu"):
         assert all(r in (1, 2) for r in routes[name]), (name, routes)               # K-resident (either form)
     if B == 64:

@@ -617,50 +617,56 @@ from lafs_cvpr2024_amd.dino_loss import DINOLoss
 from lafs_cvpr2024_amd.engine import LafsPretrainEngine
 torch.manual_seed(11)
 B, K, nl = 14, 2048, 8                      # 2 x 14 x 197 = 5516 and 8 x 14 x 37 = 4144 token rows: both groups above the split threshold
+dim, heads, depth = [int(v) for v in sys.argv[2:5]] if len(sys.argv) > 2 else (128, 2, 3)
 LN6 = partial(nn.LayerNorm, eps=1e-6)
-mk = lambda: vits.VisionTransformer(img_size=[224], patch_size=8, embed_dim=128, depth=3, num_heads=2, qkv_bias=True, norm_layer=LN6,
+mk = lambda: vits.VisionTransformer(img_size=[224], patch_size=8, embed_dim=dim, depth=depth, num_heads=heads, qkv_bias=True, norm_layer=LN6,
                                     drop_path_rate=0.1)
-student = MultiCropWrapper(mk(), vits.DINOHead(128, K, hidden_dim=256, bottleneck_dim=64))
-teacher = MultiCropWrapper(mk(), vits.DINOHead(128, K, hidden_dim=256, bottleneck_dim=64))
+student = MultiCropWrapper(mk(), vits.DINOHead(dim, K, hidden_dim=256, bottleneck_dim=64))
+teacher = MultiCropWrapper(mk(), vits.DINOHead(dim, K, hidden_dim=256, bottleneck_dim=64))
 teacher.load_state_dict(student.state_dict())
 crops = [torch.randn(B, 3, 112, 112).clamp(-1, 1) for _ in range(2)] + [torch.randn(B, 3, 48, 48).clamp(-1, 1) for _ in range(nl)]
 eng = LafsPretrainEngine(student, teacher, DINOLoss(K, 2 + nl, 0.07, 0.04, 3, 10), B, n_local=nl, use_graph=True, device="cuda")
 losses = [float(eng.step(crops, lr=1e-3, wd=0.04, momentum=0.9, teacher_temp=0.05, epoch=1).item()) for _ in range(4)]
 torch.save({"losses": losses, "teacher": {k: v.cpu() for k, v in teacher.state_dict().items()},
             "student": {k: v.cpu() for k, v in student.state_dict().items()}}, sys.argv[1])
+import ctypes as C, json
+from lafs_cvpr2024_amd import _lib
+for save in (0, 1):                         # the plan the student trunk's passes ran (lafs_trunk_plan)
+    p = _lib.TrunkPlanInfo()
+    assert _lib.lib().lafs_trunk_plan(C.byref(eng._st["vit"].desc), save, C.byref(p)) == 0
+    print("PLAN", json.dumps([{n: getattr(p.range[i], n) for n, _ in p.range[i]._fields_} for i in range(p.n_ranges)]))
 print("CHAINS_DONE")
 '''
 
 
-def test_row_chains_equal_the_single_chain(tmp_path):
-    """The trunk passes as two chains of launches over the row ranges of the two crop-resolution groups (csrc/engine.hip:
-    row_ranges; LAFS_ROW_CHAINS, read once per process) against ONE chain over all rows: four captured steps from the same
-    initialisation -- and the two-chain run a second time, which must repeat BIT FOR BIT (losses and every weight), as must the run
-    with every LayerNorm 1 launched on its own instead of written by the previous block's fused MLP; the first loss is identical, the later ones and the weights agree up to the grouping of the LayerNorm / bias
-    gradients' partial sums (per chain, then folded in a fixed order) as Adam's first steps amplify it."""
+def _run_chains_snippet(tmp_path, tag, env, *dims):
+    """One run of _CHAINS_SNIPPET in a fresh process: (its saved losses and weights, the two plans it printed)."""
+    import json
     import os
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    out = {}
-    for mode in ("2", "0", "2 again", "2 ln1 launched"):
-        f = str(tmp_path / f"chains{mode[0]}{len(mode)}.pt")
-        env = dict(os.environ, LAFS_ROW_CHAINS=mode[0], PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""))
-        if mode == "2 ln1 launched":                     # LAFS_OPT_MLP_FUSED without bit 64: every LayerNorm 1 as its own launch
-            env["LAFS_MLP_FUSED"] = "15"
-        r = subprocess.run([sys.executable, "-c", _CHAINS_SNIPPET, f], env=env, capture_output=True, text=True, timeout=600, cwd=root)
-        assert r.returncode == 0 and "CHAINS_DONE" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
-        out[mode] = torch.load(f)
+    f = str(tmp_path / f"chains{tag}.pt")
+    env = dict(os.environ, PYTHONPATH=root + os.pathsep + os.environ.get("PYTHONPATH", ""), **env)
+    r = subprocess.run([sys.executable, "-c", _CHAINS_SNIPPET, f] + [str(v) for v in dims], env=env, capture_output=True, text=True, timeout=600,
+                       cwd=root)
+    assert r.returncode == 0 and "CHAINS_DONE" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+    return torch.load(f), [json.loads(line[5:]) for line in r.stdout.splitlines() if line.startswith("PLAN ")]
+
+
+def test_row_chains_equal_the_single_chain(tmp_path):
+    """The trunk passes as two chains of launches over the row ranges of the two crop-resolution groups (csrc/engine.hip:
+    plan; LAFS_ROW_CHAINS, read once per process) against ONE chain over all rows: four captured steps from the same
+    initialisation -- and the two-chain run a second time, which must repeat BIT FOR BIT (losses and every weight); the first loss
+    is identical, the later ones and the weights agree up to the grouping of the LayerNorm / bias gradients' partial sums (per chain,
+    then folded in a fixed order) as Adam's first steps amplify it.  (At this model's width of 128 the block's MLP never runs fused:
+    the fused MLP's own claims are held at width 384 by test_next_layernorm1_in_the_fused_mlp_equals_its_launch.)"""
+    out = {mode: _run_chains_snippet(tmp_path, f"{mode[0]}{len(mode)}", dict(LAFS_ROW_CHAINS=mode[0]))[0] for mode in ("2", "0", "2 again")}
     # the SAME configuration in another process: the captured step has no fp32 atomic left -- four steps repeat bit for bit
     assert out["2"]["losses"] == out["2 again"]["losses"], (out["2"]["losses"], out["2 again"]["losses"])
     for name in ("teacher", "student"):
         for k, v in out["2"][name].items():
             assert torch.equal(v, out["2 again"][name][k]), (name, k)
-    # LayerNorm 1 of blocks 1.. written by the previous block's fused MLP (the default) or by lafs_layernorm_fwd: the same bits
-    assert out["2"]["losses"] == out["2 ln1 launched"]["losses"], (out["2"]["losses"], out["2 ln1 launched"]["losses"])
-    for name in ("teacher", "student"):
-        for k, v in out["2"][name].items():
-            assert torch.equal(v, out["2 ln1 launched"][name][k]), (name, k)
     la, lb = out["2"]["losses"], out["0"]["losses"]
     print("[row-chains] relative loss differences, steps 0-3: " + " ".join(f"{abs(a - b) / abs(b):.2e}" for a, b in zip(la, lb)))
     assert abs(la[0] - lb[0]) < 1e-6 * abs(lb[0]), (la, lb)            # same weights: the forward is the same arithmetic
@@ -676,6 +682,29 @@ def test_row_chains_equal_the_single_chain(tmp_path):
             dw = (out["2"][name][k].float() - v.float()).abs()
             assert float(dw.max()) <= 4 * 2 * 1e-3 + 1e-6, (name, k)    # at most every step's update flipped: 4 steps x 2 lr
             assert float(dw.median()) <= 2e-5 * (1.0 + float(v.float().abs().max())), (name, k)
+
+
+def test_next_layernorm1_in_the_fused_mlp_equals_its_launch(tmp_path):
+    """LAFS_MLP_FUSED_NEXT_LN1: LayerNorm 1 of blocks 1.. written by the previous block's fused MLP (the default) against every
+    LayerNorm 1 launched on its own (LAFS_MLP_FUSED=15), at width 384 where the fused MLP runs -- each process prints the plan its
+    trunk passes ran, so the comparison cannot be of a configuration with itself.  Two row chains (5516 + 4144 rows), depth 2, four
+    captured steps from the same initialisation: the same bits, losses and every weight."""
+    from lafs_cvpr2024_amd import _lib
+    launched = _lib.MLP_FUSED_FWD | _lib.MLP_FUSED_FWD_SAVE | _lib.MLP_FUSED_BWD | _lib.MLP_FUSED_LN2
+    assert launched == 15 and launched | _lib.MLP_FUSED_NEXT_LN1 == _lib.MLP_FUSED_DEFAULT
+    out, plans = {}, {}
+    for mode, env in (("inside", {}), ("launched", dict(LAFS_MLP_FUSED=str(launched)))):
+        out[mode], plans[mode] = _run_chains_snippet(tmp_path, mode, env, 384, 6, 2)
+        print(f"[next-ln1 {mode}] plans (forward-only, saving): {plans[mode]}")
+        assert len(plans[mode]) == 2
+        for plan in plans[mode]:
+            assert [r["rows"] for r in plan] == [5516, 4144], plan
+            assert all(r["fwd_fused"] == 1 and r["fwd_ln2_inside"] == 1 and r["bwd_fused"] == 1 for r in plan), plan
+            assert all(r["fwd_next_ln1"] == (1 if mode == "inside" else 0) for r in plan), (mode, plan)
+    assert out["inside"]["losses"] == out["launched"]["losses"], (out["inside"]["losses"], out["launched"]["losses"])
+    for name in ("teacher", "student"):
+        for k, v in out["inside"][name].items():
+            assert torch.equal(v, out["launched"][name][k]), (name, k)
 
 
 def test_two_engines_on_two_contexts_and_two_caller_streams_equal_the_single_engine_runs():

@@ -419,3 +419,222 @@ def test_gemm_route_equals_the_plans_route_on_random_requests():
     finally:
         ctxs.close()
     assert {0, 1, 3, 4, 5, "refused"} <= seen and 60 <= refused <= 300, (seen, refused)
+
+
+# ------------------------------------------------------------------------------------------------ the trunk passes' plan (host logic)
+_B14 = ((28, 197), (112, 37))                               # 2 x 14 global + 8 x 14 local crops: 5516 + 4144 token rows
+
+
+def _trunk_desc(_lib, dim=384, mlp=1536, groups=_B14, n_groups=None, heads=None, ctx=None, **kw):
+    """A contract-keeping trunk descriptor on fake pointers (never dereferenced: the plan reads shapes, options and presence)."""
+    d = _lib.TrunkDesc()
+    d.dim, d.heads, d.mlp, d.depth = dim, heads or dim // 64, mlp, 2
+    d.inner = d.heads * 64
+    d.n_seq, d.n_tok, d.max_len = sum(n for n, _ in groups), sum(n * l for n, l in groups), max(l for _, l in groups)
+    d.cu_seqlens = d.row2seq = d.master = d.shadow = _fake()
+    d._blocks = (_lib.BlockOffsets * 2)()
+    d.blocks = d._blocks
+    d.n_groups = len(groups) if n_groups is None else n_groups
+    for gi, (n, l) in enumerate(groups[:d.n_groups]):
+        d.group_n_seq[gi], d.group_max_len[gi] = n, l
+    d.ctx = ctx
+    for k, v in kw.items():
+        setattr(d, k, v)
+    return d
+
+
+def _trunk_plan(_lib, h, d, save):
+    import ctypes as C
+    p = _lib.TrunkPlanInfo()
+    rc = int(h.lafs_trunk_plan(C.byref(d), save, C.byref(p)))
+    assert rc == 0, (rc, h.lafs_last_error())
+    assert h.lafs_trunk_row_ranges(C.byref(d)) == p.n_ranges
+    return p
+
+
+def _rp(r, *names):
+    return tuple(getattr(r, n) for n in (names or [n for n, _ in r._fields_]))
+
+
+_PLACE = ("row0", "rows", "group", "seq0", "n_seq", "stream")
+_FLAGS = ("fwd_fused", "fwd_ln2_inside", "fwd_next_ln1", "fwd_proj_inside", "bwd_fused", "bwd_ln2_inside")
+_PARTS = ("ln1_parts", "ln2_parts")
+
+
+def test_trunk_plan_without_a_context_one_case_per_rule():
+    """lafs_trunk_plan is what lafs_trunk_forward / _backward run (csrc/engine.hip: plan).  With ctx == NULL it makes no HIP call:
+    default options, no side streams -- hence ONE range even with two groups of 5516 and 4144 rows, and attention never forked."""
+    _lib, h = _plan_lib()
+    whole = (0, 9660, 0, 0, 140, 0)
+    for save in (0, 1):
+        # dim 384, mlp 1536, no dropout: fused forward (LayerNorm 2 inside, the next block's LayerNorm 1 written) and backward
+        # (LayerNorm 2's backward launched); the projection stays a GEMM.  256 = the LayerNorm backward's cap of 4096 / 16 workgroups
+        p = _trunk_plan(_lib, h, _trunk_desc(_lib), save)
+        assert (p.n_ranges, p.attention, p.mlp_merged) == (1, _lib.ATTN_PER_GROUP, 0)
+        assert _rp(p.range[0]) == _rp(p.whole) == whole + (1, 1, 1, 0, 1, 0) + (256, 256), _rp(p.range[0])
+        # nothing fused: another width (12 heads; 8 rows per LayerNorm-backward workgroup: 4096 / 8 = 512 slots) ...
+        p = _trunk_plan(_lib, h, _trunk_desc(_lib, dim=768, mlp=2048), save)
+        assert _rp(p.range[0]) == _rp(p.whole) == whole + (0,) * 6 + (512, 512) and p.n_ranges == 1
+        # ... element dropout ...
+        p = _trunk_plan(_lib, h, _trunk_desc(_lib, dropout_p=0.1), save)
+        assert _rp(p.range[0]) == whole + (0,) * 6 + (256, 256)
+        # ... a hidden width above 1536 or below 128
+        for mlp in (1600, 64):
+            assert _rp(_trunk_plan(_lib, h, _trunk_desc(_lib, mlp=mlp), save).range[0], *_FLAGS) == (0,) * 6, mlp
+        # the attention form: one launch over all sequences without groups or with one, else one per group on the caller's stream
+        one = ((28, 197),)
+        assert _trunk_plan(_lib, h, _trunk_desc(_lib, n_groups=0), save).attention == _lib.ATTN_ONE_LAUNCH
+        assert _trunk_plan(_lib, h, _trunk_desc(_lib, groups=one), save).attention == _lib.ATTN_ONE_LAUNCH
+        p = _trunk_plan(_lib, h, _trunk_desc(_lib, groups=one), save)
+        assert _rp(p.range[0], *_PLACE) == (0, 5516, 0, 0, 28, 0) and _rp(p.range[0], *_FLAGS) == (1, 1, 1, 0, 1, 0)
+        assert _trunk_plan(_lib, h, _trunk_desc(_lib), save).attention == _lib.ATTN_PER_GROUP
+
+
+def test_trunk_queries_refuse_what_the_passes_refuse():
+    """Every refusal of the descriptor check comes back from lafs_trunk_plan (-2), lafs_trunk_row_ranges (-1) and
+    lafs_trunk_workspace_bytes (-1) alike, with its text."""
+    import ctypes as C
+    _lib, h = _plan_lib()
+    g1 = _trunk_desc(_lib)
+    g1.group_n_seq[1] = 0
+    g2 = _trunk_desc(_lib)
+    g2.group_max_len[0] = 198
+    cases = [
+        ("null descriptor", None),
+        ("dims must be multiples of 64", _trunk_desc(_lib, dim=100, heads=2)),
+        ("dims must be multiples of 64", _trunk_desc(_lib, mlp=1000)),
+        ("dims must be multiples of 64", _trunk_desc(_lib, inner=320)),
+        ("bad geometry", _trunk_desc(_lib, depth=0)),
+        ("bad geometry", _trunk_desc(_lib, max_len=257)),
+        ("null pointer in descriptor", _trunk_desc(_lib, master=None)),
+        ("null pointer in descriptor", _trunk_desc(_lib, row2seq=None)),
+        ("dropout_p must be in [0, 1)", _trunk_desc(_lib, dropout_p=1.0)),
+        ("at most 4 sequence groups", _trunk_desc(_lib, n_groups=5)),
+        ("bad sequence group", g1),
+        ("bad sequence group", g2),
+        ("sequence groups must cover n_seq", _trunk_desc(_lib, n_seq=141)),
+    ]
+    ref = lambda d: None if d is None else C.byref(d)
+    queries = (lambda d: h.lafs_trunk_plan(ref(d), 1, C.byref(_lib.TrunkPlanInfo())), lambda d: h.lafs_trunk_row_ranges(ref(d)),
+               lambda d: h.lafs_trunk_workspace_bytes(ref(d), 1))
+    other = _trunk_desc(_lib, n_tok=0)                      # (a different refusal in front of each query: the text read is its own)
+    for why, d in cases:
+        for query, code in zip(queries, (-2, -1, -1)):
+            assert query(other) == code and "bad geometry" in h.lafs_last_error().decode()
+            if "geometry" in why:
+                assert query(cases[1][1]) == code
+            rc, text = int(query(d)), h.lafs_last_error().decode()
+            assert rc == code and why in text, (why, rc, text)
+    assert h.lafs_trunk_plan(C.byref(_trunk_desc(_lib)), 1, None) == -2 and "null plan" in h.lafs_last_error().decode()
+    assert h.lafs_trunk_workspace_bytes(C.byref(_trunk_desc(_lib)), 1) > 0
+
+
+def test_trunk_plan_with_options_by_hand_and_its_invariants():
+    """The plan under LAFS_OPT_ROW_CHAINS / _SIDE_STREAMS / _MLP_FUSED, written out by hand: one case per rule of csrc/engine.hip's
+    plan.  Options need a context, which needs a device: without one all of these cases are passed over and counted -- the rules a
+    NULL context reaches are held by the test above."""
+    _lib, h = _plan_lib()
+    L = _lib
+    RC, SS, MF = L.OPT_ROW_CHAINS, L.OPT_SIDE_STREAMS, L.OPT_MLP_FUSED
+    FWD, SAVE, BWD, LN2, LN2B, MERGE, NEXT, PRJ, PRJS = (L.MLP_FUSED_FWD, L.MLP_FUSED_FWD_SAVE, L.MLP_FUSED_BWD, L.MLP_FUSED_LN2, L.MLP_FUSED_LN2_BWD,
+                                                        L.MLP_FUSED_MERGE_CHAINS, L.MLP_FUSED_NEXT_LN1, L.MLP_FUSED_PROJ_FWD, L.MLP_FUSED_PROJ_FWD_SAVE)
+    DEF = L.MLP_FUSED_DEFAULT
+    assert DEF == 79 and (FWD, SAVE, BWD, LN2, LN2B, MERGE, NEXT, PRJ, PRJS) == (1, 2, 4, 8, 16, 32, 64, 128, 256)
+    two = [(0, 5516, 0, 0, 28, 0), (5516, 4144, 1, 28, 112, 1)]
+    four = [(0, 2758, 0, 0, 14, 0), (2758, 2758, 0, 14, 14, 1), (5516, 2072, 1, 28, 56, 2), (7588, 2072, 1, 84, 56, 3)]
+    one = [(0, 9660, 0, 0, 140, 0)]
+    PG, FK = L.ATTN_PER_GROUP, L.ATTN_PER_GROUP_FORKED
+    on, off = (1, 1, 1, 0, 1, 0), (0,) * 6
+    # (options, descriptor, save) -> (ranges, attention, merged, flags of every range, (ln1_parts, ln2_parts) per range or None)
+    cases = [
+        # the row ranges
+        ({}, {}, 1, two, PG, 0, on, [(256, 256), (256, 256)]),
+        ({RC: 1}, {}, 1, one, FK, 0, on, [(256, 256)]),
+        ({RC: 4}, {}, 1, four, PG, 0, on, [(173, 173), (173, 173), (130, 130), (130, 130)]),
+        ({SS: 0}, {}, 1, one, PG, 0, on, None),
+        ({SS: 0, RC: 4}, {}, 0, one, PG, 0, on, None),
+        ({RC: 1}, dict(groups=((28, 197),)), 1, [(0, 5516, 0, 0, 28, 0)], L.ATTN_ONE_LAUNCH, 0, on, None),
+        # both sides of the 4096-row threshold, either group
+        ({}, dict(groups=((32, 128), (64, 64))), 1, [(0, 4096, 0, 0, 32, 0), (4096, 4096, 1, 32, 64, 1)], PG, 0, on, None),
+        ({}, dict(groups=((32, 128), (65, 63))), 1, [(0, 8191, 0, 0, 97, 0)], FK, 0, on, None),
+        ({RC: 4}, dict(groups=((35, 117), (64, 64))), 1, [(0, 8191, 0, 0, 99, 0)], FK, 0, on, None),
+        # a group of one sequence (at most 256 rows: below the threshold) stays with the other in one range, four chains or not
+        ({RC: 4}, dict(groups=((1, 197), (112, 37))), 1, [(0, 4341, 0, 0, 113, 0)], FK, 0, on, None),
+        # the fused bits alone ...
+        ({MF: 0}, {}, 1, two, PG, 0, off, None),
+        ({MF: FWD}, {}, 0, two, PG, 0, (1, 0, 0, 0, 0, 0), None),
+        ({MF: FWD}, {}, 1, two, PG, 0, off, None),
+        ({MF: SAVE}, {}, 1, two, PG, 0, (1, 0, 0, 0, 0, 0), None),
+        ({MF: SAVE}, {}, 0, two, PG, 0, off, None),
+        ({MF: BWD}, {}, 1, two, PG, 0, (0, 0, 0, 0, 1, 0), None),
+        ({MF: LN2 | LN2B | NEXT | PRJ | PRJS}, {}, 1, two, PG, 0, off, None),                # nothing without the launch they ride on
+        ({MF: FWD | SAVE | NEXT}, {}, 1, two, PG, 0, (1, 0, 1, 0, 0, 0), None),
+        # ... LayerNorm 2's backward inside: 128-row units, one slot each
+        ({MF: DEF | LN2B}, {}, 1, two, PG, 0, (1, 1, 1, 0, 1, 1), [(256, 44), (256, 33)]),
+        ({MF: (DEF | LN2B) & ~BWD}, {}, 1, two, PG, 0, (1, 1, 1, 0, 0, 0), [(256, 256), (256, 256)]),
+        # ... the merged MLP launch: MERGE_CHAINS switches NEXT_LN1 off, merged or not
+        ({MF: DEF | MERGE}, {}, 1, two, PG, 1, (1, 1, 0, 0, 1, 0), None),
+        ({MF: DEF | MERGE, RC: 1}, {}, 1, one, FK, 0, (1, 1, 0, 0, 1, 0), None),
+        ({MF: BWD | MERGE}, {}, 1, two, PG, 0, (0, 0, 0, 0, 1, 0), None),
+        ({MF: DEF | MERGE | PRJ | PRJS}, {}, 1, two, PG, 1, (1, 1, 0, 0, 1, 0), None),
+        # ... the projection in front: per pass, only with LayerNorm 2 inside and inner == dim
+        ({MF: DEF | PRJ | PRJS}, {}, 0, two, PG, 0, (1, 1, 1, 1, 1, 0), None),
+        ({MF: DEF | PRJ | PRJS}, {}, 1, two, PG, 0, (1, 1, 1, 1, 1, 0), None),
+        ({MF: DEF | PRJ}, {}, 1, two, PG, 0, on, None),
+        ({MF: DEF | PRJS}, {}, 0, two, PG, 0, on, None),
+        ({MF: (DEF | PRJ | PRJS) & ~LN2}, {}, 1, two, PG, 0, (1, 0, 1, 0, 1, 0), None),
+        ({MF: DEF | PRJ | PRJS}, dict(heads=5), 1, two, PG, 0, on, None),
+    ]
+    ctxs = _Contexts(h)
+    passed_over = 0
+    try:
+        for i, (opts, dkw, save, ranges, attn, merged, flags, parts) in enumerate(cases):
+            ctx = ctxs.get(opts)
+            if ctx is None:
+                passed_over += 1
+                continue
+            p = _trunk_plan(_lib, h, _trunk_desc(_lib, ctx=ctx, **dkw), save)
+            assert (p.n_ranges, p.attention, p.mlp_merged) == (len(ranges), attn, merged), (i, p.n_ranges, p.attention, p.mlp_merged)
+            assert [_rp(p.range[k], *_PLACE) for k in range(p.n_ranges)] == ranges, i
+            assert all(_rp(p.range[k], *_FLAGS) == flags for k in range(p.n_ranges)), (i, [_rp(p.range[k], *_FLAGS) for k in range(p.n_ranges)])
+            assert parts is None or [_rp(p.range[k], *_PARTS) for k in range(p.n_ranges)] == parts, (i, [_rp(p.range[k], *_PARTS) for k in range(2)])
+            assert _rp(p.whole, *_PLACE) == (0, sum(r[1] for r in ranges), 0, 0, sum(r[4] for r in ranges), 0), i
+            if merged or p.n_ranges == 1:
+                assert _rp(p.whole, *_FLAGS[:4]) == flags[:4], i
+        # invariants over the whole grid of options, shapes and passes
+        shapes = [{}, dict(dim=128, mlp=512), dict(dropout_p=0.1), dict(heads=5), dict(n_groups=0), dict(groups=((4, 197), (16, 37))),
+                  dict(groups=((32, 128), (65, 63))), dict(groups=((28, 197),))]
+        n_plans = 0
+        for chains in (1, 2, 4):
+            for side in (0, 1):
+                for mf in (0, FWD, SAVE, BWD, 15, DEF, DEF | LN2B, DEF | MERGE, DEF | PRJ | PRJS, 511, 511 & ~MERGE, 511 & ~LN2, 511 & ~BWD):
+                    ctx = ctxs.get({RC: chains, SS: side, MF: mf})
+                    if ctx is None:
+                        continue
+                    for dkw in shapes:
+                        for save in (0, 1):
+                            d = _trunk_desc(_lib, ctx=ctx, **dkw)
+                            p = _trunk_plan(_lib, h, d, save)
+                            n_plans += 1
+                            rs = [p.range[k] for k in range(p.n_ranges)]
+                            assert 1 <= p.n_ranges <= (chains if side else 1)
+                            assert rs[0].row0 == 0 and rs[-1].row0 + rs[-1].rows == d.n_tok == p.whole.rows           # the ranges tile [0, n_tok) ...
+                            assert all(a.row0 + a.rows == b.row0 and a.seq0 + a.n_seq == b.seq0 for a, b in zip(rs, rs[1:]))
+                            assert rs[0].seq0 == 0 and rs[-1].seq0 + rs[-1].n_seq == d.n_seq
+                            if p.n_ranges > 1:                                                                      # ... from sequence boundaries
+                                assert all(r.rows == r.n_seq * d.group_max_len[r.group] and r.stream == k for k, r in enumerate(rs))
+                            assert (p.attention == L.ATTN_ONE_LAUNCH) == (d.n_groups <= 1)
+                            assert (p.attention == FK) == (d.n_groups > 1 and p.n_ranges == 1 and side == 1)
+                            assert not p.mlp_merged or (p.n_ranges > 1 and mf & MERGE and p.whole.fwd_fused)
+                            for r in rs + [p.whole]:
+                                assert not r.fwd_next_ln1 or (r.fwd_fused and not p.mlp_merged and mf & NEXT and not mf & MERGE)
+                                assert not r.fwd_proj_inside or (r.fwd_ln2_inside and d.inner == d.dim and not p.mlp_merged)
+                                assert not r.fwd_ln2_inside or r.fwd_fused
+                                assert not r.bwd_ln2_inside or (r.bwd_fused and mf & LN2B)
+                                assert not (r.fwd_fused or r.bwd_fused) or (d.dim == 384 and d.dropout_p == 0)
+                                assert r.ln1_parts == h.lafs_layernorm_bwd_parts(r.rows, d.dim)
+                                assert r.ln2_parts == (h.lafs_mlp_fused_ln_parts(r.rows) if r.bwd_ln2_inside else r.ln1_parts)
+        assert n_plans == (3 * 2 * 13 * len(shapes) * 2 if torch.cuda.is_available() else 0)
+    finally:
+        ctxs.close()
+    assert len(cases) == 30 and passed_over == (0 if torch.cuda.is_available() else len(cases))

@@ -789,6 +789,42 @@ typedef struct lafs_face_tensor_aug_rec {
 int lafs_face_tensor_aug(const uint8_t* images, uint8_t* out, const lafs_face_tensor_aug_rec* recs, int B, int H, int W, int S,
                          hipStream_t stream);
 
+/* JPEG decode of the RecordIO loaders (the reference decodes with mx.image.imdecode in its DataLoader workers, image_iter.py:300-306;
+ * this project's CPU path is Pillow).  libjpeg's integer arithmetic, bit-exact against Pillow (libjpeg-turbo): Huffman decoding,
+ * dequantisation, jidctint "islow", "fancy" h2v1 / h2v2 chroma upsampling (replication for planes of width <= 2), YCbCr -> RGB.
+ * Accepted: SOF0 / SOF1 with 8-bit samples, one scan (Ss = 0, Se = 63, Ah = Al = 0), one component (written to all three planes)
+ * or three read as YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1, restart intervals, 1 <= W, H <= LAFS_JPEG_MAX_DIM.
+ * The host walks the markers (lafs_cvpr2024_amd/jpeg.py parse / pack) and hands over, per image, one record and the bytes of its scan:
+ *   data_off, data_len   the entropy-coded bytes (stuffed FF 00 and RSTn markers included, up to but excluding the marker that ends
+ *                        the scan) inside `stream`
+ *   table_off            byte offset inside `tables` of this image's LAFS_JPEG_TABLE_BYTES block: 4 x 64 uint16 quantiser entries
+ *                        (little-endian, DQT = zigzag order, slot = table id) followed by the Huffman tables DC 0, DC 1, AC 0, AC 1,
+ *                        each 16 BITS bytes + 256 HUFFVAL bytes, zero-padded; images with the same tables may share a block
+ *   width, height        must equal the W, H of the call
+ *   ncomp                1 or 3;   hs, vs  sampling factors (1x1 for one component);   tq, td, ta  table ids per component
+ *   restart_interval     MCUs between RSTn markers, 0 = none
+ * out u8 [B,3,H,W]; status i32 [B]: 0 = decoded, otherwise a sum of LAFS_JPEG_ST_* and out[b] is undefined (but only out[b] and
+ * the image's own workspace slice were written; a record that fails validation writes nothing).  The kernel trusts no field of a
+ * record, table or stream: every loop is bounded by the block count of a W x H image, reads are clamped to data_len.
+ * workspace: lafs_jpeg_workspace_bytes(B, H, W) bytes, 16-byte aligned (-1 for sizes outside the limits). */
+#define LAFS_JPEG_MAX_DIM 1024
+#define LAFS_JPEG_TABLE_BYTES 1600
+enum { LAFS_JPEG_ST_RECORD = 1,   /* record refused: size, sampling, offsets */
+       LAFS_JPEG_ST_OVERRUN = 2,  /* bits were needed past the end of the scan or past a marker */
+       LAFS_JPEG_ST_CODE = 4,     /* no Huffman code matched within 16 bits */
+       LAFS_JPEG_ST_COEF = 8,     /* a run went past coefficient 63, or a DC value left the int16 range */
+       LAFS_JPEG_ST_RESTART = 16  /* the expected RSTn marker was not there */ };
+typedef struct lafs_jpeg_image {
+  int64_t data_off;
+  int32_t data_len, table_off;
+  int32_t width, height, ncomp, restart_interval;
+  uint8_t hs[3], vs[3], tq[3], td[3], ta[3];
+  uint8_t pad[17];
+} lafs_jpeg_image;
+int64_t lafs_jpeg_workspace_bytes(int B, int H, int W);
+int lafs_jpeg_decode(const uint8_t* stream, int64_t stream_bytes, const lafs_jpeg_image* images, const uint8_t* tables,
+                     int64_t table_bytes, int B, int H, int W, uint8_t* out, int32_t* status, void* workspace, hipStream_t stream_id);
+
 /* Face verification of the fine-tune loop (reference util/utils.py:292-397 perform_val, util/verification.py:38-87 calculate_roc,
  * :224-234 calculate_accuracy; called every VER_FREQ optimizer steps by train_largescale.py:925-959).
  * lafs_eval_flip_normalize: src u8 [B,3,S,S] -> dst f32 [2B,3,S,S]; rows 0..B-1 = x / div * mul + add, every operation rounded on its

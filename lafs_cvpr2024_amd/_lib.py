@@ -191,6 +191,7 @@ _PROTOS = {
     "lafs_augment_views": [vp, vp, vp, i32, i32, vp],
     "lafs_randaug_apply": [vp, vp, vp, i32, i32, i32, i32, i32],
     "lafs_face_tensor_aug": [vp, vp, vp, i32, i32, i32, i32],
+    "lafs_jpeg_decode": [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp],
     "lafs_eval_flip_normalize": [vp, vp, i32, i32, f32, f32, f32],
     "lafs_verify_tail": [vp, i32, i32, i32, i32, i32, vp, i32, vp, i32, vp, vp, vp, vp, vp],
     "lafs_ijb_align_flip_normalize": [vp, i64, vp, vp, vp, i32, i32, f32, f32, f32, vp, vp],
@@ -239,6 +240,7 @@ _NO_STREAM = {
     "lafs_layernorm_bwd_parts": ([i32, i32], i32),
     "lafs_ijb_search_workspace": ([i32, i32, i32], i64),
     "lafs_wgrad_workspace_bytes": ([i32, i32, i32], i64),
+    "lafs_jpeg_workspace_bytes": ([i32, i32, i32], i64),
     "lafs_wgrad_group_workspace_bytes": ([C.POINTER(WgradItem), i32, i32, i32], i64),
 }
 EXPORTED = sorted(list(_PROTOS) + list(_NO_STREAM))

@@ -73,12 +73,15 @@ def get_args_parser():
                         "'synthetic_u8': uint8 112x112 images, augmented ON THE DEVICE (augment.DeviceAugmenter, Pillow-exact) into "
                         "the 20 views, then the landmark front-end -- the whole input pipeline of the reference on the GPU; "
                         "'recordio': the same from --data_path/train.rec (MXNet RecordIO, InsightFace layout; JPEG decode on "
-                        "--num_workers CPU workers, everything after it on the device)")
+                        "--num_workers CPU workers unless --decode device, everything after it on the device)")
     p.add_argument('--landmark_ckpt', '--landmark_path', dest='landmark_ckpt', default='', type=str,
                    help="state_dict of the frozen landmark CNN (reference --landmark_path, :112, :262-268)")
     # flags of the reference's PIL / recordio input pipeline: parsed for command-line compatibility, unused with synthetic data
     p.add_argument('--data_path', default='', type=str)
     p.add_argument('--num_workers', default=6, type=int)
+    p.add_argument('--decode', default='pillow', type=str, choices=['pillow', 'device'],
+                   help="--data recordio: 'pillow' decodes the JPEG records on the CPU workers; 'device' decodes each batch in one launch "
+                        "(jpeg.DeviceJpegDecoder, byte-identical; records the device does not take still go through Pillow)")
     p.add_argument('--global_crops_scale', type=float, nargs='+', default=(0.4, 1.))
     p.add_argument('--local_crops_scale', type=float, nargs='+', default=(0.05, 0.4))
     p.add_argument('--steps_per_epoch', default=100, type=int, help="iterations per epoch for --data synthetic")
@@ -156,7 +159,7 @@ class RecordIOViews:
     """--data_path/train.rec (reference lafs_train.py:157-191: FaceDataset over MXNet recordio + DataLoader) -> decoded uint8
     batches -> device-side DataAugmentation_LAFS.  One pass over the dataset per epoch, sharded over the ranks."""
 
-    def __init__(self, path, batch, n_local, device, seed, num_workers, rank=0, world=1):
+    def __init__(self, path, batch, n_local, device, seed, num_workers, rank=0, world=1, decode="pillow"):
         from .augment import DeviceAugmenter
         from .recordio import FaceRecordDataset
         self.ds = FaceRecordDataset(os.path.join(path, 'train.rec'))
@@ -168,6 +171,7 @@ class RecordIOViews:
         # permutation seeded with (seed, epoch), identical on all ranks (set_epoch)
         self.per_rank = len(self.all_seq) // world
         self.batch, self.device, self.seed, self.workers = batch, device, seed, num_workers
+        self.decode = decode
         self.aug = DeviceAugmenter(batch, n_local=n_local, device=device, seed=seed)
         self.epoch = 0
         self.set_epoch(0)
@@ -184,7 +188,7 @@ class RecordIOViews:
     def __iter__(self):
         from .recordio import device_batches
         for u8, _ in device_batches(self.ds, self.batch, self.device, num_workers=self.workers, shuffle=True,
-                                    seed=self.seed + self.epoch):
+                                    seed=self.seed + self.epoch, decode=self.decode):
             yield self.aug(u8), None
 
 
@@ -252,7 +256,7 @@ def train_lafs(args, dataset=None):
         data_loader = dataset
     elif args.data == 'recordio':
         data_loader = RecordIOViews(args.data_path, args.batch_size_per_gpu, args.local_crops_number, device,
-                                    args.seed + utils.get_rank(), args.num_workers, utils.get_rank(), world)
+                                    args.seed + utils.get_rank(), args.num_workers, utils.get_rank(), world, decode=args.decode)
         frontend = build_landmark_frontend(args, device)
     elif args.data in ('synthetic_views', 'synthetic_u8'):
         cls = SyntheticViews if args.data == 'synthetic_views' else SyntheticU8Views

@@ -423,3 +423,27 @@ def dino_loss_fwd_bwd(student, teacher, center, ncrops, student_temp, teacher_te
     call("lafs_dino_loss_fwd_bwd", _p(student), _p(teacher), ld, _p(center), ncrops, B, K, student_temp, teacher_temp,
          _p(loss), _p(grad), _ld(grad), 1 if grad.dtype == bf16 else 0, grad_scale, _p(ws), _p(dev_temps))
     return loss, grad
+
+
+def jpeg_decode(stream, images, tables, B, H, W, out=None, status=None, workspace=None):
+    """One launch of lafs_jpeg_decode (csrc/jpeg.hip) over what jpeg.pack built: stream / images / tables are uint8 device tensors
+    (scan bytes, B 64-byte records, 1600-byte table blocks).  Writes out u8 [B,3,H,W] and returns status i32 [B] (0 = decoded)."""
+    for t, n in ((stream, "stream"), (images, "images"), (tables, "tables"), (out, "out"), (workspace, "workspace")):
+        _chk(t, torch.uint8, n)
+    _chk(status, torch.int32, "status")
+    if not (stream.is_contiguous() and images.is_contiguous() and tables.is_contiguous()) or images.numel() != 64 * B:
+        raise _lib.LafsHipError("jpeg_decode: contiguous buffers and one 64-byte record per image")
+    need = _lib.lib().lafs_jpeg_workspace_bytes(B, H, W)
+    if need < 0:
+        raise _lib.LafsHipError(f"jpeg_decode: B={B}, H={H}, W={W} outside 1..LAFS_JPEG_MAX_DIM")
+    dev = stream.device
+    if out is None:
+        out = torch.empty(B, 3, H, W, device=dev, dtype=torch.uint8)
+    if status is None:
+        status = torch.empty(B, device=dev, dtype=torch.int32)
+    if workspace is None:
+        workspace = torch.empty(need, device=dev, dtype=torch.uint8)
+    if tuple(out.shape) != (B, 3, H, W) or not out.is_contiguous() or status.numel() != B or workspace.numel() < need:
+        raise _lib.LafsHipError("jpeg_decode: out must be contiguous [B,3,H,W], status [B], workspace lafs_jpeg_workspace_bytes(B,H,W)")
+    call("lafs_jpeg_decode", _p(stream), stream.numel(), _p(images), _p(tables), tables.numel(), B, H, W, _p(out), _p(status), _p(workspace))
+    return status

@@ -15,6 +15,10 @@ trips only (tests/test_recordio.py):
 of which holds the [first, last) range of its images) and yields (uint8 HWC RGB image, integer label); JPEG decoding is Pillow's
 (the reference uses mx.image.imdecode, i.e. OpenCV).  `device_batches` turns it into uint8 NCHW device batches for
 augment.DeviceAugmenter -- the rest of the reference's loader (PIL transforms in 6 workers) runs on the GPU here.
+
+With decode=False the dataset yields the encoded bytes and the marker walk of jpeg.parse instead of pixels, and
+`device_batches(..., decode="device")` decodes each batch in one launch (jpeg.DeviceJpegDecoder; samples the device does not take
+go through Pillow into their slots), byte-identical to the default decode="pillow".
 """
 import io
 import os
@@ -126,7 +130,8 @@ class IndexedRecordIO:
 class FaceRecordDataset:
     """The index logic of the reference's FaceDataset (image_iter.py:262-296) + Pillow decoding."""
 
-    def __init__(self, path_imgrec, partition=1):
+    def __init__(self, path_imgrec, partition=1, decode=True):
+        self.decode = decode            # False: __getitem__ -> (encoded bytes, label, jpeg plan or None) for the device decoder
         self.rec = IndexedRecordIO(path_imgrec[:-4] + ".idx", path_imgrec)
         header, _ = unpack(self.rec.read_idx(0))
         if header.flag > 0:
@@ -150,22 +155,46 @@ class FaceRecordDataset:
         label = header.label
         if not isinstance(label, (int, float)):
             label = label[0]
+        if not self.decode:
+            from .jpeg import try_parse
+            return img, int(label), try_parse(img)
         arr = np.asarray(Image.open(io.BytesIO(img)).convert("RGB"))
         return arr, int(label)
 
 
-def device_batches(dataset, batch_size, device, num_workers=6, shuffle=True, seed=0, drop_last=True):
-    """uint8 NCHW device batches [B,3,H,W] + int64 labels from a FaceRecordDataset (decode on CPU workers, everything after
-    it on the device)."""
+def undecoded(dataset):
+    """A shallow copy of a FaceRecordDataset that yields (encoded bytes, label, jpeg plan or None): same index, same order."""
+    import copy
+    ds = copy.copy(dataset)
+    ds.decode = False
+    return ds
+
+
+def device_batches(dataset, batch_size, device, num_workers=6, shuffle=True, seed=0, drop_last=True, decode="pillow"):
+    """uint8 NCHW device batches [B,3,H,W] + int64 labels from a FaceRecordDataset.  decode="pillow": JPEG decode on the CPU workers,
+    everything after it on the device; decode="device": the workers only read and parse the records, the decode is one launch per
+    batch (jpeg.DeviceJpegDecoder) -- the same bytes, labels and order."""
     import torch
+    if decode not in ("pillow", "device"):
+        raise ValueError("decode must be 'pillow' or 'device'")
+    decoder = None
+    if decode == "device":
+        from .jpeg import DeviceJpegDecoder
+        dataset, decoder = undecoded(dataset), DeviceJpegDecoder(device)
 
     def collate(items):
+        y = torch.tensor([it[1] for it in items], dtype=torch.int64)
+        if decoder is not None:
+            return [it[0] for it in items], y, [it[2] for it in items]
         x = torch.from_numpy(np.stack([it[0] for it in items])).permute(0, 3, 1, 2).contiguous()
-        return x, torch.tensor([it[1] for it in items], dtype=torch.int64)
+        return x, y
 
     g = torch.Generator().manual_seed(seed)
     loader = torch.utils.data.DataLoader(dataset, batch_size=batch_size, shuffle=shuffle, num_workers=num_workers, drop_last=drop_last,
                                          collate_fn=collate, pin_memory=(torch.device(device).type == "cuda"), generator=g,
                                          persistent_workers=num_workers > 0)
-    for x, y in loader:
-        yield x.to(device, non_blocking=True), y.to(device, non_blocking=True)
+    for batch in loader:
+        if decoder is not None:
+            yield decoder(batch[0], batch[2]), batch[1].to(device, non_blocking=True)
+        else:
+            yield batch[0].to(device, non_blocking=True), batch[1].to(device, non_blocking=True)

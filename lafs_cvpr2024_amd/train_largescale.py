@@ -11,7 +11,8 @@ reference but never reaches its optimizer), mixup alpha/prob, cutmix / cutmix-mi
 Input: `--data recordio --data_path DIR` reads DIR/train.rec (MXNet RecordIO, InsightFace layout, recordio.FaceRecordDataset) with
 the labels of its records, one pass over this rank's shard per epoch (lafs_train.epoch_shard: every rank runs the same number of
 steps); `--data synthetic` feeds random uint8 batches and labels.  The reference's FaceDataset (image_iter.py:299-351, built at
-train_largescale.py:506) is applied in its order: JPEG decode (Pillow, CPU workers) -> `--rand_mirror` -> channel reversal when
+train_largescale.py:506) is applied in its order: JPEG decode (Pillow on the CPU workers, or `--decode device`: one launch per
+batch, jpeg.py, byte-identical) -> `--rand_mirror` -> channel reversal when
 'ms1m' is not in the path (RecordIO only) -> `--rand_au` RandAugment (randaug.py) -> `--random_resizecrop` torchvision tensor
 chain RandomResizedCrop / ColorJitter / RandomErasing (face_tensor_aug.py; PARITY UNPINNED (restated from torchvision 0.9.1;
 torchvision is not installed)), all after the decode on the device.  With RecordIO the tensor chain's decisions are drawn in the
@@ -75,9 +76,12 @@ def get_args_parser():
     p.add_argument("--pretrain_path", default="", type=str, help="stage-1 checkpoint with the landmark CNN (alias of --landmark_ckpt)")
     p.add_argument("--data", default="synthetic", type=str,
                    help="'synthetic': random uint8 batches and labels; 'recordio': --data_path/train.rec (MXNet RecordIO, InsightFace "
-                        "layout; JPEG decode on --num_workers CPU workers, everything after it on the device)")
+                        "layout; JPEG decode on --num_workers CPU workers unless --decode device, everything after it on the device)")
     p.add_argument("--data_path", default="", type=str, help="directory holding train.rec / train.idx (--data recordio)")
     p.add_argument("--num_workers", default=6, type=int, help="DataLoader workers decoding RecordIO samples")
+    p.add_argument("--decode", default="pillow", type=str, choices=["pillow", "device"],
+                   help="--data recordio: 'pillow' decodes the JPEG records on the CPU workers; 'device' decodes each batch in one launch "
+                        "(jpeg.DeviceJpegDecoder, byte-identical; records the device does not take still go through Pillow)")
     p.add_argument("--rand_au", default=False, type=utils.bool_flag,
                    help="RandAugment of the reference's FaceDataset (rand_au=True, train_largescale.py:506) on the device")
     p.add_argument("--rand_au_config", default="rand-m1-mstd0.5-inc1", type=str, help="config_str of train_largescale.py:506")
@@ -219,19 +223,31 @@ class _WithTensorRecords:
 
     def __getitem__(self, index):
         from .face_tensor_aug import sample_one
-        arr, label = self.ds[index]
+        item = self.ds[index]
+        if len(item) == 3:              # undecoded (recordio.undecoded): the records need only H and W, which the plan carries
+            buf, label, plan = item
+            if plan is not None:
+                H, W = plan.height, plan.width
+            else:                       # not a stream the device takes: Pillow reads the size from the header
+                import io
+                from PIL import Image
+                W, H = Image.open(io.BytesIO(buf)).size
+        else:
+            arr, label = item
+            H, W = arr.shape[0], arr.shape[1]
         if self._gen is None or self._pid != os.getpid():
             worker = torch.utils.data.get_worker_info()
             self._gen = torch.Generator().manual_seed(worker.seed if worker is not None else self.seed)
             self._pid = os.getpid()
-        return arr, label, sample_one(self._gen, arr.shape[0], arr.shape[1])
+        rec = sample_one(self._gen, H, W)
+        return (buf, label, plan, rec) if len(item) == 3 else (arr, label, rec)
 
 
 class RecordIOFaces:
     """--data_path/train.rec -> (uint8 [B,3,H,W] device batch, int64 labels, tensor-chain records or None), one pass over this
     rank's shard per epoch (lafs_train.epoch_shard, DistributedSampler semantics: every rank gets len // world samples)."""
 
-    def __init__(self, path, batch, device, seed, num_workers, rank, world, num_class, tensor_records=False):
+    def __init__(self, path, batch, device, seed, num_workers, rank, world, num_class, tensor_records=False, decode="pillow"):
         from .recordio import FaceRecordDataset
         rec = os.path.join(path, "train.rec")
         self.ds = FaceRecordDataset(rec)
@@ -241,6 +257,12 @@ class RecordIOFaces:
         self.per_rank = len(self.all_seq) // world
         self.batch, self.device, self.workers, self.num_class = batch, device, num_workers, num_class
         self.tensor_records = tensor_records
+        if decode not in ("pillow", "device"):
+            raise ValueError("decode must be 'pillow' or 'device'")
+        self.decoder = None
+        if decode == "device":
+            from .jpeg import DeviceJpegDecoder
+            self.decoder = DeviceJpegDecoder(device)
         self.epoch = 0
         self.set_epoch(0)
         print(f"Data loaded: there are {len(self.all_seq)} images ({self.per_rank} per rank).")
@@ -258,12 +280,16 @@ class RecordIOFaces:
         import numpy as np
         from .face_tensor_aug import RECORD
         g = torch.Generator().manual_seed(self.seed * 1000003 + self.rank * 1009 + self.epoch)
-        ds = _WithTensorRecords(self.ds, int(torch.randint(0, 2 ** 62, (1,), generator=g))) if self.tensor_records else self.ds
+        from .recordio import undecoded
+        base = undecoded(self.ds) if self.decoder is not None else self.ds
+        ds = _WithTensorRecords(base, int(torch.randint(0, 2 ** 62, (1,), generator=g))) if self.tensor_records else base
 
         def collate(items):
-            x = torch.from_numpy(np.stack([it[0] for it in items])).permute(0, 3, 1, 2).contiguous()
             y = torch.tensor([it[1] for it in items], dtype=torch.int64)
-            recs = np.stack([it[2] for it in items]).astype(RECORD) if self.tensor_records else None
+            recs = np.stack([it[-1] for it in items]).astype(RECORD) if self.tensor_records else None
+            if self.decoder is not None:                 # the bytes and their plans: decoded on the device below
+                return ([it[0] for it in items], [it[2] for it in items]), y, recs
+            x = torch.from_numpy(np.stack([it[0] for it in items])).permute(0, 3, 1, 2).contiguous()
             return x, y, recs
 
         loader = torch.utils.data.DataLoader(ds, batch_size=self.batch, shuffle=True, num_workers=self.workers, drop_last=True,
@@ -272,7 +298,8 @@ class RecordIOFaces:
             top = int(y.max()) if int(y.min()) >= 0 else int(y.min())
             if not 0 <= top < self.num_class:
                 raise ValueError(f"{self.ds.rec.rec_path}: label {top} is outside [0, --num_class={self.num_class})")
-            yield x.to(self.device, non_blocking=True), y.to(self.device, non_blocking=True), recs
+            x = self.decoder(*x) if self.decoder is not None else x.to(self.device, non_blocking=True)
+            yield x, y.to(self.device, non_blocking=True), recs
 
 
 def verify(args, evaluator, engine, vers, highest_acc, backbone, epoch, batch):
@@ -333,7 +360,7 @@ def main(args):
     data = None
     if args.data == "recordio":
         data = RecordIOFaces(args.data_path, args.batch_size, device, cfg["SEED"], args.num_workers, utils.get_rank(), world,
-                             args.num_class, tensor_records=args.random_resizecrop)
+                             args.num_class, tensor_records=args.random_resizecrop, decode=args.decode)
         n_it = len(data)
         if n_it == 0:
             raise ValueError(f"{args.data_path}: {data.per_rank} images per rank are fewer than one batch of {args.batch_size}")

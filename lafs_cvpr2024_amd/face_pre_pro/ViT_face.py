@@ -429,7 +429,9 @@ class ViTs_face_overlap(nn.Module):
     cls rows (lafs_bn1d_fwd / lafs_bn1d_bwd).  4-D images or 3-D [B, n, 3 * ac_patch_size**2] window vectors; a list of crops runs
     one pass per run of equal-sided crops, so the batch statistics and the running-statistic updates are per group, in list order.
     ``soft_split``, ``dropout`` and ``to_latent`` are kept as attributes for parity and never called; ``fc``, whose result the
-    reference discards (:1606-1607), is ignored.  ``drop_path_rate``: the reference hard-codes 0.1 in Residual_droppath."""
+    reference discards (:1606-1607), is ignored.  ``drop_path_rate``: the reference hard-codes 0.1 in Residual_droppath.
+    ``loss_type='CosFace'`` builds the margin head the reference left commented out (:1539-1549; key ``loss.weight``, as in Part-fViT), which
+    ``forward_features(img, label=y)`` applies (:1609-1611) and FinetuneEngine trains; ``'None'`` builds the released key set."""
 
     def __init__(self, *, loss_type, GPU_ID, num_class, image_size, patch_size, ac_patch_size, pad, dim, depth, heads, mlp_dim,
                  pool='cls', channels=3, dim_head=64, dropout=0., emb_dropout=0., drop_path_rate=0.1):
@@ -470,7 +472,15 @@ class ViTs_face_overlap(nn.Module):
         self.pool = pool
         self.to_latent = nn.Identity()
         self.mlp_head = nn.Sequential(nn.BatchNorm1d(dim))
-        self.loss_type, self.pred, self.GPU_ID, self.fc = loss_type, None, GPU_ID, None     # (no loss module: commented out at :1539-1549)
+        self.loss_type, self.pred, self.GPU_ID, self.fc = loss_type, None, GPU_ID, None
+        # the margin head the reference left commented out at :1539-1549 (`loss.weight`, as in Part-fViT): what a fine-tune needs.
+        # 'None' builds no module, so the released checkpoints still load with strict=True
+        if loss_type == 'None':
+            pass
+        elif loss_type == 'CosFace':
+            self.loss = CosFace(in_features=dim, out_features=num_class, device_id=GPU_ID)
+        else:
+            raise NotImplementedError(f"loss_type {loss_type!r}: only 'CosFace' and 'None' exist in the reference")
         self._arena, self._spec, self._hook = None, None, None
 
     _sample_drop_scales = ViT_face_landmark_patch8._sample_drop_scales
@@ -511,11 +521,26 @@ class ViTs_face_overlap(nn.Module):
         The position table is sliced ``[:, :n + 1]``, not resampled (:1590)."""
         if mask is not None:
             raise NotImplementedError("attention masks are not on the hot path (the packed attention kernels take none)")
-        if label is not None:
+        if label is not None and not hasattr(self, "loss"):
             raise NotImplementedError("the reference builds no loss module for this class (its construction is commented out at "
                                       ":1539-1549), so its label branch cannot run there either")
         if patch_drop is not None and patch_drop > 0:
             raise NotImplementedError("patch_drop > 0 leaves a non-square number of tokens, which the packed geometry cannot describe yet")
+        n_img, side, n = self._window_geometry(img)
+        bn = self.mlp_head[0]
+        if self.training and n_img < 2:                   # what nn.BatchNorm1d raises (torch/nn/functional.py _verify_batch_size)
+            raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([n_img, self.dim])}")
+        geom = Fn.geometry([(n_img, side)], img.device, window=(self.ac_patch_size, self.patch_size, self.pad))
+        emb = _FViTFunction.apply(self, self._hook, img, self.pos_embedding[0, :n + 1], geom)
+        if self.training:
+            bn.num_batches_tracked += 1
+        if label is not None:                             # reference :1609-1611
+            return self.loss(emb, label), emb
+        return emb
+
+    def _window_geometry(self, img):
+        """(images, side, windows) of one group -- [B, 3, S, S] images or [B, n, 3 k^2] window vectors -- with the arena attached and
+        fresh; `side` is a side that unfolds into sqrt(n) windows per side."""
         if self._arena is None:
             attach_arena(self)
         self._arena.ensure_fresh()
@@ -539,11 +564,23 @@ class ViTs_face_overlap(nn.Module):
         if n > self.num_patches:
             raise ValueError(f"the input unfolds into {n} windows, the position table holds {self.num_patches} "
                              f"((image_size // patch_size) ** 2): build the model with a larger image_size")
-        bn = self.mlp_head[0]
-        if self.training and n_img < 2:                   # what nn.BatchNorm1d raises (torch/nn/functional.py _verify_batch_size)
-            raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size([n_img, self.dim])}")
-        geom = Fn.geometry([(n_img, side)], img.device, window=(k, stride, pad))
-        emb = _FViTFunction.apply(self, self._hook, img, self.pos_embedding[0, :n + 1], geom)
+        return n_img, side, n
+
+    @torch.no_grad()
+    def get_selfattention(self, x, layer=-1, cls_only=False):
+        """Attention probabilities of block `layer`: attn f32 [B, heads, n+1, n+1], or [B, heads, 1, n+1] (the cls query alone) with
+        `cls_only`; token 1 + i r + j is window (i, j) of nn.Unfold's row-major r x r grid.  The signature and rules of
+        ViT_face_landmark_patch8.get_selfattention, without a theta: the blocks in front of `layer` run as usual and
+        lafs_attention_probs forms P from that block's own q and k with the dim ** -0.5 scale.  Eval mode only, so the BatchNorm head
+        behind the blocks reads its running statistics and writes nothing: the buffers and num_batches_tracked stay as they are.
+        Attention masks are not supported."""
         if self.training:
-            bn.num_batches_tracked += 1
-        return emb
+            raise RuntimeError("get_selfattention reads out the deterministic eval-mode forward: call model.eval() first")
+        if not -self.depth <= layer < self.depth:
+            raise ValueError(f"layer must be in {-self.depth}..{self.depth - 1}, got {layer}")
+        layer %= self.depth
+        n_img, side, n = self._window_geometry(x)
+        geom = Fn.geometry([(n_img, side)], x.device, window=(self.ac_patch_size, self.patch_size, self.pad))
+        pos = self.pos_embedding[0, :n + 1].detach().contiguous()
+        tokens, streams = Fn.vit_streams(self._arena, self._spec, geom, [x.contiguous().float()], [pos], [max(layer, 1)])
+        return Fn.vit_block_probs(self._arena, self._spec, geom, streams[0] if layer > 0 else tokens, layer, q_rows=1 if cls_only else 0)

@@ -1,4 +1,4 @@
-"""Fused Part-fViT + CosFace fine-tune micro-step (reference train_largescale.py:785-891) on the HIP kernels.
+"""Fused Part-fViT / fViT + CosFace fine-tune micro-step (reference train_largescale.py:785-891) on the HIP kernels.
 
     u8 batch -> (x/255*2-1) + batch mixup (one kernel) -> [trainable landmark CNN -> theta -> patch gather] -> Part-fViT trunk ->
     L2-normalised embedding x L2-normalised class centres (MFMA GEMM) -> fused margin + softmax + soft-target CE (the dense [B, C]
@@ -17,6 +17,12 @@ buffers are broadcast from rank 0 at construction; the micro-steps of an accumul
 graph as on one rank (deferred weight gradients included), and the window's LAST micro-step -- whose gradient slices go out over RCCL
 as the backward retires them -- is captured as one hipGraph per segment with the FlatReducer launches between the replays, exactly as
 LafsPretrainEngine does.  Only the class-sharded head keeps the eager form (its collectives sit inside the head itself).
+
+fViT (ViTs_face_overlap, `--net VITs`): the same step with the overlapping window embedding (lafs_unfold_bf16 in front of the embedding
+GEMM, the window geometry) and the BatchNorm1d head on the cls rows (lafs_bn1d_fwd / lafs_bn1d_bwd: batch statistics and the running-
+statistic update in training mode, running statistics in eval mode); no landmark branch.  `num_batches_tracked` is counted on the
+host, one per training micro-step, and added to the buffer when a state_dict is taken (flush_batches_tracked).  Data-parallel: every
+rank normalises with its own batch statistics, as the reference's plain DDP does (no SyncBatchNorm).
 """
 import os
 
@@ -25,7 +31,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, functional as Fn, ops
-from .face_pre_pro.ViT_face import ViT_face_landmark_patch8
+from .face_pre_pro.ViT_face import ViT_face_landmark_patch8, ViTs_face_overlap
 from .distributed import FlatReducer
 from .ops import _p, call
 from .utils import PinnedRing
@@ -65,12 +71,15 @@ class FinetuneEngine:
                                     "subset is not defined here): use the dense CosFace head")
         if label_smoothing > 0.0 and margin_type != 0:
             raise _lib.LafsHipError("label smoothing needs the CosFace margin: ArcFace has no margin for a dense target")
-        if not isinstance(backbone, ViT_face_landmark_patch8) or (sharded_head is None and not hasattr(backbone, "loss")):
-            raise _lib.LafsHipError("FinetuneEngine drives ViT_face_landmark_patch8(loss_type='CosFace') or a sharded head")
+        if not isinstance(backbone, (ViT_face_landmark_patch8, ViTs_face_overlap)) or (sharded_head is None and not hasattr(backbone, "loss")):
+            raise _lib.LafsHipError("FinetuneEngine drives ViT_face_landmark_patch8 or ViTs_face_overlap with loss_type='CosFace', or "
+                                    "either of them with a sharded head")
         if batch_size % 8:
             raise _lib.LafsHipError("FinetuneEngine needs a batch size that is a multiple of 8 (16-byte rows in the class-gradient GEMM)")
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
         self.model, self.B, self.acc_step = backbone, batch_size, acc_step
+        self.fvit = isinstance(backbone, ViTs_face_overlap)          # window embedding + BatchNorm1d head, no landmark branch
+        self.with_land = bool(getattr(backbone, "with_land", False))
         self.mixup_alpha, self.mixup_prob = mixup_alpha, mixup_prob
         self.label_smoothing = float(label_smoothing)
         # per-row mixing (CutMix, pair / elem modes, smoothing): the reference's own class draws the parameters
@@ -87,6 +96,7 @@ class FinetuneEngine:
         self.ctx = _lib.Ctx(self.device)                 # this engine's side streams / events / kernel options (lafs_ctx)
         self.arena.ctx = self.ctx
         self.cnn_flush = None
+        self.bn_forward = 0                              # fViT: training forwards of the BatchNorm1d head since the last flush (below)
         if self.world > 1:
             # DDP's construction-time broadcast of parameters AND buffers from rank 0 (train_largescale.py:676-677; before the landmark
             # plan below takes its references to the BatchNorm statistics).  DDP also re-broadcasts the buffers before every forward:
@@ -101,7 +111,11 @@ class FinetuneEngine:
         self.Cpad = (self.C + 127) // 128 * 128
         self.D = backbone.dim
         self.S = image_size
-        self.geom = Fn.geometry([(batch_size, image_size)], self.device)
+        self.geom = Fn.geometry([(batch_size, image_size)], self.device,
+                                window=(backbone.ac_patch_size, backbone.patch_size, backbone.pad) if self.fvit else None)
+        if self.fvit and self.geom.npatch(0) > backbone.num_patches:
+            raise _lib.LafsHipError(f"a {image_size}-pixel image unfolds into {self.geom.npatch(0)} windows, the position table holds "
+                                    f"{backbone.num_patches}")
         dev, a, m, B, D = self.device, self.arena, backbone, batch_size, self.D
         self.hyper = torch.zeros(_lib.HP_COUNT, device=dev, dtype=f32)
         self.hyper_ring = PinnedRing((_lib.HP_COUNT,), f32)     # asynchronous upload; a pageable copy would block the host
@@ -164,7 +178,7 @@ class FinetuneEngine:
             self.dxn = torch.empty(B, D, device=dev, dtype=f32)
             self.dxn_ws = ops.wgrad_workspace(self.Cpad, B, D, dev)                 # d(emb_n): reduction over the classes
             self.dwn_ws = None if B % 32 == 0 else ops.wgrad_workspace(B, self.Cpad, D, dev)
-        self.dmosaic = torch.empty(B, 3, S, S, device=dev, dtype=f32) if m.with_land else None
+        self.dmosaic = torch.empty(B, 3, S, S, device=dev, dtype=f32) if self.with_land else None
         self.dth = None
         self.micro = 0                                   # micro-steps taken (seeds the per-step masks)
         self._since_opt = 0                              # ... since the last optimizer step
@@ -175,12 +189,16 @@ class FinetuneEngine:
         # Dropout(0.5)) and in eval mode (running statistics as constants of the backward, no dropout); LAFS_FT_CNN=torch, for A/B
         # runs, takes the nn.Module on torch autograd
         self.cnn = None
-        if m.with_land and os.environ.get("LAFS_FT_CNN", "hip") == "hip":
+        if self.with_land and os.environ.get("LAFS_FT_CNN", "hip") == "hip":
             from .landmark_train import HipLandmarkTrainer
             self.cnn = HipLandmarkTrainer(m, a, batch_size, image_size, device=dev)
             self.cnn.step_dev = self.hyper[_lib.HP_STEP:]
             m.register_state_dict_pre_hook(lambda *a_, **k_: self.cnn.flush_batches_tracked())
             self.cnn_flush = self.cnn.flush_batches_tracked
+        # fViT's BatchNorm1d head: nn.BatchNorm1d.num_batches_tracked += 1 per training forward, counted here and flushed when a
+        # state_dict is taken (as the landmark plan does): no ATen increment inside or beside a micro-step
+        if self.fvit:
+            m.register_state_dict_pre_hook(lambda *a_, **k_: self.flush_batches_tracked())
         # streams / graphs
         # (The blocks' weight gradients on a second stream INSIDE the chain were measured neutral at C4 -- 27.24 ms with, 27.03 without --
         # and removed in round 5: tools/lab/NOTES.md.  What pays is deferring them beside the landmark CNN's backward, below.)
@@ -203,12 +221,20 @@ class FinetuneEngine:
         self._pool = None
         self._ws = None
 
+    def flush_batches_tracked(self):
+        """fViT: the head's num_batches_tracked += the training micro-steps run since the last flush (the counter only matters for
+        state_dict parity -- the momentum is a constant -- so it is brought up to date when a state_dict is taken)."""
+        if self.bn_forward:
+            self.model.mlp_head[0].num_batches_tracked.add_(self.bn_forward)
+            self.bn_forward = 0
+
     def sync_buffers(self):
-        """Every rank takes rank 0's buffers (BatchNorm running statistics and counters of the landmark CNN): what DDP's
-        broadcast_buffers does in front of every forward (train_largescale.py:676-677)."""
+        """Every rank takes rank 0's buffers (BatchNorm running statistics and counters of the landmark CNN / of fViT's head): what
+        DDP's broadcast_buffers does in front of every forward (train_largescale.py:676-677)."""
         if self.world > 1:
             if self.cnn_flush is not None:
                 self.cnn_flush()
+            self.flush_batches_tracked()
             for b in self.model.buffers():
                 dist.broadcast(b, 0)
 
@@ -274,7 +300,7 @@ class FinetuneEngine:
 
     def _capturable(self):
         m = self.model
-        return self.use_graph and (not m.with_land or self.cnn is not None)
+        return self.use_graph and (not self.with_land or self.cnn is not None)
 
     def micro_step(self, inputs_u8, labels, lam=None, mix=None):
         """One forward/backward on a uint8 NCHW batch.  Gradients accumulate in the arena (loss pre-divided by acc_step).
@@ -315,6 +341,8 @@ class FinetuneEngine:
                 self.cnn.n_forward += 1
         else:
             self._body(first)
+        if self.fvit and m.training:                     # nn.BatchNorm1d.num_batches_tracked: one training forward per micro-step
+            self.bn_forward += 1
         self.micro += 1
         self._since_opt += 1
         return self.loss
@@ -323,11 +351,15 @@ class FinetuneEngine:
         """One eager micro-step body on a side stream BEFORE the first capture (as LafsPretrainEngine._capture does): code objects
         are loaded, kernel attributes set and the per-step workspaces (`_ws`, `dth`) allocated by the ordinary allocator instead of
         from inside a stream capture / the graph's private pool.  The state the body mutates -- gradients, the loss, the landmark
-        CNN's BatchNorm running statistics and loss-scale state -- is snapshotted and put back."""
+        CNN's BatchNorm running statistics and loss-scale state, the running statistics of fViT's head -- is snapshotted and put back
+        (a first step counted twice would be a 10 % error of the statistics at momentum 0.1)."""
         a, cnn = self.arena, self.cnn
         bn = []
+        if self.fvit:
+            head = self.model.mlp_head[0]
+            bn = [head.running_mean, head.running_var]
         if cnn is not None:
-            bn = [t for s in [cnn.stem["bn"]] + [L[k] for L in cnn.blocks for k in ("bn1", "bn2", "bn3")] for t in (s["rm"], s["rv"]) if t is not None]
+            bn += [t for s in [cnn.stem["bn"]] + [L[k] for L in cnn.blocks for k in ("bn1", "bn2", "bn3")] for t in (s["rm"], s["rv"]) if t is not None]
             bn.append(cnn.gscale)
         saved = [t.clone() for t in [a.grad, self.loss] + bn]
         n_fwd = cnn.n_forward if cnn is not None else 0
@@ -396,8 +428,8 @@ class FinetuneEngine:
         if m.training and (m.dropout_rate > 0.0 or m.emb_dropout_rate > 0.0):
             dropout = (m.dropout_rate, m.emb_dropout_rate, m._drop_seed0, hp[_lib.HP_STEP:])
         img_in, theta, th = self.x, None, None
-        self._cnn_hip = m.with_land and self.cnn is not None
-        if m.with_land:
+        self._cnn_hip = self.with_land and self.cnn is not None
+        if self.with_land:
             # trainable landmark regressor -> one-launch patch gather (ViT_face.py:679-711)
             theta = self.cnn.forward(self.x) if self._cnn_hip else m.landmarks(self.x)
             m.theta = theta
@@ -412,7 +444,7 @@ class FinetuneEngine:
         emb, st, _ = Fn.vit_forward(a, m._spec, self.geom, [img_in], [self.pos_rows], drop, save=True, dropout=dropout, ws=self._ws,
                                     x_in=self.x_in, x_out=self.x_out, wgrad_overwrite=first,
                                     wgrad_workgroups=self.wgrad_workgroups if defer else 0,
-                                    wgrad_defer=defer)
+                                    wgrad_defer=defer, bn_training=m.training)
         if self.head is not None:
             # class-sharded head: all-gather embeddings, local logits, exchanged softmax statistics, reduce-scatter of dE.
             # demb is the gradient of the GLOBAL-batch mean loss, so the later all-reduce of the backbone gradients is a SUM.
@@ -509,7 +541,7 @@ class FinetuneEngine:
                     self._head_first = None
         elif deferred:                                   # (eval-mode model / torch CNN: nothing to hide them behind)
             Fn.vit_wgrad_layers(st, m.depth, 0)
-        if m.with_land:
+        if self.with_land:
             _, dx = Fn.vit_backward_end(a, m._spec, st, g, want_dx=True, dpos_out=[self.dpos_rows])
             call("lafs_unpatchify_f32", _p(dx[0]), B, self.S, m._spec.patch_order, _p(self.dmosaic))
             if self.dth is None:

@@ -464,7 +464,7 @@ def _decode(path):
 
 class IJBEvaluator:
     def __init__(self, backbone, batch_size=360, device=None, norm="reference", workers=8):
-        """backbone: ViT_face_landmark_patch8 (with or without the landmark branch); batch_size: loose crops per batch; norm:
+        """backbone: ViT_face_landmark_patch8 (with or without the landmark branch) or ViTs_face_overlap; batch_size: loose crops per batch; norm:
         'reference' (x/255 - 0.5, :235) or 'train' (the fine-tune feed); workers: decode threads (at most 16)."""
         import torch
         from .verification import NORMS
@@ -483,7 +483,7 @@ class IJBEvaluator:
         self._stage = self._dev = None
         S = IMAGE_SIZE
         self._x = torch.empty(2 * self.B, 3, S, S, device=self.device, dtype=torch.float32)
-        self._mosaic = torch.empty_like(self._x) if backbone.with_land else None
+        self._mosaic = torch.empty_like(self._x) if getattr(backbone, "with_land", False) else None
         self._al = torch.empty(self.B, 3, S, S, device=self.device, dtype=torch.uint8)
 
     def _staging(self, n_bytes):
@@ -577,7 +577,7 @@ def main(argv=None):
     import torch
     from . import train_largescale as tl
     from .vision_transformer import attach_arena
-    p = argparse.ArgumentParser("Part-fViT IJB evaluation", parents=[tl.get_args_parser()], conflict_handler="resolve")
+    p = argparse.ArgumentParser("Part-fViT / fViT IJB evaluation", parents=[tl.get_args_parser()], conflict_handler="resolve")
     p.add_argument("--checkpoint", default="", type=str, help="fine-tune checkpoint (not needed with --features)")
     p.add_argument("--image_path", required=True, type=str, help="directory with loose_crop/ and meta/")
     p.add_argument("--target", default="IJBC", type=str, choices=["IJBC", "IJBB"])

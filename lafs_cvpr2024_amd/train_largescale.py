@@ -24,6 +24,8 @@ and rank 0 saves a `_checkpoint.pth` whenever need_save (:49-62, 955-959) says t
 the divisor is clamped to >= 1 (the reference divides by zero on small datasets) and an evaluation happens at eval_step = 3, 3 + F,
 3 + 2F, ...: the reference's test for every divisor F >= 3; with F = 2 the reference would also fire at eval_step 1 (Python's -1 % 2 == 1),
 with F = 1 never.
+`--net VITs` trains fViT (ViTs_face_overlap: overlapping 12/8/4 window embedding, BatchNorm1d head, no landmark branch) in the released
+configuration instead of Part-fViT (`--net VIT_land_8`, the default): the reference's names (:324-326).
 Out of scope here: tensorboard, IJB evaluation.
 """
 import argparse
@@ -37,7 +39,7 @@ import torch
 import torch.distributed as dist
 
 from . import utils
-from .face_pre_pro.ViT_face import ViT_face_landmark_patch8
+from .face_pre_pro.ViT_face import ViT_face_landmark_patch8, ViTs_face_overlap
 from .finetune_engine import FinetuneEngine
 
 
@@ -48,6 +50,8 @@ def get_config(args):
 
 def get_args_parser():
     p = argparse.ArgumentParser("Part-fViT fine-tuning", add_help=False)
+    p.add_argument("--net", "-n", default="VIT_land_8", type=str, choices=["VIT_land_8", "VITs"],
+                   help="VIT_land_8: Part-fViT; VITs: fViT, the overlapping-patch face transformer with a BatchNorm1d head (reference :324-326)")
     p.add_argument("--batch_size", "-b", default=128, type=int)
     p.add_argument("--epochs", "-e", default=34, type=int)
     p.add_argument("--lr", default=1e-3, type=float, help="base rate before the reference's rescale (train_largescale.py:355,472)")
@@ -148,9 +152,25 @@ def get_time():
     return (str(datetime.now())[:-10]).replace(' ', '-').replace(':', '-')
 
 
+def check_net_args(args):
+    """An argument error for flags that have no meaning with the chosen --net."""
+    if args.net == "VITs" and (args.landmark_ckpt or args.pretrain_path):
+        raise SystemExit("error: --landmark_ckpt / --pretrain_path load a landmark CNN, which --net VITs does not have")
+
+
+def checkpoint_stem(args):
+    """Backbone_<this>_Epoch_... : 'VIT' for Part-fViT (as before), 'VITs' for fViT."""
+    return "VITs" if args.net == "VITs" else "VIT"
+
+
 def build_backbone(args):
     """The fine-tune model of the reference (:432, 542-557) for these flags."""
+    check_net_args(args)
     sharded = args.head == "PartialFC"
+    if args.net == "VITs":              # the released fViT configuration; --with_land is not read
+        return ViTs_face_overlap(loss_type="None" if sharded else "CosFace", GPU_ID=None, num_class=args.num_class, image_size=112,
+                                 patch_size=8, ac_patch_size=12, pad=4, dim=768, depth=12, heads=11, mlp_dim=2048,
+                                 dropout=args.dropout, emb_dropout=args.dropout, drop_path_rate=args.drop_path)
     # the dense ArcFace head lives in the same `loss.weight` tensor as CosFace (the reference names an ArcFace class it never
     # defines, ViT_face.py:654-655); the margin is applied by the fused kernel
     return ViT_face_landmark_patch8(loss_type="None" if sharded else "CosFace", GPU_ID=None, num_class=args.num_class,
@@ -319,10 +339,11 @@ def verify(args, evaluator, engine, vers, highest_acc, backbone, epoch, batch):
         acc.append(res[0])
     if main_proc and need_save(acc, highest_acc):
         torch.save({"module." + k: v for k, v in backbone.state_dict().items()},
-                   os.path.join(args.outdir, f"Backbone_VIT_Epoch_{epoch + 1}_Batch_{batch + 1}_Time_{get_time()}_checkpoint.pth"))
+                   os.path.join(args.outdir, f"Backbone_{checkpoint_stem(args)}_Epoch_{epoch + 1}_Batch_{batch + 1}_Time_{get_time()}_checkpoint.pth"))
 
 
 def main(args):
+    check_net_args(args)
     utils.init_distributed_mode(args)
     cfg = get_config(args)
     utils.fix_random_seeds(cfg["SEED"])
@@ -407,6 +428,6 @@ def main(args):
             batch += 1
         if utils.is_main_process():
             torch.save({"module." + k: v for k, v in backbone.state_dict().items()},
-                       os.path.join(args.outdir, f"Backbone_VIT_Epoch_{epoch + 1}.pth"))    # IJB loader expects 'module.' (IJB_evaluation.py:126)
+                       os.path.join(args.outdir, f"Backbone_{checkpoint_stem(args)}_Epoch_{epoch + 1}.pth"))    # IJB loader expects 'module.' (IJB_evaluation.py:126)
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -13,6 +13,9 @@ The pair counts with dist < t_k are prefix sums of that histogram, so every fold
 test, follow on the host without a pass over the pairs per threshold; `metrics_from_hist` then makes calculate_roc's choices with the
 same float operations (first maximum of the train accuracy, tpr / fpr = 0 on an empty class, np.mean over the folds).
 
+fViT (ViTs_face_overlap, `--net VITs`) takes the same path without a landmark plan or a mosaic: the window geometry of its overlapping
+embedding and, in the BatchNorm1d head, the running statistics (read, never written).
+
 The model is evaluated as the reference's backbone.eval() runs it (BatchNorm running statistics, Dropout and DropPath off) without
 touching the model's state: the CNN plan is rebuilt from the live weights and running statistics at every evaluation (the HIP training
 plan of landmark_train.py updates the module's own running_mean / running_var tensors in place), nothing is written to the parameter
@@ -182,7 +185,7 @@ def evaluate(hist, norm_sum, norm_count, thresholds=THRESHOLDS):
 def landmark_plan(model, device):
     """The frozen-CNN inference plan of the landmark branch, built from the live weights and running statistics (None without one)."""
     from .landmark_cnn import HipLandmarkCNN
-    return HipLandmarkCNN(model, device) if model.with_land else None
+    return HipLandmarkCNN(model, device) if getattr(model, "with_land", False) else None
 
 
 @torch.no_grad()
@@ -199,7 +202,8 @@ def extract_features(model, arena, x, n, cnn, mosaic, device):
         img = mosaic[: 2 * n]
         call("lafs_patch_gather_fwd", _p(x), _p(theta), 2 * n, S, n_full, _p(img))
     side = img.shape[-1]
-    geom = Fn.geometry([(2 * n, side)], device)
+    # (fViT: the overlapping embedding's window geometry; its BatchNorm1d head runs on the running statistics, bn_training=False)
+    geom = Fn.geometry([(2 * n, side)], device, window=model._spec.window if model._spec.overlapping else None)
     D = model._spec.trunk.dim
     pos = arena.view(arena.master, model._spec.prefix + model._spec.pos).view(-1, D)[: geom.npatch(0) + 1]
     feat, _, _ = Fn.vit_forward(arena, model._spec, geom, [img], [pos], None, save=False, dropout=None)
@@ -208,7 +212,7 @@ def extract_features(model, arena, x, n, cnn, mosaic, device):
 
 class VerificationEvaluator:
     def __init__(self, backbone, batch_size, device=None, norm="reference", n_folds=N_FOLDS):
-        """backbone: ViT_face_landmark_patch8 (with or without the landmark branch); batch_size: images per batch (even);
+        """backbone: ViT_face_landmark_patch8 (with or without the landmark branch) or ViTs_face_overlap; batch_size: images per batch (even);
         norm: 'reference' (x/255 - 0.5, utils.py:314) or 'train' (x/255*2 - 1, the fine-tune feed)."""
         if batch_size <= 0 or batch_size % 2:
             raise ValueError(f"the verification batch size must be even, got {batch_size}")
@@ -227,7 +231,7 @@ class VerificationEvaluator:
             dev, B = self.device, self.B
             self._bufs = dict(S=S, u8=torch.empty(B, 3, S, S, device=dev, dtype=torch.uint8),
                               x=torch.empty(2 * B, 3, S, S, device=dev, dtype=f32),
-                              mosaic=torch.empty(2 * B, 3, S, S, device=dev, dtype=f32) if self.model.with_land else None)
+                              mosaic=torch.empty(2 * B, 3, S, S, device=dev, dtype=f32) if getattr(self.model, "with_land", False) else None)
         return self._bufs
 
     def _landmark_plan(self):
@@ -297,7 +301,7 @@ def report(name, batch, result):
 def main(argv=None):
     """Accuracy of a saved fine-tune checkpoint (the `module.`-prefixed state dict train_largescale.py writes) without training."""
     from . import train_largescale as tl
-    p = argparse.ArgumentParser("Part-fViT verification", parents=[tl.get_args_parser()])
+    p = argparse.ArgumentParser("Part-fViT / fViT verification", parents=[tl.get_args_parser()])
     p.add_argument("--checkpoint", required=True, type=str)
     args = p.parse_args(argv)
     if not args.val_path:

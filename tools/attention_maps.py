@@ -3,13 +3,16 @@
 
   python tools/attention_maps.py --arch vit_small --checkpoint ckpt.pth --bin lfw.bin --out maps/
   python tools/attention_maps.py --arch partfvit --random-init --dims 128,2,3,256 --out maps/      (smoke run, synthetic batch)
+  python tools/attention_maps.py --arch fvit --checkpoint Backbone_VITs_Epoch_34.pth --bin lfw.bin --out maps/
 
 --arch vit_tiny / vit_small / vit_base: the DINO ViT with patch 8 (VisionTransformer.get_last_selfattention); the r x r patch grid
 is upsampled x8 to the image.  --arch partfvit: Part-fViT with its landmark branch (ViT_face_landmark_patch8.get_selfattention):
 every patch's weight is spread over its 8 x 8 footprint at the predicted landmark, overlapping coverage is averaged and the
 landmark centres are marked -- the picture the reference's visualize_attentionmap_DINO_landmark draws (util/utils.py:808-990).
+--arch fvit: fViT (ViTs_face_overlap.get_selfattention) with its 12/8/4 window embedding: one weight per window of the r x r grid
+(14 x 14 at 112 px), each spread over the 8 x 8 stride cell at the window's centre, i.e. upsampled x8 like the ViT's patch grid.
 
-Files: <out>/img<b>_head<h>.npy (f32: [r, r] for the ViT, [n] in landmark order for Part-fViT; plus img<b>_theta.npy [n, 2] pixels)
+Files: <out>/img<b>_head<h>.npy (f32: [r, r] for the ViT and fViT, [n] in landmark order for Part-fViT; plus img<b>_theta.npy [n, 2] pixels)
 and <out>/img<b>_head<h>.png.  The attention comes from the HIP read-out kernel; the drawing is host-side numpy + Pillow.
 """
 import argparse
@@ -24,14 +27,14 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 def get_args():
     p = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    p.add_argument("--arch", default="vit_small", choices=["vit_tiny", "vit_small", "vit_base", "partfvit"])
+    p.add_argument("--arch", default="vit_small", choices=["vit_tiny", "vit_small", "vit_base", "partfvit", "fvit"])
     p.add_argument("--dims", default="", help="dim,depth,heads,mlp: a smaller model than the architecture's (smoke runs)")
     p.add_argument("--checkpoint", default="", help="a state_dict, or a training checkpoint (its 'teacher' / 'state_dict' entry)")
     p.add_argument("--random-init", dest="random_init", action="store_true", help="no checkpoint: seeded random weights")
     p.add_argument("--bin", default="", help="verification set (.bin) to take the images from; default: a synthetic batch")
     p.add_argument("--num", default=2, type=int, help="number of images")
     p.add_argument("--image_size", default=112, type=int)
-    p.add_argument("--layer", default=-1, type=int, help="block to read (partfvit only; the ViT reads its last block)")
+    p.add_argument("--layer", default=-1, type=int, help="block to read (partfvit / fvit; the ViT reads its last block)")
     p.add_argument("--out", default="attention_maps")
     return p.parse_args()
 
@@ -39,12 +42,16 @@ def get_args():
 def build_model(args):
     from functools import partial
     from lafs_cvpr2024_amd import vision_transformer as vits
-    from lafs_cvpr2024_amd.face_pre_pro.ViT_face import ViT_face_landmark_patch8
+    from lafs_cvpr2024_amd.face_pre_pro.ViT_face import ViT_face_landmark_patch8, ViTs_face_overlap
     dims = [int(v) for v in args.dims.split(",")] if args.dims else None
     if args.arch == "partfvit":
         dim, depth, heads, mlp = dims or (768, 12, 11, 2048)
         return ViT_face_landmark_patch8(loss_type="None", GPU_ID=None, num_class=1, image_size=args.image_size, patch_size=8, dim=dim,
                                         depth=depth, heads=heads, mlp_dim=mlp, with_land=True)
+    if args.arch == "fvit":
+        dim, depth, heads, mlp = dims or (768, 12, 11, 2048)
+        return ViTs_face_overlap(loss_type="None", GPU_ID=None, num_class=1, image_size=args.image_size, patch_size=8, ac_patch_size=12,
+                                 pad=4, dim=dim, depth=depth, heads=heads, mlp_dim=mlp)
     if dims:
         dim, depth, heads, mlp = dims
         return vits.VisionTransformer(img_size=[args.image_size], patch_size=8, embed_dim=dim, depth=depth, num_heads=heads,
@@ -125,8 +132,13 @@ def main():
         cls = attn[:, :, 0, 1:].cpu().numpy()                      # [B, heads, n] in landmark order
         theta = theta.detach().float().cpu().numpy()
     else:
-        cls = model.get_last_selfattention(x)[:, :, 0, 1:].cpu().numpy()
-        r = S // 8
+        if args.arch == "fvit":
+            from lafs_cvpr2024_amd.vision_transformer import attach_arena
+            attach_arena(model)
+            cls = model.get_selfattention(x, layer=args.layer, cls_only=True)[:, :, 0, 1:].cpu().numpy()
+        else:
+            cls = model.get_last_selfattention(x)[:, :, 0, 1:].cpu().numpy()
+        r = int(round(cls.shape[-1] ** 0.5))                        # S // 8 for the ViT; nn.Unfold's window count per side for fViT
         cls = cls.reshape(cls.shape[0], cls.shape[1], r, r)
     os.makedirs(args.out, exist_ok=True)
     img = u8.numpy()
@@ -140,7 +152,10 @@ def main():
                 for px, py in np.clip(np.rint(theta[b]).astype(int), 0, S - 1):
                     pic[py, px] = 255                              # landmark centres
             else:
-                pic = overlay(img[b], np.kron(cls[b, h], np.ones((8, 8), np.float32)))
+                heat = np.full((S, S), np.nan, np.float32)         # (an fViT grid need not tile the image exactly: NaN = not covered)
+                up = np.kron(cls[b, h], np.ones((8, 8), np.float32))[:S, :S]
+                heat[:up.shape[0], :up.shape[1]] = up
+                pic = overlay(img[b], heat)
             Image.fromarray(pic).save(os.path.join(args.out, f"img{b}_head{h}.png"))
     print(f"wrote {cls.shape[0] * cls.shape[1]} maps ({cls.shape[0]} images x {cls.shape[1]} heads) to {args.out}")
 

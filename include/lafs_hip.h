@@ -424,6 +424,22 @@ int lafs_bn1d_fwd(const float* x, int ldx, int n, int D, const float* gamma, con
 int lafs_bn1d_bwd(const float* dy, int lddy, const float* x, int ldx, int n, int D, const float* save_mean, const float* save_rstd,
                   const float* gamma, int training, float* dx, int lddx, float* dgamma, float* dbeta, int accumulate,
                   hipStream_t stream);
+/* The same head over G crop groups of one packed pass (face_pre_pro/ViT_face.py:1530-1533,1556-1569: forward() runs the head once per
+ * run of equal-sided crops, in list order), one launch: group g is the rows [group_rows[g], group_rows[g + 1]) of x / y / dy / dx.
+ * group_rows is a HOST array of G + 1 ascending row numbers, group_rows[0] = 0, 1 <= G <= LAFS_BN1D_MAX_GROUPS; it is copied into the
+ * launch by value, so nothing is read from it after the call returns and the launch can be captured.  The result is bit for bit that
+ * of G lafs_bn1d_fwd / lafs_bn1d_bwd calls on the row ranges in group order (the same arithmetic, no atomics): every group has its own
+ * mean, biased variance and rstd (save_mean / save_rstd f32 [G, D], row g for group g); in training the running buffers take the
+ * (1 - momentum) old + momentum new update once per group, group 0 first, the unbiased variance with that group's own row count, and
+ * every group needs >= 2 rows; training == 0: every group is normalised with the running statistics, nothing is updated.
+ * Backward: dgamma / dbeta = (accumulate ? old : 0) + the groups' sums added in group order; dx per group as lafs_bn1d_bwd. */
+#define LAFS_BN1D_MAX_GROUPS 8
+int lafs_bn1d_groups_fwd(const float* x, int ldx, const int* group_rows, int G, int D, const float* gamma, const float* beta, float eps,
+                         float momentum, int training, float* running_mean, float* running_var, float* y, int ldy, float* save_mean,
+                         float* save_rstd, hipStream_t stream);
+int lafs_bn1d_groups_bwd(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, int G, int D, const float* save_mean,
+                         const float* save_rstd, const float* gamma, int training, float* dx, int lddx, float* dgamma, float* dbeta,
+                         int accumulate, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DINO head pieces  (vision_transformer.py:284-287, 299-300)

@@ -215,6 +215,8 @@ _PROTOS = {
     "lafs_add_cols_f32": [vp, i32, i32, i32, vp, i32, i32],
     "lafs_bn1d_fwd": [vp, i32, i32, i32, vp, vp, f32, f32, i32, vp, vp, vp, i32, vp, vp],
     "lafs_bn1d_bwd": [vp, i32, vp, i32, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, i32],
+    "lafs_bn1d_groups_fwd": [vp, i32, vp, i32, i32, vp, vp, f32, f32, i32, vp, vp, vp, i32, vp, vp],
+    "lafs_bn1d_groups_bwd": [vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, i32, vp, vp, i32],
 }
 _NO_STREAM = {
     "lafs_version": ([], i32),

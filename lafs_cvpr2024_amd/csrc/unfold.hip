@@ -108,15 +108,12 @@ __device__ __forceinline__ float bn_combine(float (*red)[64], float v, int w, in
   return s;
 }
 
-__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_fwd_kernel(const float* __restrict__ x, int ldx, int n, int D,
-                                                                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
-                                                                 float momentum, int training, float* __restrict__ running_mean,
-                                                                 float* __restrict__ running_var, float* __restrict__ y, int ldy,
-                                                                 float* __restrict__ save_mean, float* __restrict__ save_rstd) {
-  __shared__ float red[BN_WAVES][64];
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + lane;
-  const bool on = col < D;                                // (no early return: every lane reaches the barriers)
+// One group of rows through the forward: the whole arithmetic of lafs_bn1d_fwd, shared by the single-group kernel and the grouped
+// one so that the two give the same bits.  Every thread of the workgroup calls it (barriers inside); `on`: this lane has a column.
+__device__ __forceinline__ void bn_fwd_rows(float (*red)[64], const float* __restrict__ x, int ldx, int n, const float* __restrict__ gamma,
+                                            const float* __restrict__ beta, float eps, float momentum, int training,
+                                            float* __restrict__ running_mean, float* __restrict__ running_var, float* __restrict__ y, int ldy,
+                                            float* __restrict__ save_mean, float* __restrict__ save_rstd, int col, bool on, int w, int lane) {
   float mean = 0.f, rstd = 0.f;
   if (training) {
     const float x0 = on ? x[col] : 0.f;
@@ -143,16 +140,24 @@ __global__ __launch_bounds__(64 * BN_WAVES) void bn1d_fwd_kernel(const float* __
   for (int r = w; r < n; r += BN_WAVES) y[(size_t)r * ldy + col] = (x[(size_t)r * ldx + col] - mean) * rstd * g + bt;
 }
 
-// training: dx = gamma rstd (dy - mean(dy) - xhat mean(dy xhat));  eval (statistics are constants): dx = gamma rstd dy
-__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
-                                                                 int n, int D, const float* __restrict__ save_mean,
-                                                                 const float* __restrict__ save_rstd, const float* __restrict__ gamma,
-                                                                 int training, float* __restrict__ dx, int lddx, float* __restrict__ dgamma,
-                                                                 float* __restrict__ dbeta, int accumulate) {
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_fwd_kernel(const float* __restrict__ x, int ldx, int n, int D,
+                                                                 const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                                                 float momentum, int training, float* __restrict__ running_mean,
+                                                                 float* __restrict__ running_var, float* __restrict__ y, int ldy,
+                                                                 float* __restrict__ save_mean, float* __restrict__ save_rstd) {
   __shared__ float red[BN_WAVES][64];
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  const int col = blockIdx.x * 64 + lane;
-  const bool on = col < D;
+  const int col = blockIdx.x * 64 + lane;                 // (no early return: every lane reaches the barriers)
+  bn_fwd_rows(red, x, ldx, n, gamma, beta, eps, momentum, training, running_mean, running_var, y, ldy, save_mean, save_rstd, col, col < D,
+              w, lane);
+}
+
+// training: dx = gamma rstd (dy - mean(dy) - xhat mean(dy xhat));  eval (statistics are constants): dx = gamma rstd dy
+__device__ __forceinline__ void bn_bwd_rows(float (*red)[64], const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
+                                            int n, const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
+                                            const float* __restrict__ gamma, int training, float* __restrict__ dx, int lddx,
+                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate, int col, bool on, int w,
+                                            int lane) {
   const float mean = on ? save_mean[col] : 0.f, rstd = on ? save_rstd[col] : 0.f;
   float sb = 0.f, sg = 0.f;
   if (on)
@@ -173,6 +178,56 @@ __global__ __launch_bounds__(64 * BN_WAVES) void bn1d_bwd_kernel(const float* __
   for (int r = w; r < n; r += BN_WAVES) {
     const float xh = (x[(size_t)r * ldx + col] - mean) * rstd;
     dx[(size_t)r * lddx + col] = gr * (dy[(size_t)r * lddy + col] - mb - xh * mg);
+  }
+}
+
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
+                                                                 int n, int D, const float* __restrict__ save_mean,
+                                                                 const float* __restrict__ save_rstd, const float* __restrict__ gamma,
+                                                                 int training, float* __restrict__ dx, int lddx, float* __restrict__ dgamma,
+                                                                 float* __restrict__ dbeta, int accumulate) {
+  __shared__ float red[BN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  bn_bwd_rows(red, dy, lddy, x, ldx, n, save_mean, save_rstd, gamma, training, dx, lddx, dgamma, dbeta, accumulate, col, col < D, w, lane);
+}
+
+// ---- The same over G row ranges [rows[g], rows[g + 1]) of one packed buffer (a crop group each: reference :1556-1569 runs the head once
+// per group, in list order).  One workgroup per 64 columns walks the groups in order, so what is ordered -- the running buffers' chain
+// of (1 - m) old + m new updates, dgamma / dbeta summed group by group -- is read and written by the same thread (wave 0's lane of the
+// column) in program order: one launch, the bits of G single-group launches.  The row table travels in the kernel arguments.
+struct BnGroupRows { int rows[LAFS_BN1D_MAX_GROUPS + 1]; };
+
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_groups_fwd_kernel(const float* __restrict__ x, int ldx, BnGroupRows gr, int G, int D,
+                                                                        const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                        float eps, float momentum, int training,
+                                                                        float* __restrict__ running_mean, float* __restrict__ running_var,
+                                                                        float* __restrict__ y, int ldy, float* __restrict__ save_mean,
+                                                                        float* __restrict__ save_rstd) {
+  __shared__ float red[BN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  for (int g = 0; g < G; ++g) {
+    const int r0 = gr.rows[g];
+    bn_fwd_rows(red, x + (size_t)r0 * ldx, ldx, gr.rows[g + 1] - r0, gamma, beta, eps, momentum, training, running_mean, running_var,
+                y + (size_t)r0 * ldy, ldy, save_mean + (size_t)g * D, save_rstd + (size_t)g * D, col, col < D, w, lane);
+  }
+}
+
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_groups_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x,
+                                                                        int ldx, BnGroupRows gr, int G, int D,
+                                                                        const float* __restrict__ save_mean,
+                                                                        const float* __restrict__ save_rstd, const float* __restrict__ gamma,
+                                                                        int training, float* __restrict__ dx, int lddx,
+                                                                        float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
+  __shared__ float red[BN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  for (int g = 0; g < G; ++g) {
+    const int r0 = gr.rows[g];
+    bn_bwd_rows(red, dy + (size_t)r0 * lddy, lddy, x + (size_t)r0 * ldx, ldx, gr.rows[g + 1] - r0, save_mean + (size_t)g * D,
+                save_rstd + (size_t)g * D, gamma, training, dx + (size_t)r0 * lddx, lddx, dgamma, dbeta, (g > 0 || accumulate) ? 1 : 0, col,
+                col < D, w, lane);
   }
 }
 
@@ -253,6 +308,51 @@ extern "C" int lafs_bn1d_bwd(const float* dy, int lddy, const float* x, int ldx,
   LAFS_CHECK_ARG(!training || n >= 2, "batch statistics need more than one row");
   hipLaunchKernelGGL(bn1d_bwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, dy, lddy, x, ldx, n, D, save_mean, save_rstd,
                      gamma, training ? 1 : 0, dx, lddx, dgamma, dbeta, accumulate ? 1 : 0);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+// validates the host row table and copies it into the launch argument; the reason of a refusal, or nullptr
+static const char* bn_group_rows(const int* group_rows, int G, int training, BnGroupRows* out) {
+  if (group_rows == nullptr) return "null operand";
+  if (G < 1 || G > LAFS_BN1D_MAX_GROUPS) return "1 <= G <= LAFS_BN1D_MAX_GROUPS";
+  if (group_rows[0] != 0) return "group_rows[0] must be 0";
+  for (int g = 0; g < G; ++g) {
+    if (group_rows[g + 1] <= group_rows[g]) return "group_rows must ascend strictly (no empty group)";
+    if (training && group_rows[g + 1] - group_rows[g] < 2) return "batch statistics need more than one row in every group";
+  }
+  for (int g = 0; g <= LAFS_BN1D_MAX_GROUPS; ++g) out->rows[g] = g <= G ? group_rows[g] : group_rows[G];
+  return nullptr;
+}
+
+extern "C" int lafs_bn1d_groups_fwd(const float* x, int ldx, const int* group_rows, int G, int D, const float* gamma, const float* beta,
+                                    float eps, float momentum, int training, float* running_mean, float* running_var, float* y, int ldy,
+                                    float* save_mean, float* save_rstd, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(x && gamma && beta && y && save_mean && save_rstd, "null operand");
+  LAFS_CHECK_ARG(D > 0 && D <= 2048 && ldx >= D && ldy >= D, "1 <= D <= 2048 and row strides >= D");
+  BnGroupRows gr;
+  const char* why = bn_group_rows(group_rows, G, training, &gr);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  LAFS_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "running_mean and running_var come together");
+  LAFS_CHECK_ARG(training || running_mean != nullptr, "the eval forward normalises with the running statistics");
+  hipLaunchKernelGGL(bn1d_groups_fwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, x, ldx, gr, G, D, gamma, beta, eps,
+                     momentum, training ? 1 : 0, running_mean, running_var, y, ldy, save_mean, save_rstd);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_bn1d_groups_bwd(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, int G, int D,
+                                    const float* save_mean, const float* save_rstd, const float* gamma, int training, float* dx, int lddx,
+                                    float* dgamma, float* dbeta, int accumulate, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(dy && x && save_mean && save_rstd && gamma && dx && dgamma && dbeta, "null operand");
+  LAFS_CHECK_ARG(D > 0 && D <= 2048 && lddy >= D && ldx >= D && lddx >= D, "1 <= D <= 2048 and row strides >= D");
+  BnGroupRows gr;
+  const char* why = bn_group_rows(group_rows, G, training, &gr);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  hipLaunchKernelGGL(bn1d_groups_bwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, dy, lddy, x, ldx, gr, G, D, save_mean,
+                     save_rstd, gamma, training ? 1 : 0, dx, lddx, dgamma, dbeta, accumulate ? 1 : 0);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }

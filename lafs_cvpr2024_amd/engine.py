@@ -28,6 +28,17 @@ def _is_partfvit(m):
     from .face_pre_pro.ViT_face import ViT_face_landmark_patch8
     return isinstance(m, ViT_face_landmark_patch8)
 
+
+def _is_fvit(m):
+    from .face_pre_pro.ViT_face import ViTs_face_overlap
+    return isinstance(m, ViTs_face_overlap)
+
+
+# The reference converts both networks to SyncBatchNorm before it wraps them (lafs_train.py:362-364): fViT's BatchNorm1d head then
+# normalises with the statistics of the cls rows of ALL ranks.  lafs_bn1d_groups_fwd sees one rank's rows.
+FVIT_MULTI_RANK = ("fViT pre-training on more than one rank needs SyncBatchNorm statistics across the ranks (reference "
+                   "lafs_train.py:362-364), which are not implemented: run --arch fvit on a single rank")
+
 f32, bf16 = torch.float32, torch.bfloat16
 
 
@@ -56,9 +67,20 @@ class LafsPretrainEngine:
         # ViT_face_landmark_patch8 -- the pair the reference actually pre-trains (lafs_train.py:300-335, arch 'mynet'): landmark
         # mosaics as [B, n, 192] patch tokens, position table sliced to n+1 rows, DropPath 0.1 + dropout 0.1 live in the student
         # AND the teacher (the reference never calls teacher.eval()).
+        # fViT (ViTs_face_overlap) is the Part-fViT transformer behind an overlapping window embedding and with a BatchNorm1d head on
+        # the cls rows: it shares every `facevit` choice below (sliced position table, constant DropPath, live dropout in both
+        # networks); its own are the window geometry and the head, whose batch statistics and running-statistic updates are per crop
+        # group (lafs_bn1d_groups_fwd) in BOTH networks -- the reference never calls teacher.eval() (lafs_train.py: no .eval() but :269),
+        # so the teacher normalises its 2B global rows with batch statistics and updates its own running buffers.
         self.partfvit = _is_partfvit(vit_s)
-        if not (isinstance(vit_s, VisionTransformer) or self.partfvit) or type(vit_s) is not type(vit_t):
-            raise _lib.LafsHipError("LafsPretrainEngine drives a VisionTransformer or a ViT_face_landmark_patch8 pair")
+        self.fvit = _is_fvit(vit_s)
+        self.facevit = self.partfvit or self.fvit
+        if not (isinstance(vit_s, VisionTransformer) or self.facevit) or type(vit_s) is not type(vit_t):
+            raise _lib.LafsHipError("LafsPretrainEngine drives a VisionTransformer, a ViT_face_landmark_patch8 or a ViTs_face_overlap pair")
+        if self.fvit and self.world > 1:
+            raise _lib.LafsHipError(FVIT_MULTI_RANK)
+        if self.fvit and (vit_s.ac_patch_size, vit_s.patch_size, vit_s.pad) != (vit_t.ac_patch_size, vit_t.patch_size, vit_t.pad):
+            raise _lib.LafsHipError("student and teacher fViT must embed with the same window")
         if self.partfvit and (vit_s.with_land or vit_t.with_land):
             raise _lib.LafsHipError("LAFS pre-training uses with_land=False backbones (the landmark CNN is the frozen front-end)")
         self.sa = attach_arena(student, self.device)
@@ -68,7 +90,8 @@ class LafsPretrainEngine:
         # The row chains (long / short sequences on two streams) pay on the ViT-S trunk, whose K = 384 kernels leave CUs idle; the
         # Part-fViT trunk's wide GEMMs run on one-workgroup-per-CU persistent tiles (gemm_big.hip) that want the whole chip and the
         # merged 44 160 rows (753 tiles of 176x256 = 2.94 rounds): `mynet` pair 36.1 ms with two chains, 35.4-35.5 with one.
-        if self.partfvit and "LAFS_ROW_CHAINS" not in os.environ:
+        # fViT runs the same wide trunk and follows that default; the choice has not been measured for fViT.
+        if self.facevit and "LAFS_ROW_CHAINS" not in os.environ:
             self.ctx.set(_lib.OPT_ROW_CHAINS, 1)
         self.ta = getattr(teacher, "_lafs_arena", None)
         if self.ta is None:
@@ -79,6 +102,8 @@ class LafsPretrainEngine:
             for name, m in teacher.named_modules():
                 if hasattr(m, "_bind_arena"):
                     m._bind_arena(self.ta, name + "." if name else "")
+        for b in teacher.buffers():                  # (fViT's running statistics: the kernels update them in place)
+            b.data = b.data.to(self.device)
         if self.sa.names != self.ta.names or self.sa.size != self.ta.size:
             raise _lib.LafsHipError("student and teacher must have identical parameter layouts")
         self.sa.ctx = self.ta.ctx = self.ctx
@@ -89,14 +114,21 @@ class LafsPretrainEngine:
             self.sa.refresh_shadows(); self.ta.refresh_shadows()
         self.K = student.head.out_dim
         self.Kpad = (self.K + 127) // 128 * 128
-        B, D = batch_size, (vit_s.dim if self.partfvit else vit_s.embed_dim)
-        self.geom_s = Fn.geometry([(2 * B, global_size), (n_local * B, local_size)] if n_local else [(2 * B, global_size)], self.device)
-        self.geom_t = Fn.geometry([(2 * B, global_size)], self.device)
+        B, D = batch_size, (vit_s.dim if self.facevit else vit_s.embed_dim)
+        window = (vit_s.ac_patch_size, vit_s.patch_size, vit_s.pad) if self.fvit else None      # nn.Unfold(k, stride, padding)
+        self.geom_s = Fn.geometry([(2 * B, global_size), (n_local * B, local_size)] if n_local else [(2 * B, global_size)], self.device,
+                                  window=window)
+        self.geom_t = Fn.geometry([(2 * B, global_size)], self.device, window=window)
         self.spec_s, self.spec_t = vit_s._spec, vit_t._spec
         self.head_prefix_s, self.head_prefix_t = student.head._prefix, teacher.head._prefix
         # bicubic resampling matrices for the stored position table (Part-fViT: plain slices, no resampling)
         self.grids = [global_size // 8] + ([local_size // 8] if n_local else [])
-        if self.partfvit:
+        if self.fvit:                                # windows per side: 14 and 6 for 112 / 48 px at 12 / 8 / 4
+            self.grids = [ops.unfold_windows(s, *window) for s in [global_size] + ([local_size] if n_local else [])]
+            if self.B < 2:
+                raise _lib.LafsHipError("fViT's BatchNorm1d head needs more than one row per crop group: batch_size >= 2")
+            self.bn_s, self.bn_t = vit_s.mlp_head[0], vit_t.mlp_head[0]
+        if self.facevit:
             if vit_s.num_patches < self.grids[0] ** 2:
                 raise _lib.LafsHipError("pos_embedding is shorter than the global crops' token count")
             self.interp = [None for _ in self.grids]
@@ -107,7 +139,7 @@ class LafsPretrainEngine:
         # whose seed is (network seed + 7919 * hyper[HP_STEP]), the step read on the DEVICE inside the kernels exactly as the
         # DropPath draw reads it -- a captured graph draws new masks on every replay, and the masks are indexed by absolute token
         # rows, so the row chains stay legal
-        self.has_dropout = self.partfvit and (vit_s.dropout_rate > 0 or vit_s.emb_dropout_rate > 0 or
+        self.has_dropout = self.facevit and (vit_s.dropout_rate > 0 or vit_s.emb_dropout_rate > 0 or
                                               vit_t.dropout_rate > 0 or vit_t.emb_dropout_rate > 0)
         self.dropout_seed_s, self.dropout_seed_t = 0x5EED, 0x7EAC4E5       # independent masks in the two networks
         # static buffers
@@ -138,7 +170,7 @@ class LafsPretrainEngine:
         # DropPath scales are drawn by lafs_droppath_scales from (seed, hyper[HP_STEP]): new masks on every graph replay without
         # an ATen RNG kernel; keep probabilities per block on the device, None when every rate is 0
         def keep_probs(v):
-            rates = [v.drop_path_rate] * v.depth if self.partfvit else list(v.drop_path_rates)
+            rates = [v.drop_path_rate] * v.depth if self.facevit else list(v.drop_path_rates)
             return torch.tensor([1.0 - r for r in rates], device=dev, dtype=f32) if any(rates) else None
         self.keep_s, self.keep_t = keep_probs(vit_s), keep_probs(vit_t)
         self.drop_s = torch.empty(vit_s.depth, 2, self.geom_s.n_seq, device=dev, dtype=f32)
@@ -225,8 +257,8 @@ class LafsPretrainEngine:
         pe = arena.view(arena.master, spec.prefix + spec.pos).view(-1, spec.trunk.dim)
         out = []
         for M, r, buf in zip(self.interp, self.grids, bufs):
-            if self.partfvit:
-                out.append(pe[:r * r + 1])                 # pos_embedding[:, :n+1] (reference ViT_face.py:766)
+            if self.facevit:
+                out.append(pe[:r * r + 1])                 # pos_embedding[:, :n+1] (reference ViT_face.py:766, fViT :1590)
             elif M is None:
                 out.append(pe)
             else:                                          # bicubic resampling as its fixed linear map, one small launch
@@ -256,7 +288,7 @@ class LafsPretrainEngine:
 
     def _dropout_cfg(self, vit, seed):
         """(p_trunk, p_embedding, seed, device step counter) of a Part-fViT network in training mode, else None."""
-        if not self.partfvit or not vit.training or (vit.dropout_rate == 0.0 and vit.emb_dropout_rate == 0.0):
+        if not self.facevit or not vit.training or (vit.dropout_rate == 0.0 and vit.emb_dropout_rate == 0.0):
             return None
         return (vit.dropout_rate, vit.emb_dropout_rate, seed, self.hyper[_lib.HP_STEP:])
 
@@ -274,7 +306,10 @@ class LafsPretrainEngine:
             vit_t = self.teacher.backbone
             drop_t = self._drop_scales(self.keep_t, self.drop_t, 1) if vit_t.training else None   # rate 0 for the DINO ViT teacher
             dd_t = self._dropout_cfg(vit_t, self.dropout_seed_t)
-            feat_t, _, _ = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False, dropout=dd_t)
+            feat_t, _, _ = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False, dropout=dd_t,
+                                          bn_training=vit_t.training)
+            if self.fvit and vit_t.training:           # one forward of one group (device add: no host sync, capturable)
+                self.bn_t.num_batches_tracked.add_(1)
             _, st_ht = Fn.head_forward(ta, self.head_prefix_t, feat_t, self.K, save=False, logits=self._logits_t, skip_logits=self.fused_head)
         # student: all views in one packed pass
         vit = self.student.backbone
@@ -283,7 +318,10 @@ class LafsPretrainEngine:
         dd_s = self._dropout_cfg(vit, self.dropout_seed_s)
         feat_s, st_v, _ = Fn.vit_forward(sa, self.spec_s, self.geom_s, imgs, self._pos_tokens(sa, self.spec_s, self.pos_s), drop,
                                          save=True, dropout=dd_s, wgrad_overwrite=True,
-                                         wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0)
+                                         wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0,
+                                         bn_training=vit.training)
+        if self.fvit and vit.training:                 # the reference's forward runs the head once per crop group (:1556-1569)
+            self.bn_s.num_batches_tracked.add_(len(self.geom_s.groups))
         _, st_h = Fn.head_forward(sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)
         cur.wait_stream(side)
         if self.fused_head:
@@ -313,7 +351,7 @@ class LafsPretrainEngine:
             gpe = sa.view(sa.grad, self.spec_s.prefix + self.pos_name).view(-1, self.spec_s.trunk.dim)
             # a table that is used as stored (Part-fViT slices, or a crop size equal to the table's grid) takes its gradient rows
             # directly; a resampled one goes through the transposed interpolation map
-            direct = [gpe[:r * r + 1] if (self.partfvit or M is None) else None for M, r in zip(self.interp, self.grids)]
+            direct = [gpe[:r * r + 1] if (self.facevit or M is None) else None for M, r in zip(self.interp, self.grids)]
             dpos = Fn.vit_backward_end(sa, self.spec_s, self._st["vit"], self._st["g"], dpos_out=direct)
             for M, dp, dr in zip(self.interp, dpos, direct):
                 if dr is None:
@@ -461,16 +499,20 @@ class LafsPretrainEngine:
             runs.append((cur, hi))
         return runs
 
-    # warm-up/capture executes real optimisation steps on whatever is in the buffers: snapshot and restore the state
-    def _snapshot(self):
+    # warm-up/capture executes real optimisation steps on whatever is in the buffers: snapshot and restore the state -- fViT's
+    # BatchNorm buffers (running_mean, running_var, num_batches_tracked of both networks) included, which those passes update
+    def _state_tensors(self):
         sa, ta = self.sa, self.ta
-        return [t.clone() for t in (sa.master, sa.exp_avg, sa.exp_avg_sq, sa.seg_step, ta.master, self.dino_loss.center)], \
-            torch.cuda.get_rng_state(self.device)
+        bn = [b for m in ((self.bn_s, self.bn_t) if self.fvit else ()) for b in (m.running_mean, m.running_var, m.num_batches_tracked)]
+        return [sa.master, sa.exp_avg, sa.exp_avg_sq, sa.seg_step, ta.master, self.dino_loss.center] + bn
+
+    def _snapshot(self):
+        return [t.clone() for t in self._state_tensors()], torch.cuda.get_rng_state(self.device)
 
     def _restore(self, saved):
         tensors, rng = saved
         sa, ta = self.sa, self.ta
-        for dst, src in zip((sa.master, sa.exp_avg, sa.exp_avg_sq, sa.seg_step, ta.master, self.dino_loss.center), tensors):
+        for dst, src in zip(self._state_tensors(), tensors):
             dst.copy_(src)
         sa.refresh_shadows()
         ta.refresh_shadows()

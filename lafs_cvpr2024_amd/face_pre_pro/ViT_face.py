@@ -422,12 +422,38 @@ class _FViTFunction(torch.autograd.Function):
         return None, None, dx[0], dpos[0], None
 
 
+class _FViTGroupsFunction(torch.autograd.Function):
+    """Several crop groups of fViT in ONE packed pass as one autograd node; the BatchNorm1d head keeps per-group statistics
+    (lafs_bn1d_groups_fwd / _bwd).  Inputs behind the hook: the groups' images, then their position slices."""
+
+    @staticmethod
+    def forward(ctx, model, n_groups, hook, geom, *tensors):
+        imgs, pos = tensors[:n_groups], tensors[n_groups:]
+        save = any(ctx.needs_input_grad)
+        drop = model._sample_drop_scales(geom) if model.training else None
+        feat, st, _ = Fn.vit_forward(model._arena, model._spec, geom, [x.contiguous().float() for x in imgs],
+                                     [p.detach().contiguous() for p in pos], drop, save=save, dropout=model._next_dropout(),
+                                     bn_training=model.training)
+        ctx.model, ctx.st, ctx.n_groups = model, (st if save else None), n_groups
+        return feat
+
+    @staticmethod
+    def backward(ctx, dfeat):
+        model, st, G = ctx.model, ctx.st, ctx.n_groups
+        if not any(ctx.needs_input_grad[4:4 + G]):
+            dpos = Fn.vit_backward(model._arena, model._spec, st, dfeat)
+            return (None,) * (4 + G) + tuple(dpos)
+        dpos, dx = Fn.vit_backward(model._arena, model._spec, st, dfeat, want_dx=True)
+        return (None,) * 4 + tuple(d if need else None for d, need in zip(dx, ctx.needs_input_grad[4:4 + G])) + tuple(dpos)
+
+
 class ViTs_face_overlap(nn.Module):
     """fViT (reference face_pre_pro/ViT_face.py:1506-1613): the Part-fViT transformer (pre-LN, bias-free qkv, scale dim**-0.5,
     ``heads * 64`` inner width, DropPath on every residual branch) behind an OVERLAPPING patch embedding -- nn.Unfold(ac_patch_size,
     stride patch_size, padding pad) + Linear, one lafs_unfold_bf16 launch + the embedding GEMM here -- and with a BatchNorm1d head on the
     cls rows (lafs_bn1d_fwd / lafs_bn1d_bwd).  4-D images or 3-D [B, n, 3 * ac_patch_size**2] window vectors; a list of crops runs
     one pass per run of equal-sided crops, so the batch statistics and the running-statistic updates are per group, in list order.
+    ``forward_groups`` runs already concatenated groups as ONE packed pass with the same per-group statistics (lafs_bn1d_groups_fwd).
     ``soft_split``, ``dropout`` and ``to_latent`` are kept as attributes for parity and never called; ``fc``, whose result the
     reference discards (:1606-1607), is ignored.  ``drop_path_rate``: the reference hard-codes 0.1 in Residual_droppath.
     ``loss_type='CosFace'`` builds the margin head the reference left commented out (:1539-1549; key ``loss.weight``, as in Part-fViT), which
@@ -515,6 +541,26 @@ class ViTs_face_overlap(nn.Module):
 
     def forward_head(self, x):
         return self.pred(x) if self.pred is not None else x
+
+    def forward_groups(self, groups):
+        """Already concatenated crop groups (one tensor per resolution) in ONE packed pass -> BatchNorm1d(cls) f32 [sum B, dim], the
+        rows in group order.  What ``forward(list)`` gives by running the groups one after the other (reference :1556-1569): the
+        BatchNorm statistics are per group and the running buffers are updated once per group, in list order
+        (lafs_bn1d_groups_fwd); the trunk runs once over all tokens.  MultiCropWrapper.forward takes this pass."""
+        if len(groups) == 1:
+            return self.forward_features(groups[0])
+        if len(groups) > 4:
+            raise NotImplementedError("the packed trunk runs at most 4 crop resolutions in one pass")
+        shapes = [self._window_geometry(img) for img in groups]
+        if self.training and min(n_img for n_img, _, _ in shapes) < 2:
+            raise ValueError("Expected more than 1 value per channel when training (a crop group of one image)")
+        geom = Fn.geometry([(n_img, side) for n_img, side, _ in shapes], groups[0].device,
+                           window=(self.ac_patch_size, self.patch_size, self.pad))
+        pos = [self.pos_embedding[0, :n + 1] for _, _, n in shapes]
+        emb = _FViTGroupsFunction.apply(self, len(groups), self._hook, geom, *groups, *pos)
+        if self.training:
+            self.mlp_head[0].num_batches_tracked += len(groups)
+        return emb
 
     def forward_features(self, img, label=None, mask=None, patch_drop=None):
         """(reference :1578-1613)  One group: [B, 3, S, S] images or [B, n, 3 k^2] window vectors -> BatchNorm1d(cls) f32 [B, dim].

@@ -163,6 +163,11 @@ class ViTState:
 EMB_DROP_SITE = 0x40000000          # seed offset of the embedding dropout (the trunk sites use seed + 3*layer + {0,1,2})
 
 
+def bn_group_rows(geom: PackedGeometry):
+    """Row table of the grouped BatchNorm1d head: the cls rows of crop group g are [rows[g], rows[g + 1]) of the gathered [n_seq, D]."""
+    return list(geom.seq_start) + [geom.n_seq]
+
+
 def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, drop_scales=None, save=True,
                 ws=None, x_in=None, x_out=None, dropout=None, wgrad_overwrite=False, wgrad_workgroups=0, wgrad_defer=False,
                 bn_training=False):
@@ -221,11 +226,13 @@ def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, dr
     call("lafs_gather_cls", _p(x_out), D, _p(geom.cu_seqlens), geom.n_seq, D, _p(st.cls_rows))
     st.bn_training = bool(bn_training)
     if spec.head == "batchnorm":
-        if len(geom.groups) != 1:                         # (the statistics are per crop resolution: reference :1561-1563)
-            raise _lib.LafsHipError("the BatchNorm1d head takes one crop resolution per pass (its batch statistics are per group)")
         rm, rv = arena.module.get_buffer(pre + spec.bn_mean), arena.module.get_buffer(pre + spec.bn_var)
-        feat, mean, rstd = ops.bn1d_fwd(st.cls_rows, arena.view(arena.master, pre + spec.final_g),
-                                        arena.view(arena.master, pre + spec.final_b), spec.bn_eps, spec.bn_momentum, st.bn_training, rm, rv)
+        bn_g, bn_b = arena.view(arena.master, pre + spec.final_g), arena.view(arena.master, pre + spec.final_b)
+        if len(geom.groups) == 1:
+            feat, mean, rstd = ops.bn1d_fwd(st.cls_rows, bn_g, bn_b, spec.bn_eps, spec.bn_momentum, st.bn_training, rm, rv)
+        else:                                             # the statistics and the running-statistic updates are per crop group, in
+            feat, mean, rstd = ops.bn1d_groups_fwd(st.cls_rows, bn_group_rows(geom), bn_g, bn_b, spec.bn_eps, spec.bn_momentum,
+                                                   st.bn_training, rm, rv)       # list order (reference :1556-1569); stats [G, D]
         st.stats = (mean, rstd)
     elif spec.head == "layernorm":
         _, feat, st.stats = ops.layernorm_fwd(st.cls_rows, arena.view(arena.master, pre + spec.final_g),
@@ -296,7 +303,11 @@ def vit_backward_begin(arena, spec: ViTSpec, st: ViTState, dfeat, g_buf=None):
     geom, D, pre = st.geom, spec.trunk.dim, spec.prefix
     dev = dfeat.device
     gv = lambda n: arena.view(arena.grad, pre + n)
-    if spec.head == "batchnorm":
+    if spec.head == "batchnorm" and len(geom.groups) > 1:
+        dcls_rows = ops.bn1d_groups_bwd(dfeat.contiguous().float(), st.cls_rows, bn_group_rows(geom), st.stats[0], st.stats[1],
+                                        arena.view(arena.master, pre + spec.final_g), st.bn_training, gv(spec.final_g), gv(spec.final_b),
+                                        accumulate=True)
+    elif spec.head == "batchnorm":
         dcls_rows = ops.bn1d_bwd(dfeat.contiguous().float(), st.cls_rows, st.stats[0], st.stats[1], arena.view(arena.master, pre + spec.final_g),
                                  st.bn_training, gv(spec.final_g), gv(spec.final_b), accumulate=True)
     else:

@@ -12,6 +12,8 @@ Differences from the reference, all forced by its own breakage or by scope (SURV
   * the data pipeline (MXNet recordio + PIL augmentations + landmark CNN) is out of scope: `--data synthetic` feeds the
     crop shapes the landmark gather emits (2 x 112^2 + n x 48^2), or pass any Dataset through `train_lafs(args, dataset=...)`
     yielding lists of 2 + n crops;
+  * --arch fvit pre-trains ViTs_face_overlap (the overlapping-patch fViT with its BatchNorm1d head; --fvit_dims, --fvit_window,
+    --fvit_dropout), single rank only: the reference's SyncBatchNorm conversion (:362-364) has no counterpart here;
   * the optimizer is the engine's fused per-tensor-clip + AdamW (the reference's default and only used one).
 """
 import argparse
@@ -42,7 +44,7 @@ FP16_SCALER_STATE = {"scale": 65536.0, "growth_factor": 2.0, "backoff_factor": 0
 
 def get_args_parser():
     p = argparse.ArgumentParser('LAFS', add_help=False)
-    p.add_argument('--arch', default='mynet', type=str, choices=['mynet', 'vit_tiny', 'vit_small', 'vit_base'])
+    p.add_argument('--arch', default='mynet', type=str, choices=['mynet', 'fvit', 'vit_tiny', 'vit_small', 'vit_base'])
     p.add_argument('--patch_size', default=8, type=int)
     p.add_argument('--out_dim', default=100000, type=int)
     p.add_argument('--norm_last_layer', default=True, type=utils.bool_flag)
@@ -66,6 +68,10 @@ def get_args_parser():
     p.add_argument('--drop_path_rate', type=float, default=0.1)
     p.add_argument('--mynet_dims', default='768,12,11,2048', type=str, help="dim,depth,heads,mlp_dim of --arch mynet (reference :300-335)")
     p.add_argument('--mynet_dropout', default=0.1, type=float, help="dropout = emb_dropout of --arch mynet (reference: 0.1)")
+    p.add_argument('--fvit_dims', default='768,12,11,2048', type=str, help="dim,depth,heads,mlp_dim of --arch fvit (ViTs_face_overlap)")
+    p.add_argument('--fvit_window', default='12,8,4', type=str,
+                   help="k,stride,pad of fViT's overlapping patch embedding: nn.Unfold(kernel_size=k, stride, padding=pad)")
+    p.add_argument('--fvit_dropout', default=0.1, type=float, help="dropout = emb_dropout of --arch fvit")
     p.add_argument('--local_crops_number', type=int, default=8)
     p.add_argument('--data', default='synthetic', type=str,
                    help="'synthetic': random landmark-crop shaped tensors; 'synthetic_views': the 20 augmented 112x112 views of "
@@ -209,6 +215,17 @@ def build_backbones(args):
     """(student backbone, teacher backbone, embed_dim).  'mynet' = the reference's hard-coded Part-fViT pair
     (lafs_train.py:300-335): both networks with dropout / emb_dropout 0.1 and Residual_droppath 0.1, and neither is ever put in
     eval mode, so the teacher is stochastic too.  `--mynet_dims dim,depth,heads,mlp` shrinks it for smoke runs."""
+    if args.arch == 'fvit':
+        # fViT (reference face_pre_pro/ViT_face.py:1506-1613) with the released key set: no margin table.  Both networks get the same
+        # DropPath rate (the reference class hard-codes 0.1 in both) and neither is put in eval mode, so both BatchNorm heads run on
+        # batch statistics.  The teacher checkpoint is what train_largescale.py --net VITs --model_dir loads.
+        from .face_pre_pro.ViT_face import ViTs_face_overlap
+        dim, depth, heads, mlp = (int(v) for v in args.fvit_dims.split(","))
+        k, stride, pad = (int(v) for v in args.fvit_window.split(","))
+        mk = lambda: ViTs_face_overlap(loss_type='None', GPU_ID=None, num_class=10, image_size=112, patch_size=stride, ac_patch_size=k,
+                                       pad=pad, dim=dim, depth=depth, heads=heads, mlp_dim=mlp, dropout=args.fvit_dropout,
+                                       emb_dropout=args.fvit_dropout, drop_path_rate=args.drop_path_rate)
+        return mk(), mk(), dim
     if args.arch != 'mynet':
         sb = vits.__dict__[args.arch](patch_size=args.patch_size, drop_path_rate=args.drop_path_rate)
         tb = vits.__dict__[args.arch](patch_size=args.patch_size)
@@ -235,6 +252,10 @@ def train_lafs(args, dataset=None):
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     device = torch.device("cuda", args.gpu)
     world = utils.get_world_size()
+    if args.arch == 'fvit' and world > 1:                 # (before anything is built: the engine would refuse the pair anyway)
+        from .engine import FVIT_MULTI_RANK
+        print(FVIT_MULTI_RANK, file=sys.stderr)
+        sys.exit(FVIT_MULTI_RANK)
 
     # ---- student / teacher: MultiCropWrapper(backbone, DINOHead), as reference lafs_train.py:200-356 ----
     student_b, teacher_b, embed_dim = build_backbones(args)

@@ -388,6 +388,51 @@ def bn1d_bwd(dy, x, mean, rstd, gamma, training, dgamma, dbeta, accumulate=True)
     return dx
 
 
+def _group_rows(group_rows):
+    """Host row table of the grouped BatchNorm entry points as a C int array (the entry point validates it)."""
+    rows = [int(r) for r in group_rows]
+    return (C.c_int * max(len(rows), 1))(*rows), len(rows) - 1
+
+
+def bn1d_groups_fwd(x, group_rows, gamma, beta, eps, momentum, training, running_mean, running_var, out=None):
+    """nn.BatchNorm1d on each row range [group_rows[g], group_rows[g + 1]) of f32 [n, D], in group order, one launch
+    (lafs_bn1d_groups_fwd).  Returns (y, save_mean [G, D], save_rstd [G, D]); training updates the running buffers once per group.
+    out: f32 [n, D] view to write y into (any row stride >= D)."""
+    _chk(x, torch.float32, "x")
+    n, D = x.shape
+    tab, G = _group_rows(group_rows)
+    if G >= 1 and tab[G] != n:
+        raise _lib.LafsHipError(f"bn1d_groups_fwd: the row table ends at {tab[G]}, x has {n} rows")
+    y = torch.empty(n, D, device=x.device, dtype=torch.float32) if out is None else out
+    _chk(y, torch.float32, "out")
+    if tuple(y.shape) != (n, D):
+        raise _lib.LafsHipError(f"bn1d_groups_fwd: out {tuple(y.shape)} for x {tuple(x.shape)}")
+    mean = torch.empty(max(G, 1), D, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(max(G, 1), D, device=x.device, dtype=torch.float32)
+    call("lafs_bn1d_groups_fwd", _p(x), _ld(x), tab, G, D, _p(gamma), _p(beta), float(eps), float(momentum), 1 if training else 0,
+         _p(running_mean), _p(running_var), _p(y), _ld(y), _p(mean), _p(rstd))
+    return y, mean, rstd
+
+
+def bn1d_groups_bwd(dy, x, group_rows, mean, rstd, gamma, training, dgamma, dbeta, accumulate=True, out=None):
+    """Backward of bn1d_groups_fwd (lafs_bn1d_groups_bwd): returns dx (written into `out` when given); dgamma / dbeta take the groups'
+    sums in group order."""
+    _chk(dy, torch.float32, "dy"); _chk(x, torch.float32, "x")
+    n, D = x.shape
+    tab, G = _group_rows(group_rows)
+    if G >= 1 and (tab[G] != n or dy.shape[0] != n or mean.shape[0] != G or rstd.shape[0] != G):
+        raise _lib.LafsHipError(f"bn1d_groups_bwd: row table ending at {tab[G]} / {G} groups against x {tuple(x.shape)}, "
+                                f"dy {tuple(dy.shape)}, statistics {tuple(mean.shape)}")
+    dx = torch.empty(n, D, device=x.device, dtype=torch.float32) if out is None else out
+    _chk(dx, torch.float32, "out")
+    if tuple(dx.shape) != (n, D):
+        raise _lib.LafsHipError(f"bn1d_groups_bwd: out {tuple(dx.shape)} for x {tuple(x.shape)}")
+    call("lafs_bn1d_groups_bwd", _p(dy), _ld(dy), _p(x), _ld(x), tab, G, D, _p(mean), _p(rstd), _p(gamma), 1 if training else 0, _p(dx),
+         _ld(dx),
+         _p(dgamma), _p(dbeta), 1 if accumulate else 0)
+    return dx
+
+
 def dino_head_loss(zn_s, zn_t, wn_s, wn_t, center, ncrops, K, student_temp, teacher_temp, grad, loss=None, colsum=None, ws=None,
                    dev_temps=None, grad_scale=1.0):
     """DINOHead's last layer of both networks + DINO loss + centre row sums with the logits never stored (csrc/dino_head_loss.hip).

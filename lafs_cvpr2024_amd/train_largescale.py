@@ -210,9 +210,10 @@ def load_ssl_teacher(backbone, path, min_matched=0.9):
     for k, a, b in dropped:
         print(f"=> SSL teacher: skipping {k}: checkpoint {a} vs model {b}")
     if len(hit) < min_matched * len(trunk):
+        arch = "fvit" if hasattr(backbone, "ac_patch_size") else "mynet"      # (--net VITs is ViTs_face_overlap: lafs_train.py --arch fvit)
         raise RuntimeError(f"{path}: only {len(hit)} of the backbone's {len(trunk)} trunk tensors are in ckpt['teacher'] "
                            f"(first missing: {[k for k in trunk if k not in clean][:3]}); is this a checkpoint of another architecture? "
-                           "LAFS pre-training must use --arch mynet for its teacher to initialise this model")
+                           f"LAFS pre-training must use --arch {arch} for its teacher to initialise this model")
     print(f"=> loaded SSL teacher: {len(hit)}/{len(trunk)} trunk tensors;", backbone.load_state_dict(clean, strict=False))
 
 

@@ -660,7 +660,9 @@ int lafs_fill_zero(void* buf, int64_t bytes, hipStream_t stream);
 /* CosFace logits + soft-target CE, fused over the class axis (face_pre_pro/ViT_face.py:49-89;
  * timm SoftTargetCrossEntropy, train_largescale.py:820).  cos(f32) [B, ld] holds x_hat . w_hat^T on entry and
  * dL/dcos on exit.  The (mixup) target is given sparsely: y1,y2 (i32 [B]) with weights lam,(1-lam).
- * loss_out(f32)[1] = mean_b CE.  margin_type 0 = CosFace s*(cos - m*y), 1 = ArcFace (hard labels only). */
+ * loss_out(f32)[1] = mean_b CE.  margin_type 0 = CosFace s*(cos - m*y), 1 = ArcFace (hard labels only).
+ * One workgroup per row, one launch (the row loss is formed before the row is overwritten).  The target, the log-sum-exp and the
+ * gradient expression are the ones of the two chunked entry points below: one implementation, three shapes of launch. */
 int lafs_margin_softmax_ce(float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, float lam,
                            float s, float m, int margin_type, float loss_scale, float* loss_out, float* row_ws,
                            hipStream_t stream);
@@ -686,7 +688,8 @@ int lafs_mixup_normalize(const uint8_t* src_u8, float* dst, int B, int S, float 
 /* The fused margin-softmax + soft-target CE of lafs_margin_softmax_ce over (row, chunk) workgroups, for the captured fine-tune
  * step: cos(f32) [B, ld] is READ-ONLY, dL/dcos leaves as bf16 in dcos [B, lddc] (pad columns [C, lddc) zeroed) -- the operand of
  * the two class-gradient GEMMs; y2 == NULL: the mixup partner of row b is row B-1-b; lam_dev != NULL: lambda from device memory.
- * row_ws f32 [B], part_ws f32 [B * 32].  Same references as lafs_margin_softmax_ce. */
+ * row_ws f32 [B], part_ws f32 [B * 32].  Same references as lafs_margin_softmax_ce.  This is lafs_margin_softmax_ce_mix_bf16 with one
+ * lambda for the whole batch and eps = 0: the same kernels run. */
 int lafs_margin_softmax_ce_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, float lam,
                                 const float* lam_dev, float s, float m, int margin_type, float loss_scale, void* dcos, int lddc,
                                 float* loss_out, float* row_ws, float* part_ws, hipStream_t stream);
@@ -703,9 +706,10 @@ int lafs_mix_normalize(const uint8_t* src_u8, float* dst, int B, int S, const in
  *   y_k = eps/C + (1-eps) (lam_b [k = y1[b]] + (1-lam_b) [k = y2[b]])     (util/mixup_my.py:18-24; equal classes: the summed weight)
  * entering the CosFace margin itself, z_k = s (cos_k - m y_k) (face_pre_pro/ViT_face.py:69-73);  loss_b = lse(z) - sum_k y_k z_k
  * (timm SoftTargetCrossEntropy, train_largescale.py:820) = lse(z) - eps/C sum_k z_k - the two spikes;  dcos = loss_scale/B (softmax - y) s.
- * Same (row, chunk) decomposition, bf16 dcos [B, lddc] with zeroed pad columns and y2 == NULL convention; with eps = 0 and one lambda on
- * every row, loss and dcos equal lafs_margin_softmax_ce_bf16's bit for bit.  margin_type 1 (ArcFace) treats the two spikes as that
- * entry point does and requires eps = 0.  row_ws f32 [B]; part_ws f32 [B * 48] (per row and chunk: max, sum exp, sum z). */
+ * The (row, chunk) kernels of lafs_margin_softmax_ce_bf16, bf16 dcos [B, lddc] with zeroed pad columns and y2 == NULL convention; with
+ * eps = 0 the very same launches run, so with one lambda on every row loss and dcos equal that entry's bit for bit.  margin_type 1
+ * (ArcFace) treats the two spikes as that entry point does and requires eps = 0.  row_ws f32 [B]; part_ws f32 [B * 48] (per row and
+ * chunk: max, sum exp, and for eps > 0 sum z). */
 int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, const float* lam_rows,
                                     int lam_stride, float eps, float s, float m, int margin_type, float loss_scale, void* dcos, int lddc,
                                     float* loss_out, float* row_ws, float* part_ws, hipStream_t stream);

@@ -27,245 +27,197 @@ __device__ __forceinline__ float margin_dlogit(float c, float y, float s, float 
   return s * __sinf(th + m) / __sinf(th);
 }
 
-// one workgroup per sample row
+// ---- the dense head's loss: margin + softmax + soft-target CE, one implementation behind three entry points ----
+// Target of row b, never materialised (util/mixup_my.py:18-24 label smoothing; :152-200 batch / pair / elem modes; :71-81 CutMix's
+// area-corrected lambda):
+//     y_k = off + (1 - eps) (lam_b [k = a1] + (1 - lam_b) [k = a2]),   off = eps / C.
+// It enters the margin itself, z_k = s (cos_k - m y_k) (ViT_face.py:69-73), and
+//     loss_b = lse(z) - sum_k y_k z_k = lse(z) - off sum_k z_k - (the two spikes),      d loss / d z_k = softmax_k - y_k.
+// With eps = 0 the target is exactly lam_b [k = a1] + (1 - lam_b) [k = a2] (off = 0, 1 - eps = 1; equal classes: lam + (1 - lam)).
+struct MixLabel {
+  int a1, a2; float w1, w2, off;
+  __device__ __forceinline__ float operator()(int k) const { return off + (((k == a1) ? w1 : 0.f) + ((k == a2) ? w2 : 0.f)); }
+};
+// y2 == nullptr: the mixup partner of row b is row B-1-b (Mixup batch mode, util/mixup_my.py:189-200)
+__device__ __forceinline__ void mce_labels(const int* y1, const int* y2, int b, int B, int& a1, int& a2) {
+  a1 = y1[b];
+  a2 = (y2 != nullptr) ? y2[b] : y1[B - 1 - b];
+}
+// lambda of row b: lam_rows[b * lam_stride] when lam_rows != nullptr (device memory, read when the kernel runs: stride 0 = one lambda for
+// the batch, 1 = a plain array, LAFS_MIX_WORDS = the parameter table of lafs_mix_normalize), else lam_scalar
+__device__ __forceinline__ MixLabel mix_label(const int* y1, const int* y2, const float* lam_rows, int lam_stride, float lam_scalar, float eps,
+                                              int b, int B, int C) {
+  MixLabel L;
+  mce_labels(y1, y2, b, B, L.a1, L.a2);
+  const float lam = lam_rows ? lam_rows[(size_t)b * lam_stride] : lam_scalar, on = 1.f - eps;
+  L.w1 = on * lam; L.w2 = on * (1.f - lam); L.off = eps / (float)C;
+  return L;
+}
+
+// online (max, sum exp) of a stream of logits: per thread, then per workgroup of 4 waves
+struct OnlineLse {
+  float mx = -INFINITY, sum = 0.f;
+  __device__ __forceinline__ void add(float z) {
+    if (z > mx) { sum = sum * __expf(mx - z) + 1.f; mx = z; } else { sum += __expf(z - mx); }
+  }
+  // a*b + c*d with both products rounded (no fma)
+  static __device__ __forceinline__ float dot2_unfused(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+    return a * b + c * d;
+  }
+  // The pair of the union of two disjoint streams (both empty: max stays -inf, sum 0).  Which product of sa*ea + sb*eb joins the add
+  // in an fma is spelled out: left to -ffp-contract the compiler picks, and not the same way in every kernel (common.hpp, ln_sq4).
+  static __device__ __forceinline__ void merge(float& ma, float& sa, float mb, float sb, bool fuse) {
+    const float mn = fmaxf(ma, mb), ea = __expf(ma - mn), eb = __expf(mb - mn);
+    sa = (mn == -INFINITY) ? 0.f : fuse ? __builtin_fmaf(sa, ea, sb * eb) : dot2_unfused(sa, ea, sb, eb);
+    ma = mn;
+  }
+  // 64-lane butterfly, then the 4 waves through LDS (one barrier).  The workgroup's pair is valid in thread 0 only.  The butterfly's
+  // last level adds two rounded products and the levels before it fuse the own one: the arithmetic every recorded result was made with.
+  __device__ __forceinline__ void block_fold() {
+    __shared__ float sm[4], ss[4];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) merge(mx, sum, __shfl_xor(mx, o, 64), __shfl_xor(sum, o, 64), o > 1);
+    if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = mx; ss[threadIdx.x >> 6] = sum; }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      mx = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
+      sum = 0.f;
+      for (int w = 0; w < 4; ++w) if (sm[w] != -INFINITY) sum += ss[w] * __expf(sm[w] - mx);
+    }
+  }
+  __device__ __forceinline__ float lse() const { return mx + __logf(sum); }
+};
+
+// gscale * (exp(z - shift) * pscale - y) * dz/dcos: the dense head has shift = lse, pscale = 1; the class-sharded head the global
+// max and 1/Z
+__device__ __forceinline__ float margin_grad(float c, float y, float shift, float pscale, float s, float m, int type, float gscale) {
+  return gscale * (__expf(margin_logit(c, y, s, m, type) - shift) * pscale - y) * margin_dlogit(c, y, s, m, type);
+}
+// the spikes' share of sum_k y_k z_k: (y_k - off) z_k at a1 and a2 (a1 == a2: the summed weight, once)
+__device__ __forceinline__ float spike_dot(const float* row, const MixLabel& label, float s, float m, int type) {
+  const int a1 = label.a1, a2 = label.a2;
+  float dot = (label(a1) - label.off) * margin_logit(row[a1], label(a1), s, m, type);
+  if (a2 != a1) dot += (label(a2) - label.off) * margin_logit(row[a2], label(a2), s, m, type);
+  return dot;
+}
+
+// One workgroup per sample row, in place, one launch: cos -> d loss / d cos (f32).  The row loss is formed before the barrier
+// because the overwrite below destroys row[a1] and row[a2].
 __global__ __launch_bounds__(256) void margin_ce_kernel(float* __restrict__ cosv, int ld, int C, const int* __restrict__ y1,
                                                        const int* __restrict__ y2, float lam, float s, float m, int type,
                                                        float gscale, float* __restrict__ row_loss) {
-  __shared__ float sm[4], ss[4];
-  __shared__ float bc[2];
+  __shared__ float bc;
   const int b = blockIdx.x;
   float* row = cosv + (size_t)b * ld;
-  const int a1 = y1[b], a2 = y2[b];
-  auto label = [&](int k) { return ((k == a1) ? lam : 0.f) + ((k == a2) ? (1.f - lam) : 0.f); };
-  float mx = -INFINITY, sum = 0.f;
-  for (int k = threadIdx.x; k < C; k += 256) {
-    const float z = margin_logit(row[k], label(k), s, m, type);
-    if (z > mx) { sum = sum * __expf(mx - z) + 1.f; mx = z; } else { sum += __expf(z - mx); }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float mo = __shfl_xor(mx, o, 64), so = __shfl_xor(sum, o, 64);
-    const float mn = fmaxf(mx, mo);
-    sum = (mn == -INFINITY) ? 0.f : sum * __expf(mx - mn) + so * __expf(mo - mn);
-    mx = mn;
-  }
-  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = mx; ss[threadIdx.x >> 6] = sum; }
-  __syncthreads();
+  const MixLabel label = mix_label(y1, y2, nullptr, 0, lam, 0.f, b, gridDim.x, C);
+  OnlineLse acc;
+  for (int k = threadIdx.x; k < C; k += 256) acc.add(margin_logit(row[k], label(k), s, m, type));
+  acc.block_fold();
   if (threadIdx.x == 0) {
-    const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-    float S = 0.f;
-    for (int w = 0; w < 4; ++w) if (sm[w] != -INFINITY) S += ss[w] * __expf(sm[w] - M);
-    const float lse = M + __logf(S);
-    bc[0] = lse;
-    float dot = label(a1) * margin_logit(row[a1], label(a1), s, m, type);
-    if (a2 != a1) dot += label(a2) * margin_logit(row[a2], label(a2), s, m, type);
-    row_loss[b] = lse - dot;                               // sum_k y_k = 1
+    bc = acc.lse();
+    row_loss[b] = acc.lse() - spike_dot(row, label, s, m, type);   // sum_k y_k = 1
   }
   __syncthreads();
-  const float lse = bc[0];
-  for (int k = threadIdx.x; k < C; k += 256) {
-    const float c = row[k], y = label(k);
-    const float z = margin_logit(c, y, s, m, type);
-    row[k] = gscale * (__expf(z - lse) - y) * margin_dlogit(c, y, s, m, type);
-  }
+  const float lse = bc;
+  for (int k = threadIdx.x; k < C; k += 256) row[k] = margin_grad(row[k], label(k), lse, 1.f, s, m, type, gscale);
 }
 
 // The same loss over (row, chunk) workgroups: one workgroup per row streams 824 KB twice at C = 205 990 and 128 rows leave half
 // the chip idle (556 us, latency-bound); NCH chunks per row fill it.  Pass 1: per-chunk (max, sum exp) of the margin logits; pass 2:
 // every workgroup folds its row's NCH partials, writes d loss / d cos of its chunk as bf16 (the operand format of the two
-// gradient GEMMs: no fp32 round trip, no separate cast) and chunk 0 the row loss.  cos is read-only.  y2 == nullptr: the mixup
-// partner of row b is row B-1-b (Mixup batch mode, util/mixup_my.py:189-200).  lam_dev != nullptr: lambda read from device memory.
+// gradient GEMMs: no fp32 round trip, no separate cast) and chunk 0 the row loss.  cos is read-only.
+// SMOOTH: label smoothing is on (off > 0), so pass 1 keeps a third per-chunk partial, sum_k z_k, and the row loss takes its
+// off * sum_k z_k term: part f32 [B, NCH, 3] instead of [B, NCH, 2].  Without it off is exactly 0 and the term it drops is 0 * sum z.
 constexpr int MCE_NCH = 16;
-__device__ __forceinline__ void mce_labels(const int* y1, const int* y2, int b, int B, int& a1, int& a2) {
-  a1 = y1[b];
-  a2 = (y2 != nullptr) ? y2[b] : y1[B - 1 - b];
+struct MceChunk { int k0, k1; };
+__device__ __forceinline__ MceChunk mce_chunk(int C, int ch) {
+  const int per = ((C + MCE_NCH - 1) / MCE_NCH + 3) & ~3, k0 = ch * per;
+  return {k0, min(C, k0 + per)};
 }
-__global__ __launch_bounds__(256) void margin_ce_part_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
-                                                            const int* __restrict__ y2, float lam, const float* __restrict__ lam_dev, float s,
-                                                            float m, int type, float* __restrict__ part) {
-  __shared__ float sm[4], ss[4];
-  if (lam_dev != nullptr) lam = *lam_dev;
-  const int b = blockIdx.y, ch = blockIdx.x;
-  const float* row = cosv + (size_t)b * ld;
-  int a1, a2;
-  mce_labels(y1, y2, b, B, a1, a2);
-  auto label = [&](int k) { return ((k == a1) ? lam : 0.f) + ((k == a2) ? (1.f - lam) : 0.f); };
-  const int per = ((C + MCE_NCH - 1) / MCE_NCH + 3) & ~3, k0 = ch * per, k1 = min(C, k0 + per);
-  float mx = -INFINITY, sum = 0.f;
-  for (int k = k0 + threadIdx.x; k < k1; k += 256) {
-    const float z = margin_logit(row[k], label(k), s, m, type);
-    if (z > mx) { sum = sum * __expf(mx - z) + 1.f; mx = z; } else { sum += __expf(z - mx); }
-  }
+// lse of a row from its NCH (max, sum exp) partials, NP floats apart
+template <int NP>
+__device__ __forceinline__ float mce_fold_lse(const float* prow) {
+  OnlineLse r;
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float mo = __shfl_xor(mx, o, 64), so = __shfl_xor(sum, o, 64);
-    const float mn = fmaxf(mx, mo);
-    sum = (mn == -INFINITY) ? 0.f : sum * __expf(mx - mn) + so * __expf(mo - mn);
-    mx = mn;
-  }
-  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = mx; ss[threadIdx.x >> 6] = sum; }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-    float S = 0.f;
-    for (int w = 0; w < 4; ++w) if (sm[w] != -INFINITY) S += ss[w] * __expf(sm[w] - M);
-    part[((size_t)b * MCE_NCH + ch) * 2] = M;
-    part[((size_t)b * MCE_NCH + ch) * 2 + 1] = S;
-  }
-}
-__global__ __launch_bounds__(256) void margin_ce_grad_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
-                                                            const int* __restrict__ y2, float lam, const float* __restrict__ lam_dev, float s,
-                                                            float m, int type, float gscale, const float* __restrict__ part,
-                                                            bf16_t* __restrict__ dcos, int lddc, float* __restrict__ row_loss) {
-  if (lam_dev != nullptr) lam = *lam_dev;
-  const int b = blockIdx.y, ch = blockIdx.x;
-  const float* row = cosv + (size_t)b * ld;
-  int a1, a2;
-  mce_labels(y1, y2, b, B, a1, a2);
-  auto label = [&](int k) { return ((k == a1) ? lam : 0.f) + ((k == a2) ? (1.f - lam) : 0.f); };
-  float M = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < MCE_NCH; ++c) M = fmaxf(M, part[((size_t)b * MCE_NCH + c) * 2]);
-  float S = 0.f;
+  for (int c = 0; c < MCE_NCH; ++c) r.mx = fmaxf(r.mx, prow[c * NP]);
 #pragma unroll
   for (int c = 0; c < MCE_NCH; ++c) {
-    const float mc = part[((size_t)b * MCE_NCH + c) * 2];
-    if (mc != -INFINITY) S += part[((size_t)b * MCE_NCH + c) * 2 + 1] * __expf(mc - M);
+    const float mc = prow[c * NP];
+    if (mc != -INFINITY) r.sum += prow[c * NP + 1] * __expf(mc - r.mx);
   }
-  const float lse = M + __logf(S);
-  if (ch == 0 && threadIdx.x == 0) {
-    float dot = label(a1) * margin_logit(row[a1], label(a1), s, m, type);
-    if (a2 != a1) dot += label(a2) * margin_logit(row[a2], label(a2), s, m, type);
-    row_loss[b] = lse - dot;
-  }
-  const int per = ((C + MCE_NCH - 1) / MCE_NCH + 3) & ~3, k0 = ch * per, k1 = min(C, k0 + per);
-  bf16_t* drow = dcos + (size_t)b * lddc;
-  for (int k = k0 + 4 * threadIdx.x; k < k1; k += 1024) {           // 4 consecutive classes per thread: 16-byte loads, 8-byte stores
+  return r.lse();
+}
+// bf16 gradient of classes [k0, k1) of one row (k0 a multiple of 4); `pads`: also zero the pad columns [C, lddc) of the gradient operand
+__device__ __forceinline__ void mce_write_chunk(const float* row, bf16_t* drow, MceChunk ck, const MixLabel& label, float lse, float s, float m,
+                                                int type, float gscale, bool pads, int C, int lddc) {
+  const int k1 = ck.k1;
+  for (int k = ck.k0 + 4 * threadIdx.x; k < k1; k += 1024) {        // 4 consecutive classes per thread: 16-byte loads, 8-byte stores
     if (k + 3 < k1) {
       const float4 c4 = *reinterpret_cast<const float4*>(row + k);
       const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
       float g[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float y = label(k + e);
-        g[e] = gscale * (__expf(margin_logit(cv[e], y, s, m, type) - lse) - y) * margin_dlogit(cv[e], y, s, m, type);
-      }
+      for (int e = 0; e < 4; ++e) g[e] = margin_grad(cv[e], label(k + e), lse, 1.f, s, m, type, gscale);
       *reinterpret_cast<uint2*>(drow + k) = make_uint2(pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]));
     } else {
-      for (int e = 0; e < 4 && k + e < k1; ++e) {
-        const float c = row[k + e], y = label(k + e);
-        drow[k + e] = f2bf(gscale * (__expf(margin_logit(c, y, s, m, type) - lse) - y) * margin_dlogit(c, y, s, m, type));
-      }
+      for (int e = 0; e < 4 && k + e < k1; ++e) drow[k + e] = f2bf(margin_grad(row[k + e], label(k + e), lse, 1.f, s, m, type, gscale));
     }
   }
-  // pad columns [C, lddc) of the gradient operand are zero (chunk NCH-1 owns them)
-  if (ch == MCE_NCH - 1)
+  if (pads)
     for (int k = C + threadIdx.x; k < lddc; k += 256) drow[k] = 0;
 }
 
-// ---- the same (row, chunk) loss with a lambda PER ROW and label smoothing (util/mixup_my.py:18-24 with smoothing > 0; pair / elem
-// modes :152-187; CutMix's area-corrected lambda :71-81).  The target of row b is dense,
-//     y_k = off + (1 - eps) (lam_b [k = a1] + (1 - lam_b) [k = a2]),   off = eps / C,
-// and enters the CosFace margin itself, z_k = s (cos_k - m y_k) (ViT_face.py:69-73); it is never built:
-//     loss_b = lse(z) - sum_k y_k z_k = lse(z) - off sum_k z_k - (the two spikes),      d loss / d z_k = softmax_k - y_k.
-// Pass 1 therefore keeps a third per-chunk partial, sum_k z_k, beside (max, sum exp): part f32 [B, NCH, 3].  With eps = 0 every
-// expression below reduces exactly (off = 0, 1 - eps = 1) to the one of margin_ce_part_kernel / margin_ce_grad_kernel, evaluated
-// in the same order: the results are bit-identical.  lam of row b = lam_rows[b * lam_stride] (the parameter table of
-// lafs_mix_normalize, read when the kernel runs).
-struct MixLabel {
-  int a1, a2; float w1, w2, off;
-  __device__ __forceinline__ float operator()(int k) const { return off + (((k == a1) ? w1 : 0.f) + ((k == a2) ? w2 : 0.f)); }
-};
-__device__ __forceinline__ MixLabel mix_label(const int* y1, const int* y2, const float* lam_rows, int lam_stride, float eps, int b, int B,
-                                              int C) {
-  MixLabel L;
-  mce_labels(y1, y2, b, B, L.a1, L.a2);
-  const float lam = lam_rows[(size_t)b * lam_stride], on = 1.f - eps;
-  L.w1 = on * lam; L.w2 = on * (1.f - lam); L.off = eps / (float)C;
-  return L;
-}
-__global__ __launch_bounds__(256) void margin_ce_mix_part_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
-                                                                const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
-                                                                float eps, float s, float m, int type, float* __restrict__ part) {
-  __shared__ float sm[4], ss[4], sz[4];
+template <bool SMOOTH>
+__global__ __launch_bounds__(256) void margin_ce_part_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
+                                                            const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
+                                                            float lam, float eps, float s, float m, int type, float* __restrict__ part) {
+  constexpr int NP = SMOOTH ? 3 : 2;
+  __shared__ float sz[4];
   const int b = blockIdx.y, ch = blockIdx.x;
   const float* row = cosv + (size_t)b * ld;
-  const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, eps, b, B, C);
-  const int per = ((C + MCE_NCH - 1) / MCE_NCH + 3) & ~3, k0 = ch * per, k1 = min(C, k0 + per);
-  float mx = -INFINITY, sum = 0.f, zs = 0.f;
-  for (int k = k0 + threadIdx.x; k < k1; k += 256) {
+  const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, lam, eps, b, B, C);
+  const MceChunk ck = mce_chunk(C, ch);
+  OnlineLse acc;
+  float zs = 0.f;
+  for (int k = ck.k0 + threadIdx.x; k < ck.k1; k += 256) {
     const float z = margin_logit(row[k], label(k), s, m, type);
-    zs += z;
-    if (z > mx) { sum = sum * __expf(mx - z) + 1.f; mx = z; } else { sum += __expf(z - mx); }
+    if constexpr (SMOOTH) zs += z;
+    acc.add(z);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float mo = __shfl_xor(mx, o, 64), so = __shfl_xor(sum, o, 64);
-    const float mn = fmaxf(mx, mo);
-    sum = (mn == -INFINITY) ? 0.f : sum * __expf(mx - mn) + so * __expf(mo - mn);
-    mx = mn;
+  if constexpr (SMOOTH) {
+    zs = wave_sum(zs);
+    if ((threadIdx.x & 63) == 0) sz[threadIdx.x >> 6] = zs;
   }
-  zs = wave_sum(zs);
-  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = mx; ss[threadIdx.x >> 6] = sum; sz[threadIdx.x >> 6] = zs; }
-  __syncthreads();
+  acc.block_fold();
   if (threadIdx.x == 0) {
-    const float M = fmaxf(fmaxf(sm[0], sm[1]), fmaxf(sm[2], sm[3]));
-    float S = 0.f;
-    for (int w = 0; w < 4; ++w) if (sm[w] != -INFINITY) S += ss[w] * __expf(sm[w] - M);
-    float* p = part + ((size_t)b * MCE_NCH + ch) * 3;
-    p[0] = M; p[1] = S; p[2] = (sz[0] + sz[1]) + (sz[2] + sz[3]);
+    float* p = part + ((size_t)b * MCE_NCH + ch) * NP;
+    p[0] = acc.mx; p[1] = acc.sum;
+    if constexpr (SMOOTH) p[2] = (sz[0] + sz[1]) + (sz[2] + sz[3]);
   }
 }
-__global__ __launch_bounds__(256) void margin_ce_mix_grad_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
-                                                                const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
-                                                                float eps, float s, float m, int type, float gscale,
-                                                                const float* __restrict__ part, bf16_t* __restrict__ dcos, int lddc,
-                                                                float* __restrict__ row_loss) {
+template <bool SMOOTH>
+__global__ __launch_bounds__(256) void margin_ce_grad_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
+                                                            const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
+                                                            float lam, float eps, float s, float m, int type, float gscale,
+                                                            const float* __restrict__ part, bf16_t* __restrict__ dcos, int lddc,
+                                                            float* __restrict__ row_loss) {
+  constexpr int NP = SMOOTH ? 3 : 2;
   const int b = blockIdx.y, ch = blockIdx.x;
   const float* row = cosv + (size_t)b * ld;
-  const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, eps, b, B, C);
-  const int a1 = label.a1, a2 = label.a2;
-  const float* prow = part + (size_t)b * MCE_NCH * 3;
-  float M = -INFINITY;
-#pragma unroll
-  for (int c = 0; c < MCE_NCH; ++c) M = fmaxf(M, prow[c * 3]);
-  float S = 0.f;
-#pragma unroll
-  for (int c = 0; c < MCE_NCH; ++c) {
-    const float mc = prow[c * 3];
-    if (mc != -INFINITY) S += prow[c * 3 + 1] * __expf(mc - M);
-  }
-  const float lse = M + __logf(S);
+  const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, lam, eps, b, B, C);
+  const float* prow = part + (size_t)b * MCE_NCH * NP;
+  const float lse = mce_fold_lse<NP>(prow);
   if (ch == 0 && threadIdx.x == 0) {
-    // the spikes' share of sum_k y_k z_k: (y_k - off) z_k at a1 and a2 (a1 == a2: the summed weight, once)
-    float dot = (label(a1) - label.off) * margin_logit(row[a1], label(a1), s, m, type);
-    if (a2 != a1) dot += (label(a2) - label.off) * margin_logit(row[a2], label(a2), s, m, type);
-    float Zs = 0.f;
-    for (int c = 0; c < MCE_NCH; ++c) Zs += prow[c * 3 + 2];
-    row_loss[b] = (lse - dot) - label.off * Zs;             // sum_k y_k = 1
-  }
-  const int per = ((C + MCE_NCH - 1) / MCE_NCH + 3) & ~3, k0 = ch * per, k1 = min(C, k0 + per);
-  bf16_t* drow = dcos + (size_t)b * lddc;
-  for (int k = k0 + 4 * threadIdx.x; k < k1; k += 1024) {           // 4 consecutive classes per thread: 16-byte loads, 8-byte stores
-    if (k + 3 < k1) {
-      const float4 c4 = *reinterpret_cast<const float4*>(row + k);
-      const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
-      float g[4];
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float y = label(k + e);
-        g[e] = gscale * (__expf(margin_logit(cv[e], y, s, m, type) - lse) - y) * margin_dlogit(cv[e], y, s, m, type);
-      }
-      *reinterpret_cast<uint2*>(drow + k) = make_uint2(pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]));
-    } else {
-      for (int e = 0; e < 4 && k + e < k1; ++e) {
-        const float c = row[k + e], y = label(k + e);
-        drow[k + e] = f2bf(gscale * (__expf(margin_logit(c, y, s, m, type) - lse) - y) * margin_dlogit(c, y, s, m, type));
-      }
+    float loss = lse - spike_dot(row, label, s, m, type);   // sum_k y_k = 1
+    if constexpr (SMOOTH) {
+      float Zs = 0.f;
+      for (int c = 0; c < MCE_NCH; ++c) Zs += prow[c * NP + 2];
+      loss -= label.off * Zs;
     }
+    row_loss[b] = loss;
   }
-  if (ch == MCE_NCH - 1)
-    for (int k = C + threadIdx.x; k < lddc; k += 256) drow[k] = 0;
+  mce_write_chunk(row, dcos + (size_t)b * lddc, mce_chunk(C, ch), label, lse, s, m, type, gscale, ch == MCE_NCH - 1, C, lddc);
 }
 
 __global__ __launch_bounds__(256) void cast_i64_i32_kernel(const long long* __restrict__ src, int* __restrict__ dst, int n) {
@@ -296,22 +248,27 @@ __global__ __launch_bounds__(256) void mean_kernel(const float* __restrict__ v, 
   if (threadIdx.x == 0) out[0] = (red[0] + red[1] + red[2] + red[3]) * scale;
 }
 
+// u8 -> [-1,1] (x/255*2-1) and the mixup blend of a pixel with its partner's, shared by the two kernels below.  At lambda 1 the pixel
+// passes through and the partner is not loaded (hence the pointer).
+__device__ __forceinline__ float u8_norm(uint8_t v) { return (float)v * (2.f / 255.f) - 1.f; }
+__device__ __forceinline__ float mix_blend(float x, const uint8_t* partner, float lam) {
+  return (lam == 1.f) ? x : x * lam + u8_norm(*partner) * (1.f - lam);
+}
+
 __global__ __launch_bounds__(256) void mixup_norm_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int B, size_t per,
                                                         float lam, const float* __restrict__ lam_dev) {
   if (lam_dev != nullptr) lam = *lam_dev;                // a captured step reads this micro-step's lambda from device memory
   const size_t total = (size_t)B * per;
   for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (size_t)gridDim.x * 256) {
     const size_t b = i / per, r = i % per;
-    const float x = (float)src[i] * (2.f / 255.f) - 1.f;
-    const float xf = (float)src[(B - 1 - b) * per + r] * (2.f / 255.f) - 1.f;
-    dst[i] = (lam == 1.f) ? x : x * lam + xf * (1.f - lam);
+    dst[i] = mix_blend(u8_norm(src[i]), src + (B - 1 - b) * per + r, lam);
   }
 }
 
 // u8 -> [-1,1] with this micro-step's mixing folded in, per ROW (util/mixup_my.py:152-200: batch, pair and elem modes all mix row b
 // with row B-1-b of the unmixed batch).  tab: LAFS_MIX_WORDS 32-bit words per row -- lambda (f32), CutMix flag, box yl, yh, xl, xh --
 // read when the kernel runs.  A CutMix row takes its partner inside the box ([yl, yh) x [xl, xh), every channel: :163, :180-181, :196)
-// and itself outside; any other row is blended with mixup_norm_kernel's arithmetic (lambda 1: the row passes through).
+// and itself outside; any other row is blended as mixup_norm_kernel blends (mix_blend).
 __global__ __launch_bounds__(256) void mix_norm_kernel(const uint8_t* __restrict__ src, float* __restrict__ dst, int B, int S,
                                                       const int* __restrict__ tab) {
   const size_t per = (size_t)3 * S * S, total = (size_t)B * per;
@@ -319,13 +276,13 @@ __global__ __launch_bounds__(256) void mix_norm_kernel(const uint8_t* __restrict
     const size_t b = i / per, r = i % per;
     const int* t = tab + b * LAFS_MIX_WORDS;
     const float lam = __int_as_float(t[0]);
-    const float x = (float)src[i] * (2.f / 255.f) - 1.f;
-    const float xf = (float)src[(B - 1 - b) * per + r] * (2.f / 255.f) - 1.f;
+    const uint8_t* partner = src + (B - 1 - b) * per + r;
+    const float x = u8_norm(src[i]), xf = u8_norm(*partner);
     if (t[1] != 0) {
       const int px = (int)(r % S), py = (int)((r / S) % S);
       dst[i] = (py >= t[2] && py < t[3] && px >= t[4] && px < t[5]) ? xf : x;
     } else {
-      dst[i] = (lam == 1.f) ? x : x * lam + xf * (1.f - lam);
+      dst[i] = mix_blend(x, partner, lam);
     }
   }
 }
@@ -455,11 +412,7 @@ __global__ __launch_bounds__(256) void shard_grad_kernel(float* __restrict__ cos
   float* row = cosv + (size_t)b * ld;
   const ShardLabel L = shard_label(y, y2, lam, b);
   const float g = gmax[b], iz = 1.0f / Z[b];
-  for (int k = threadIdx.x; k < S; k += 256) {
-    const float c = row[k], yk = L(k);
-    const float z = margin_logit(c, yk, s, m, type);
-    row[k] = gscale * (__expf(z - g) * iz - yk) * margin_dlogit(c, yk, s, m, type);
-  }
+  for (int k = threadIdx.x; k < S; k += 256) row[k] = margin_grad(row[k], L(k), g, iz, s, m, type, gscale);
 }
 
 // ---- landmark post-processing: raw regressor output -> pixel landmarks (face_pre_pro/ViT_face.py:1347-1378) ----
@@ -485,6 +438,22 @@ __global__ __launch_bounds__(256) void landmark_theta_kernel(const float* __rest
     if (noise) v += noise_scale * noise[(size_t)b * L + src];
     theta[(size_t)b * 2 * n_out + k] = v;
   }
+}
+
+// the chunked form's three launches: partials, gradient + row losses, mean loss
+template <bool SMOOTH>
+int launch_margin_ce(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, const float* lam_rows, int lam_stride, float lam,
+                     float eps, float s, float m, int margin_type, float loss_scale, void* dcos, int lddc, float* loss_out, float* row_ws,
+                     float* part_ws, hipStream_t stream) {
+  hipLaunchKernelGGL(margin_ce_part_kernel<SMOOTH>, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, lam, eps,
+                     s, m, margin_type, part_ws);
+  LAFS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(margin_ce_grad_kernel<SMOOTH>, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, lam, eps,
+                     s, m, margin_type, loss_scale / (float)B, part_ws, (bf16_t*)dcos, lddc, row_ws);
+  LAFS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, stream, row_ws, B, 1.0f / (float)B, loss_out);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
 }
 
 int isqrt_exact(int n) {
@@ -515,14 +484,8 @@ extern "C" int lafs_margin_softmax_ce_bf16(const float* cos, int ld, int B, int 
   LAFS_CHECK_ARG(cos && y1 && dcos && loss_out && row_ws && part_ws && B > 0 && C > 0 && ld >= C && lddc >= C, "bad operand");
   LAFS_CHECK_ARG(ld % 4 == 0 && lddc % 4 == 0, "row strides must be multiples of 4 elements");
   LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
-  hipLaunchKernelGGL(margin_ce_part_kernel, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam, lam_dev, s, m, margin_type, part_ws);
-  LAFS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(margin_ce_grad_kernel, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam, lam_dev, s, m, margin_type,
-                     loss_scale / (float)B, part_ws, (bf16_t*)dcos, lddc, row_ws);
-  LAFS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, stream, row_ws, B, 1.0f / (float)B, loss_out);
-  LAFS_LAUNCH_CHECK();
-  return LAFS_OK;
+  return launch_margin_ce<false>(cos, ld, B, C, y1, y2, lam_dev, 0, lam, 0.f, s, m, margin_type, loss_scale, dcos, lddc, loss_out, row_ws, part_ws,
+                                 stream);
 }
 
 extern "C" int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2,
@@ -536,15 +499,8 @@ extern "C" int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, 
   LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
   LAFS_CHECK_ARG(eps >= 0.f && eps < 1.f, "label smoothing must lie in [0, 1)");
   LAFS_CHECK_ARG(eps == 0.f || margin_type == 0, "label smoothing needs the CosFace margin (ArcFace has no margin for a dense target)");
-  hipLaunchKernelGGL(margin_ce_mix_part_kernel, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, eps, s, m,
-                     margin_type, part_ws);
-  LAFS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(margin_ce_mix_grad_kernel, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, eps, s, m,
-                     margin_type, loss_scale / (float)B, part_ws, (bf16_t*)dcos, lddc, row_ws);
-  LAFS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, stream, row_ws, B, 1.0f / (float)B, loss_out);
-  LAFS_LAUNCH_CHECK();
-  return LAFS_OK;
+  const auto launch = eps > 0.f ? launch_margin_ce<true> : launch_margin_ce<false>;        // eps == 0: off = 0, nothing to smooth
+  return launch(cos, ld, B, C, y1, y2, lam_rows, lam_stride, 0.f, eps, s, m, margin_type, loss_scale, dcos, lddc, loss_out, row_ws, part_ws, stream);
 }
 
 extern "C" int lafs_cast_i64_i32(const int64_t* src, int32_t* dst, int n, hipStream_t stream) {

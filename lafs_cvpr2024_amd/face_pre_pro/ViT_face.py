@@ -58,7 +58,7 @@ def extract_patches_pytorch_gridsample(imgs, landmarks, patch_shape=None, num_la
 # ------------------------------------------------------------------------------------------------- margin head
 class _CosFaceFunction(torch.autograd.Function):
     """s * (cos(x, W) - m * y).  cos is an MFMA GEMM over row-normalised bf16 operands; the normalisations are HIP
-    row kernels.  (The training engine fuses margin + softmax + CE instead: lafs_margin_softmax_ce.)"""
+    row kernels.  (The training engine fuses margin + softmax + CE instead: lafs_margin_softmax_ce_bf16 / _mix_bf16.)"""
 
     @staticmethod
     def forward(ctx, x, weight, label, s, m):

@@ -135,6 +135,94 @@ def test_capture_friendly_margin_kernel_equals_the_in_place_one(margin_type, m, 
         assert torch.equal(out, Fn.unpatchify_grad(dp, order).contiguous())
 
 
+# ---- the dense head's loss against fp64: both entry points that take one lambda per batch (the per-row entry: test_gpu_mixup_modes.py) ----
+MCE_SHAPES = [(8, 50), (8, 1000), (32, 20533)]       # most chunks short or empty / one float4 body / C % 4 = 1: tail and pad columns live
+MCE_MARGINS = [(0, 0.4, 0.3), (1, 0.5, 1.0), (1, 0.5, 0.3)]
+GATE_MCE_F32 = 3.04e-6                               # 4 x 7.60e-7, the worst in-place gradient error observed (test_in_place_margin_loss_... docstring)
+_MCE_REF = {}
+
+
+def _mce_case(B, C, margin_type, m, lam):
+    """Inputs and the fp64 reference of one case, computed once and shared: fp32 cosines, labels with one row whose partner (row B-1-b)
+    carries its own class, and (mean loss, row losses, d mean loss / d cos) of the dense formulation.  CosFace: tests/mixup_oracle.py with
+    smoothing 0.  ArcFace, restated here: margin s cos(acos(c) + m) on the classes whose target weight is > 0, s c elsewhere; loss
+    lse(z) - sum_k y_k z_k; gradient by autograd."""
+    key = (B, C, margin_type, lam)
+    if key not in _MCE_REF:
+        import mixup_oracle as mo
+        g = torch.Generator().manual_seed(131 * C + B)
+        Cpad = (C + 127) // 128 * 128
+        cos = torch.rand(B, Cpad, generator=g) * 2 - 1
+        cos[:, C:] = 0
+        y = torch.randint(0, C, (B,), generator=g)
+        y[2] = y[B - 3]                                                   # a1 == a2 (with lam = 0.3: strictly inside (0, 1))
+        if margin_type == 0:
+            ref = mo.loss_and_dcos(cos[:, :C], y, torch.full((B,), lam, dtype=torch.float64), 0.0, s=64.0, m=m)
+        else:
+            c = cos[:, :C].double().requires_grad_(True)
+            t = mo.dense_target(y, C, torch.full((B,), lam, dtype=torch.float64))
+            z = 64.0 * torch.where(t > 0, torch.cos(torch.acos(c) + m), c)
+            rows = torch.logsumexp(z, dim=-1) - (t * z).sum(-1)
+            rows.mean().backward()
+            ref = (rows.mean().detach(), rows.detach(), c.grad)
+        _MCE_REF[key] = (cos, y, Cpad, ref)
+    return _MCE_REF[key]
+
+
+def _mce_errors(tag, loss, rows, grad, ref):
+    ref_loss, ref_rows, ref_g = ref
+    e_loss = abs(float(loss) - float(ref_loss)) / abs(float(ref_loss))
+    e_rows = float(((rows.cpu().double() - ref_rows).abs() / ref_rows.abs()).max())
+    e_grad = rel_l2(grad, ref_g)
+    print(f"[{tag}] loss {float(loss):.6f} vs {float(ref_loss):.6f}: rel {e_loss:.2e}; worst row {e_rows:.2e}; gradient rel-L2 {e_grad:.3e}")
+    return e_loss, e_rows, e_grad
+
+
+@pytest.mark.parametrize("margin_type,m,lam", MCE_MARGINS)
+@pytest.mark.parametrize("B,C", MCE_SHAPES)
+def test_chunked_margin_loss_against_the_dense_fp64_oracle(margin_type, m, lam, B, C):
+    """lafs_margin_softmax_ce_bf16 (implied partner, lambda from device memory) against fp64 on the same fp32 cosines.  Bounds: the
+    project's own for the bf16 entry -- mean loss and every row loss 1e-5 relative, gradient 4e-3 relative L2 (the bf16 rounding of
+    the output), pad columns exactly 0."""
+    cos, y, Cpad, ref = _mce_case(B, C, margin_type, m, lam)
+    cos_d, y1, lam_dev = cos.to(DEV), y.to(DEV, torch.int32), torch.tensor([lam], device=DEV)      # (named: _p keeps no tensor alive)
+    dcos = torch.full((B, Cpad), 7.0, device=DEV, dtype=torch.bfloat16)
+    loss, rows, part = torch.zeros(1, device=DEV), torch.empty(B, device=DEV), torch.empty(B * 32, device=DEV)
+    call("lafs_margin_softmax_ce_bf16", _p(cos_d), Cpad, B, C, _p(y1), None, -7.0, _p(lam_dev), 64.0, m, margin_type, 1.0, _p(dcos), Cpad,
+         _p(loss), _p(rows), _p(part))
+    e_loss, e_rows, e_grad = _mce_errors(f"chunked margin loss vs fp64, B={B} C={C} type={margin_type} lam={lam}", loss, rows, dcos[:, :C].float(), ref)
+    assert e_loss < 1e-5
+    assert e_rows < 1e-5                                                # every row on its own: no row's error hides behind another's
+    assert e_grad < 4e-3
+    assert float(dcos[:, C:].float().abs().max()) == 0.0
+
+
+@pytest.mark.parametrize("margin_type,m,lam", MCE_MARGINS)
+@pytest.mark.parametrize("B,C", MCE_SHAPES)
+def test_in_place_margin_loss_against_the_dense_fp64_oracle(margin_type, m, lam, B, C):
+    """lafs_margin_softmax_ce (one workgroup per row, f32 gradient in place of the cosines) against fp64.  Loss bounds: those of the
+    chunked entry (the same fp32 arithmetic: 1e-5 relative, mean and every row).  Gradient: fp32 out, so no bf16 rounding; gate =
+    4x the worst relative L2 observed over these nine cases (the allowance for another seed's draw), far below the bf16 entry's 4e-3.
+    Observed on MI355X before the three copies of the loss were merged into one (CosFace lam 0.3 / ArcFace lam 1 / ArcFace lam 0.3):
+      (8, 50)      5.36e-7 / 5.11e-7 / 5.41e-7
+      (8, 1000)    7.03e-7 / 3.40e-7 / 7.60e-7
+      (32, 20533)  1.73e-7 / 2.40e-7 / 3.62e-7
+    (the merged implementation gives the same figures to every printed digit: its results equal the old ones bit for bit).
+    The pad columns of the row are not the kernel's: they must stay as they were."""
+    cos, y, Cpad, ref = _mce_case(B, C, margin_type, m, lam)
+    y1 = y.to(DEV, torch.int32)
+    y2 = y1.flip(0).contiguous()
+    buf = cos.to(DEV)
+    buf[:, C:] = 7.0
+    loss, rows = torch.zeros(1, device=DEV), torch.empty(B, device=DEV)
+    call("lafs_margin_softmax_ce", _p(buf), Cpad, B, C, _p(y1), _p(y2), lam, 64.0, m, margin_type, 1.0, _p(loss), _p(rows))
+    e_loss, e_rows, e_grad = _mce_errors(f"in-place margin loss vs fp64, B={B} C={C} type={margin_type} lam={lam}", loss, rows, buf[:, :C], ref)
+    assert e_loss < 1e-5
+    assert e_rows < 1e-5
+    assert e_grad < GATE_MCE_F32 < 4e-3
+    assert bool((buf[:, C:] == 7.0).all())
+
+
 @pytest.mark.parametrize("with_land", [False, True])
 def test_captured_finetune_step_equals_the_eager_single_stream_step(with_land, monkeypatch):
     """The fine-tune micro-step as hipGraphs (the default; with the landmark branch: weight gradients deferred onto a second stream

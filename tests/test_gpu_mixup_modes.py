@@ -114,7 +114,9 @@ def test_mix_loss_kernel_without_smoothing_equals_the_batch_kernel_bit_for_bit(m
     """eps = 0 and one lambda on every row: the target expression off + (1 - eps) w reduces exactly to w, every reduction runs in the
     same order -- loss and bf16 gradient equal lafs_margin_softmax_ce_bf16's bit for bit, for both margin types; lambda read from a
     plain array and from the parameter table, partner implied and explicit.  ArcFace runs with lambda 1 (hard labels) and with 0.3, where
-    both spikes are live: the two kernels treat them alike."""
+    both spikes are live.  Both entry points launch the same kernel pair when eps = 0, so this guards the lambda plumbing (scalar, one
+    device word at stride 0, a word per row at stride 1 or LAFS_MIX_WORDS) and the dispatch on eps; the arithmetic itself is held against
+    fp64 in tests/test_gpu_finetune.py (batch entries) and below (per-row entry)."""
     cos, y, Cpad = _cos_and_labels(B, C, 31 + B)
     cos = cos.to(DEV)
     y1 = y.to(DEV, torch.int32)

@@ -440,6 +440,38 @@ int lafs_bn1d_groups_fwd(const float* x, int ldx, const int* group_rows, int G, 
 int lafs_bn1d_groups_bwd(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, int G, int D, const float* save_mean,
                          const float* save_rstd, const float* gamma, int training, float* dx, int lddx, float* dgamma, float* dbeta,
                          int accumulate, hipStream_t stream);
+/* The grouped head in training mode with the statistics of ALL ranks: what nn.SyncBatchNorm.convert_sync_batchnorm (reference
+ * lafs_train.py:362-364) makes of the BatchNorm1d of face_pre_pro/ViT_face.py:1530-1533 in the per-group forward of :1556-1569.
+ * Forward and backward are each cut where the ranks meet; the exchange between the two halves is the caller's (torch.distributed,
+ * outside the graphs).  group_rows is this rank's row table as above, except that a group may hold a SINGLE row on a rank (no empty
+ * group); group_total is a HOST table of the G total row counts over all ranks (by value, like group_rows; each >= 2, >= this rank's
+ * own count, <= 2^24).  All four launches can be captured, use no atomics and walk the groups in order, one workgroup per 64 columns.
+ *
+ * lafs_bn1d_groups_stats: this rank's partial statistics, partial f32 [G, 1 + 2 D] = per group {count, mean[D], M2[D]}, mean the
+ *   shifted sum and M2 = sum (x - mean)^2 the second pass of lafs_bn1d_fwd, operation for operation (one row: M2 = 0).
+ * lafs_bn1d_groups_sync_fwd: partials f32 = the W ranks' partials, rank r at partials + r ldw (ldw >= G (1 + 2 D) floats; W <=
+ *   LAFS_BN1D_MAX_RANKS).  Per group and column they are folded in rank order 0 .. W-1 with
+ *     n = n_a + n_b, delta = mean_b - mean_a, mean = mean_a + delta n_b / n, M2 = M2_a + M2_b + delta^2 n_a n_b / n
+ *   (the counts come from the partials), rstd = 1 / sqrt(M2 / N + eps); save_mean / save_rstd f32 [G, D]; the running buffers (both
+ *   or neither) take (1 - momentum) old + momentum {mean, M2 / N * (N / (N - 1))} once per group, group 0 first; y = this rank's rows
+ *   normalised.  The order is fixed, so every rank that is given the same partials computes the same bits.  W = 1: every output has
+ *   the bits of lafs_bn1d_groups_fwd (training).
+ * lafs_bn1d_groups_bwd_sums: sums f32 [G, 2 D] = per group {sum_r dy [D], sum_r dy xhat [D]} over this rank's rows, and dgamma /
+ *   dbeta = (accumulate ? old : 0) + those sums added in group order: rank-local, as in torch's SyncBatchNorm (the gradient
+ *   all-reduce treats them like every other parameter gradient).
+ * lafs_bn1d_groups_sync_bwd: sums = the sums of all ranks added up; dx = gamma rstd (dy - sum dy / N - xhat sum(dy xhat) / N) for this
+ *   rank's rows, N = group_total[g].  With the sums of the one rank (W = 1) the two launches give the bits of lafs_bn1d_groups_bwd. */
+#define LAFS_BN1D_MAX_RANKS 4096
+int lafs_bn1d_groups_stats(const float* x, int ldx, const int* group_rows, int G, int D, float* partial, hipStream_t stream);
+int lafs_bn1d_groups_sync_fwd(const float* x, int ldx, const int* group_rows, const int* group_total, int G, int D, const float* partials,
+                              int W, int64_t ldw, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                              float* running_var, float* y, int ldy, float* save_mean, float* save_rstd, hipStream_t stream);
+int lafs_bn1d_groups_bwd_sums(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, int G, int D,
+                              const float* save_mean, const float* save_rstd, float* sums, float* dgamma, float* dbeta, int accumulate,
+                              hipStream_t stream);
+int lafs_bn1d_groups_sync_bwd(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, const int* group_total, int G,
+                              int D, const float* save_mean, const float* save_rstd, const float* gamma, const float* sums, float* dx,
+                              int lddx, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DINO head pieces  (vision_transformer.py:284-287, 299-300)

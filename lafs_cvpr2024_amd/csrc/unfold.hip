@@ -108,36 +108,58 @@ __device__ __forceinline__ float bn_combine(float (*red)[64], float v, int w, in
   return s;
 }
 
-// One group of rows through the forward: the whole arithmetic of lafs_bn1d_fwd, shared by the single-group kernel and the grouped
-// one so that the two give the same bits.  Every thread of the workgroup calls it (barriers inside); `on`: this lane has a column.
+// The pieces of one group of rows through the forward.  lafs_bn1d_fwd, the grouped kernel and the cross-rank pair (statistics /
+// sync forward) are all made of them, so that they give the same bits wherever they compute the same thing.  Every thread of the
+// workgroup calls them (barriers inside bn_moments_rows); `on`: this lane has a column.
+// mean = x0 + sum(x - x0) / n and M2 = sum (x - mean)^2 of the n rows
+__device__ __forceinline__ void bn_moments_rows(float (*red)[64], const float* __restrict__ x, int ldx, int n, int col, bool on, int w,
+                                                int lane, float& mean, float& m2) {
+  const float x0 = on ? x[col] : 0.f;
+  float s = 0.f;
+  if (on) for (int r = w; r < n; r += BN_WAVES) s += x[(size_t)r * ldx + col] - x0;
+  s = bn_combine(red, s, w, lane);
+  mean = x0 + s / (float)n;
+  float q = 0.f;
+  if (on) for (int r = w; r < n; r += BN_WAVES) { const float d = x[(size_t)r * ldx + col] - mean; q = __builtin_fmaf(d, d, q); }
+  m2 = bn_combine(red, q, w, lane);
+}
+
+// rstd of the batch statistics (mean, M2) of nf rows; wave 0's lane of the column steps the running buffers (unbiased variance)
+__device__ __forceinline__ float bn_batch_rstd(float mean, float m2, float nf, float eps, float momentum, float* __restrict__ running_mean,
+                                               float* __restrict__ running_var, int col, bool on, int w) {
+  const float var = m2 / nf;
+  const float rstd = 1.0f / sqrtf(var + eps);
+  if (on && w == 0 && running_mean != nullptr) {
+    running_mean[col] = (1.0f - momentum) * running_mean[col] + momentum * mean;
+    running_var[col] = (1.0f - momentum) * running_var[col] + momentum * (var * (nf / (nf - 1.0f)));
+  }
+  return rstd;
+}
+
+__device__ __forceinline__ void bn_apply_rows(const float* __restrict__ x, int ldx, int n, float mean, float rstd,
+                                              const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ y, int ldy,
+                                              float* __restrict__ save_mean, float* __restrict__ save_rstd, int col, bool on, int w) {
+  if (!on) return;
+  if (w == 0) { save_mean[col] = mean; save_rstd[col] = rstd; }
+  const float g = gamma[col], bt = beta[col];
+  for (int r = w; r < n; r += BN_WAVES) y[(size_t)r * ldy + col] = (x[(size_t)r * ldx + col] - mean) * rstd * g + bt;
+}
+
+// One group of rows through the forward: the whole arithmetic of lafs_bn1d_fwd, shared by the single-group kernel and the grouped one.
 __device__ __forceinline__ void bn_fwd_rows(float (*red)[64], const float* __restrict__ x, int ldx, int n, const float* __restrict__ gamma,
                                             const float* __restrict__ beta, float eps, float momentum, int training,
                                             float* __restrict__ running_mean, float* __restrict__ running_var, float* __restrict__ y, int ldy,
                                             float* __restrict__ save_mean, float* __restrict__ save_rstd, int col, bool on, int w, int lane) {
   float mean = 0.f, rstd = 0.f;
   if (training) {
-    const float x0 = on ? x[col] : 0.f;
-    float s = 0.f;
-    if (on) for (int r = w; r < n; r += BN_WAVES) s += x[(size_t)r * ldx + col] - x0;
-    s = bn_combine(red, s, w, lane);
-    mean = x0 + s / (float)n;
-    float q = 0.f;
-    if (on) for (int r = w; r < n; r += BN_WAVES) { const float d = x[(size_t)r * ldx + col] - mean; q = __builtin_fmaf(d, d, q); }
-    q = bn_combine(red, q, w, lane);
-    const float var = q / (float)n;
-    rstd = 1.0f / sqrtf(var + eps);
-    if (on && w == 0 && running_mean != nullptr) {
-      running_mean[col] = (1.0f - momentum) * running_mean[col] + momentum * mean;
-      running_var[col] = (1.0f - momentum) * running_var[col] + momentum * (var * ((float)n / (float)(n - 1)));
-    }
+    float m2;
+    bn_moments_rows(red, x, ldx, n, col, on, w, lane, mean, m2);
+    rstd = bn_batch_rstd(mean, m2, (float)n, eps, momentum, running_mean, running_var, col, on, w);
   } else if (on) {
     mean = running_mean[col];
     rstd = 1.0f / sqrtf(running_var[col] + eps);
   }
-  if (!on) return;
-  if (w == 0) { save_mean[col] = mean; save_rstd[col] = rstd; }
-  const float g = gamma[col], bt = beta[col];
-  for (int r = w; r < n; r += BN_WAVES) y[(size_t)r * ldy + col] = (x[(size_t)r * ldx + col] - mean) * rstd * g + bt;
+  bn_apply_rows(x, ldx, n, mean, rstd, gamma, beta, y, ldy, save_mean, save_rstd, col, on, w);
 }
 
 __global__ __launch_bounds__(64 * BN_WAVES) void bn1d_fwd_kernel(const float* __restrict__ x, int ldx, int n, int D,
@@ -153,13 +175,13 @@ __global__ __launch_bounds__(64 * BN_WAVES) void bn1d_fwd_kernel(const float* __
 }
 
 // training: dx = gamma rstd (dy - mean(dy) - xhat mean(dy xhat));  eval (statistics are constants): dx = gamma rstd dy
-__device__ __forceinline__ void bn_bwd_rows(float (*red)[64], const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
-                                            int n, const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
-                                            const float* __restrict__ gamma, int training, float* __restrict__ dx, int lddx,
-                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate, int col, bool on, int w,
-                                            int lane) {
-  const float mean = on ? save_mean[col] : 0.f, rstd = on ? save_rstd[col] : 0.f;
-  float sb = 0.f, sg = 0.f;
+// The two halves of one group's backward, shared like the forward's pieces: the column sums of dy and dy xhat (added into dgamma /
+// dbeta by wave 0's lane of the column) and dx from the two means mb = sum dy / N, mg = sum dy xhat / N.
+__device__ __forceinline__ void bn_bwd_sums_rows(float (*red)[64], const float* __restrict__ dy, int lddy, const float* __restrict__ x,
+                                                 int ldx, int n, float mean, float rstd, float* __restrict__ dgamma,
+                                                 float* __restrict__ dbeta, int accumulate, int col, bool on, int w, int lane, float& sb,
+                                                 float& sg) {
+  sb = 0.f; sg = 0.f;
   if (on)
     for (int r = w; r < n; r += BN_WAVES) {
       const float d = dy[(size_t)r * lddy + col];
@@ -168,17 +190,33 @@ __device__ __forceinline__ void bn_bwd_rows(float (*red)[64], const float* __res
     }
   sb = bn_combine(red, sb, w, lane);
   sg = bn_combine(red, sg, w, lane);
-  if (!on) return;
-  if (w == 0) {
+  if (on && w == 0) {
     dgamma[col] = accumulate ? dgamma[col] + sg : sg;
     dbeta[col] = accumulate ? dbeta[col] + sb : sb;
   }
+}
+
+__device__ __forceinline__ void bn_bwd_apply_rows(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx, int n,
+                                                  float mean, float rstd, const float* __restrict__ gamma, float mb, float mg,
+                                                  float* __restrict__ dx, int lddx, int col, bool on, int w) {
+  if (!on) return;
   const float gr = gamma[col] * rstd;
-  const float mb = training ? sb / (float)n : 0.f, mg = training ? sg / (float)n : 0.f;
   for (int r = w; r < n; r += BN_WAVES) {
     const float xh = (x[(size_t)r * ldx + col] - mean) * rstd;
     dx[(size_t)r * lddx + col] = gr * (dy[(size_t)r * lddy + col] - mb - xh * mg);
   }
+}
+
+__device__ __forceinline__ void bn_bwd_rows(float (*red)[64], const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
+                                            int n, const float* __restrict__ save_mean, const float* __restrict__ save_rstd,
+                                            const float* __restrict__ gamma, int training, float* __restrict__ dx, int lddx,
+                                            float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate, int col, bool on, int w,
+                                            int lane) {
+  const float mean = on ? save_mean[col] : 0.f, rstd = on ? save_rstd[col] : 0.f;
+  float sb, sg;
+  bn_bwd_sums_rows(red, dy, lddy, x, ldx, n, mean, rstd, dgamma, dbeta, accumulate, col, on, w, lane, sb, sg);
+  const float mb = training ? sb / (float)n : 0.f, mg = training ? sg / (float)n : 0.f;
+  bn_bwd_apply_rows(dy, lddy, x, ldx, n, mean, rstd, gamma, mb, mg, dx, lddx, col, on, w);
 }
 
 __global__ __launch_bounds__(64 * BN_WAVES) void bn1d_bwd_kernel(const float* __restrict__ dy, int lddy, const float* __restrict__ x, int ldx,
@@ -228,6 +266,94 @@ __global__ __launch_bounds__(64 * BN_WAVES) void bn1d_groups_bwd_kernel(const fl
     bn_bwd_rows(red, dy + (size_t)r0 * lddy, lddy, x + (size_t)r0 * ldx, ldx, gr.rows[g + 1] - r0, save_mean + (size_t)g * D,
                 save_rstd + (size_t)g * D, gamma, training, dx + (size_t)r0 * lddx, lddx, dgamma, dbeta, (g > 0 || accumulate) ? 1 : 0, col,
                 col < D, w, lane);
+  }
+}
+
+
+// ---- The grouped head in training mode with the statistics of ALL ranks (the reference's SyncBatchNorm conversion, lafs_train.py:
+// 362-364): forward and backward are each cut where the ranks meet.  A rank's partial of a group is {count, mean[D], M2[D]} (f32
+// [G, 1 + 2 D]); the W partials of a group are folded in rank order 0 .. W-1 by the pairwise update (Chan et al.), the same sequence
+// of operations on every rank: bit-identical statistics and running buffers everywhere.  One partial (W = 1) is taken as it is.
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_groups_stats_kernel(const float* __restrict__ x, int ldx, BnGroupRows gr, int G, int D,
+                                                                          float* __restrict__ partial) {
+  __shared__ float red[BN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  const bool on = col < D;
+  for (int g = 0; g < G; ++g) {
+    const int r0 = gr.rows[g], n = gr.rows[g + 1] - r0;
+    float mean, m2;
+    bn_moments_rows(red, x + (size_t)r0 * ldx, ldx, n, col, on, w, lane, mean, m2);
+    float* p = partial + (size_t)g * (1 + 2 * D);
+    if (w == 0 && on) { p[1 + col] = mean; p[1 + D + col] = m2; }
+    if (w == 0 && col == 0) p[0] = (float)n;
+  }
+}
+
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_groups_sync_fwd_kernel(const float* __restrict__ x, int ldx, BnGroupRows gr, int G,
+                                                                             int D, const float* __restrict__ partials, int W, size_t ldw,
+                                                                             const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                             float eps, float momentum, float* __restrict__ running_mean,
+                                                                             float* __restrict__ running_var, float* __restrict__ y, int ldy,
+                                                                             float* __restrict__ save_mean, float* __restrict__ save_rstd) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  const bool on = col < D;
+  for (int g = 0; g < G; ++g) {
+    const float* p = partials + (size_t)g * (1 + 2 * D);
+    float nf = p[0], mean = on ? p[1 + col] : 0.f, m2 = on ? p[1 + D + col] : 0.f;
+    for (int r = 1; r < W; ++r) {                         // (every wave folds its own copy: W small numbers, no barrier)
+      const float* q = p + (size_t)r * ldw;
+      const float nb = q[0], mean_b = on ? q[1 + col] : 0.f, m2_b = on ? q[1 + D + col] : 0.f;
+      const float nn = nf + nb, delta = mean_b - mean;
+      mean = mean + delta * nb / nn;
+      m2 = m2 + m2_b + delta * delta * nf * nb / nn;
+      nf = nn;
+    }
+    const float rstd = bn_batch_rstd(mean, m2, nf, eps, momentum, running_mean, running_var, col, on, w);
+    const int r0 = gr.rows[g];
+    bn_apply_rows(x + (size_t)r0 * ldx, ldx, gr.rows[g + 1] - r0, mean, rstd, gamma, beta, y + (size_t)r0 * ldy, ldy,
+                  save_mean + (size_t)g * D, save_rstd + (size_t)g * D, col, on, w);
+  }
+}
+
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_groups_bwd_sums_kernel(const float* __restrict__ dy, int lddy,
+                                                                             const float* __restrict__ x, int ldx, BnGroupRows gr, int G,
+                                                                             int D, const float* __restrict__ save_mean,
+                                                                             const float* __restrict__ save_rstd, float* __restrict__ sums,
+                                                                             float* __restrict__ dgamma, float* __restrict__ dbeta,
+                                                                             int accumulate) {
+  __shared__ float red[BN_WAVES][64];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  const bool on = col < D;
+  for (int g = 0; g < G; ++g) {
+    const int r0 = gr.rows[g];
+    const float mean = on ? save_mean[(size_t)g * D + col] : 0.f, rstd = on ? save_rstd[(size_t)g * D + col] : 0.f;
+    float sb, sg;
+    bn_bwd_sums_rows(red, dy + (size_t)r0 * lddy, lddy, x + (size_t)r0 * ldx, ldx, gr.rows[g + 1] - r0, mean, rstd, dgamma, dbeta,
+                     (g > 0 || accumulate) ? 1 : 0, col, on, w, lane, sb, sg);
+    if (w == 0 && on) { sums[(size_t)g * 2 * D + col] = sb; sums[(size_t)g * 2 * D + D + col] = sg; }
+  }
+}
+
+__global__ __launch_bounds__(64 * BN_WAVES) void bn1d_groups_sync_bwd_kernel(const float* __restrict__ dy, int lddy,
+                                                                             const float* __restrict__ x, int ldx, BnGroupRows gr,
+                                                                             BnGroupRows total, int G, int D,
+                                                                             const float* __restrict__ save_mean,
+                                                                             const float* __restrict__ save_rstd,
+                                                                             const float* __restrict__ gamma, const float* __restrict__ sums,
+                                                                             float* __restrict__ dx, int lddx) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int col = blockIdx.x * 64 + lane;
+  const bool on = col < D;
+  for (int g = 0; g < G; ++g) {
+    const int r0 = gr.rows[g];
+    const float mean = on ? save_mean[(size_t)g * D + col] : 0.f, rstd = on ? save_rstd[(size_t)g * D + col] : 0.f;
+    const float sb = on ? sums[(size_t)g * 2 * D + col] : 0.f, sg = on ? sums[(size_t)g * 2 * D + D + col] : 0.f;
+    const float mb = sb / (float)total.rows[g], mg = sg / (float)total.rows[g];
+    bn_bwd_apply_rows(dy + (size_t)r0 * lddy, lddy, x + (size_t)r0 * ldx, ldx, gr.rows[g + 1] - r0, mean, rstd, gamma, mb, mg,
+                      dx + (size_t)r0 * lddx, lddx, col, on, w);
   }
 }
 
@@ -313,13 +439,13 @@ extern "C" int lafs_bn1d_bwd(const float* dy, int lddy, const float* x, int ldx,
 }
 
 // validates the host row table and copies it into the launch argument; the reason of a refusal, or nullptr
-static const char* bn_group_rows(const int* group_rows, int G, int training, BnGroupRows* out) {
+static const char* bn_group_rows(const int* group_rows, int G, int min_rows, BnGroupRows* out) {
   if (group_rows == nullptr) return "null operand";
   if (G < 1 || G > LAFS_BN1D_MAX_GROUPS) return "1 <= G <= LAFS_BN1D_MAX_GROUPS";
   if (group_rows[0] != 0) return "group_rows[0] must be 0";
   for (int g = 0; g < G; ++g) {
     if (group_rows[g + 1] <= group_rows[g]) return "group_rows must ascend strictly (no empty group)";
-    if (training && group_rows[g + 1] - group_rows[g] < 2) return "batch statistics need more than one row in every group";
+    if (group_rows[g + 1] - group_rows[g] < min_rows) return "batch statistics need more than one row in every group";
   }
   for (int g = 0; g <= LAFS_BN1D_MAX_GROUPS; ++g) out->rows[g] = g <= G ? group_rows[g] : group_rows[G];
   return nullptr;
@@ -332,7 +458,7 @@ extern "C" int lafs_bn1d_groups_fwd(const float* x, int ldx, const int* group_ro
   LAFS_CHECK_ARG(x && gamma && beta && y && save_mean && save_rstd, "null operand");
   LAFS_CHECK_ARG(D > 0 && D <= 2048 && ldx >= D && ldy >= D, "1 <= D <= 2048 and row strides >= D");
   BnGroupRows gr;
-  const char* why = bn_group_rows(group_rows, G, training, &gr);
+  const char* why = bn_group_rows(group_rows, G, training ? 2 : 1, &gr);
   LAFS_CHECK_ARG(why == nullptr, why);
   LAFS_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "running_mean and running_var come together");
   LAFS_CHECK_ARG(training || running_mean != nullptr, "the eval forward normalises with the running statistics");
@@ -349,10 +475,88 @@ extern "C" int lafs_bn1d_groups_bwd(const float* dy, int lddy, const float* x, i
   LAFS_CHECK_ARG(dy && x && save_mean && save_rstd && gamma && dx && dgamma && dbeta, "null operand");
   LAFS_CHECK_ARG(D > 0 && D <= 2048 && lddy >= D && ldx >= D && lddx >= D, "1 <= D <= 2048 and row strides >= D");
   BnGroupRows gr;
-  const char* why = bn_group_rows(group_rows, G, training, &gr);
+  const char* why = bn_group_rows(group_rows, G, training ? 2 : 1, &gr);
   LAFS_CHECK_ARG(why == nullptr, why);
   hipLaunchKernelGGL(bn1d_groups_bwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, dy, lddy, x, ldx, gr, G, D, save_mean,
                      save_rstd, gamma, training ? 1 : 0, dx, lddx, dgamma, dbeta, accumulate ? 1 : 0);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+// the total row counts of the groups over all ranks (host table of G entries, by value like the row table); the reason of a refusal
+static const char* bn_group_totals(const int* group_total, const BnGroupRows& gr, int G, BnGroupRows* out) {
+  if (group_total == nullptr) return "null operand";
+  for (int g = 0; g < G; ++g) {
+    if (group_total[g] < gr.rows[g + 1] - gr.rows[g]) return "a group's total row count is below this rank's own";
+    if (group_total[g] < 2) return "batch statistics need more than one row per group over all ranks";
+    if (group_total[g] > (1 << 24)) return "a group's total row count must be exact in f32 (<= 2^24)";
+  }
+  for (int g = 0; g <= LAFS_BN1D_MAX_GROUPS; ++g) out->rows[g] = g < G ? group_total[g] : 0;
+  return nullptr;
+}
+
+extern "C" int lafs_bn1d_groups_stats(const float* x, int ldx, const int* group_rows, int G, int D, float* partial, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(x && partial, "null operand");
+  LAFS_CHECK_ARG(D > 0 && D <= 2048 && ldx >= D, "1 <= D <= 2048 and row strides >= D");
+  BnGroupRows gr;
+  const char* why = bn_group_rows(group_rows, G, 1, &gr);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  hipLaunchKernelGGL(bn1d_groups_stats_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, x, ldx, gr, G, D, partial);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_bn1d_groups_sync_fwd(const float* x, int ldx, const int* group_rows, const int* group_total, int G, int D,
+                                         const float* partials, int W, int64_t ldw, const float* gamma, const float* beta, float eps,
+                                         float momentum, float* running_mean, float* running_var, float* y, int ldy, float* save_mean,
+                                         float* save_rstd, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(x && partials && gamma && beta && y && save_mean && save_rstd, "null operand");
+  LAFS_CHECK_ARG(D > 0 && D <= 2048 && ldx >= D && ldy >= D, "1 <= D <= 2048 and row strides >= D");
+  LAFS_CHECK_ARG(W >= 1 && W <= LAFS_BN1D_MAX_RANKS, "1 <= W <= LAFS_BN1D_MAX_RANKS");
+  LAFS_CHECK_ARG(G >= 1 && G <= LAFS_BN1D_MAX_GROUPS && (W == 1 || ldw >= (int64_t)G * (1 + 2 * D)),
+                 "1 <= G <= LAFS_BN1D_MAX_GROUPS and the ranks' partials must not overlap (ldw >= G (1 + 2 D))");
+  BnGroupRows gr, total;
+  const char* why = bn_group_rows(group_rows, G, 1, &gr);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  why = bn_group_totals(group_total, gr, G, &total);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  LAFS_CHECK_ARG((running_mean == nullptr) == (running_var == nullptr), "running_mean and running_var come together");
+  hipLaunchKernelGGL(bn1d_groups_sync_fwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, x, ldx, gr, G, D, partials, W,
+                     (size_t)ldw, gamma, beta, eps, momentum, running_mean, running_var, y, ldy, save_mean, save_rstd);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_bn1d_groups_bwd_sums(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, int G, int D,
+                                         const float* save_mean, const float* save_rstd, float* sums, float* dgamma, float* dbeta,
+                                         int accumulate, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(dy && x && save_mean && save_rstd && sums && dgamma && dbeta, "null operand");
+  LAFS_CHECK_ARG(D > 0 && D <= 2048 && lddy >= D && ldx >= D, "1 <= D <= 2048 and row strides >= D");
+  BnGroupRows gr;
+  const char* why = bn_group_rows(group_rows, G, 1, &gr);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  hipLaunchKernelGGL(bn1d_groups_bwd_sums_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, dy, lddy, x, ldx, gr, G, D,
+                     save_mean, save_rstd, sums, dgamma, dbeta, accumulate ? 1 : 0);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_bn1d_groups_sync_bwd(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, const int* group_total,
+                                         int G, int D, const float* save_mean, const float* save_rstd, const float* gamma,
+                                         const float* sums, float* dx, int lddx, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(dy && x && save_mean && save_rstd && gamma && sums && dx, "null operand");
+  LAFS_CHECK_ARG(D > 0 && D <= 2048 && lddy >= D && ldx >= D && lddx >= D, "1 <= D <= 2048 and row strides >= D");
+  BnGroupRows gr, total;
+  const char* why = bn_group_rows(group_rows, G, 1, &gr);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  why = bn_group_totals(group_total, gr, G, &total);
+  LAFS_CHECK_ARG(why == nullptr, why);
+  hipLaunchKernelGGL(bn1d_groups_sync_bwd_kernel, dim3(ceil_div(D, 64)), dim3(64 * BN_WAVES), 0, stream, dy, lddy, x, ldx, gr, total, G, D,
+                     save_mean, save_rstd, gamma, sums, dx, lddx);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }

@@ -18,7 +18,7 @@ import torch.distributed as dist
 
 from . import _lib, functional as Fn, ops
 from .arena import ParamArena
-from .distributed import FlatReducer
+from .distributed import BnStatExchange, FlatReducer
 from .ops import _p, call
 from .utils import PinnedRing
 from .vision_transformer import VisionTransformer, attach_arena, _is_matrix_for_dgrad
@@ -35,9 +35,10 @@ def _is_fvit(m):
 
 
 # The reference converts both networks to SyncBatchNorm before it wraps them (lafs_train.py:362-364): fViT's BatchNorm1d head then
-# normalises with the statistics of the cls rows of ALL ranks.  lafs_bn1d_groups_fwd sees one rank's rows.
+# normalises with the statistics of the cls rows of ALL ranks.  lafs_bn1d_groups_fwd sees one rank's rows; the cross-rank form
+# (lafs_bn1d_groups_stats / _sync_fwd / _bwd_sums / _sync_bwd with two small collectives between them) is behind `sync_bn`.
 FVIT_MULTI_RANK = ("fViT pre-training on more than one rank needs SyncBatchNorm statistics across the ranks (reference "
-                   "lafs_train.py:362-364), which are not implemented: run --arch fvit on a single rank")
+                   "lafs_train.py:362-364): pass sync_bn=True (lafs_train.py --sync_bn true), or run --arch fvit on a single rank")
 
 f32, bf16 = torch.float32, torch.bfloat16
 
@@ -56,7 +57,7 @@ def _interp_matrix(grid_src, grid_dst, device):
 
 class LafsPretrainEngine:
     def __init__(self, student, teacher, dino_loss, batch_size, n_local=8, global_size=112, local_size=48,
-                 clip_grad=3.0, freeze_last_layer=1, use_graph=True, device=None, grad_slices=4):
+                 clip_grad=3.0, freeze_last_layer=1, use_graph=True, device=None, grad_slices=4, sync_bn=False):
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
         self.student, self.teacher, self.dino_loss = student, teacher, dino_loss
         self.B, self.n_local, self.ncrops = batch_size, n_local, 2 + n_local
@@ -77,8 +78,15 @@ class LafsPretrainEngine:
         self.facevit = self.partfvit or self.fvit
         if not (isinstance(vit_s, VisionTransformer) or self.facevit) or type(vit_s) is not type(vit_t):
             raise _lib.LafsHipError("LafsPretrainEngine drives a VisionTransformer, a ViT_face_landmark_patch8 or a ViTs_face_overlap pair")
-        if self.fvit and self.world > 1:
+        if self.fvit and self.world > 1 and not sync_bn:
             raise _lib.LafsHipError(FVIT_MULTI_RANK)
+        # sync_bn (fViT pairs only): the head normalises every crop group with the statistics of the cls rows of ALL ranks.  The forward
+        # segment is cut twice around the exchange of the partial statistics, the head backward once around the all-reduce of its two
+        # sums (_seg_forward_a / _seg_forward_b / _seg_trunk_backward).  One rank has nobody to exchange with: it takes this segmented
+        # form only where it runs the multi-rank launch structure anyway (LAFS_ONE_GRAPH=0), else the plain kernels -- the same bits.
+        self.sync_bn = bool(sync_bn) and self.fvit and (self.world > 1 or os.environ.get("LAFS_ONE_GRAPH", "1") == "0")
+        self.n_fwd = 2 if self.sync_bn else 1                # graph segments of the forward
+        self._bn_sums_live = False
         if self.fvit and (vit_s.ac_patch_size, vit_s.patch_size, vit_s.pad) != (vit_t.ac_patch_size, vit_t.patch_size, vit_t.pad):
             raise _lib.LafsHipError("student and teacher fViT must embed with the same window")
         if self.partfvit and (vit_s.with_land or vit_t.with_land):
@@ -109,7 +117,8 @@ class LafsPretrainEngine:
         self.sa.ctx = self.ta.ctx = self.ctx
         dino_loss.to(self.device)
         if self.world > 1:                       # DDP's initial parameter broadcast (reference lafs_train.py:375)
-            for t in (self.sa.master, self.ta.master, dino_loss.center):
+            bn = [b for m in (vit_s.mlp_head[0], vit_t.mlp_head[0]) for b in m.buffers()] if self.fvit else []      # (DDP: buffers too)
+            for t in [self.sa.master, self.ta.master, dino_loss.center] + bn:
                 dist.broadcast(t, 0)
             self.sa.refresh_shadows(); self.ta.refresh_shadows()
         self.K = student.head.out_dim
@@ -125,8 +134,9 @@ class LafsPretrainEngine:
         self.grids = [global_size // 8] + ([local_size // 8] if n_local else [])
         if self.fvit:                                # windows per side: 14 and 6 for 112 / 48 px at 12 / 8 / 4
             self.grids = [ops.unfold_windows(s, *window) for s in [global_size] + ([local_size] if n_local else [])]
-            if self.B < 2:
-                raise _lib.LafsHipError("fViT's BatchNorm1d head needs more than one row per crop group: batch_size >= 2")
+            if self.B * (self.world if self.sync_bn else 1) < 2:
+                raise _lib.LafsHipError("fViT's BatchNorm1d head needs more than one row per crop group: batch_size >= 2 "
+                                        "(with sync_bn: batch_size x ranks >= 2)")
             self.bn_s, self.bn_t = vit_s.mlp_head[0], vit_t.mlp_head[0]
         if self.facevit:
             if vit_s.num_patches < self.grids[0] ** 2:
@@ -202,6 +212,11 @@ class LafsPretrainEngine:
         off = lambda blk: self.sa.offsets[self.spec_s.trunk.block_names[blk]["ln1_g"]] if blk > 0 else 0
         self.cut_offsets = [off(c) for c in self.cuts[1:]]                                   # arena offset where each run starts
         self.reducer = FlatReducer()
+        if self.sync_bn:
+            # student and teacher partials in one buffer (one collective); the groups' row counts over all ranks
+            self.bn_x = BnStatExchange([len(self.geom_s.groups), len(self.geom_t.groups)], D, dev, self.reducer)
+            self.bn_total_s = [n * self.world for n, _ in self.geom_s.groups]
+            self.bn_total_t = [n * self.world for n, _ in self.geom_t.groups]
         if self.world > 1:
             # LAFS_COMM_CUS=n (opt-in, default 0) shrinks the K-resident GEMM's grid by 2 n workgroups while gradients are on the
             # wire.  It does not reserve CUs (the dispatcher still spreads the remaining workgroups over the chip) and has never been
@@ -222,10 +237,11 @@ class LafsPretrainEngine:
         for (lo, hi), (s_lo, s_hi) in zip(self.pieces, self.piece_segs):        # a piece is whole tensors: its first / last chunk carry its first / last segment
             assert lo % _lib.CHUNK == 0 and hi % _lib.CHUNK == 0 and 0 <= s_lo < s_hi <= self.sa.n_seg
             assert int(chunk_seg[lo // _lib.CHUNK]) == s_lo and int(chunk_seg[hi // _lib.CHUNK - 1]) == s_hi - 1, (lo, hi, s_lo, s_hi)
-        n_segments = len(self.cuts) + 1                     # forward, the runs of the trunk backward, the final update
+        n_segments = self.n_fwd + len(self.cuts)            # forward (two with sync_bn), the runs of the trunk backward, the final update
+        self.n_segments = n_segments
         slack = 1 if self.world > 1 else 0
         serial = os.environ.get("LAFS_OPT_OVERLAP", "1") == "0"          # A/B knob: every piece in the final segment
-        self.piece_runs_at = [n_segments - 1 if serial else min(p + 1 + slack, n_segments - 1) for p in range(len(self.pieces))]
+        self.piece_runs_at = [n_segments - 1 if serial else min(p + self.n_fwd + slack, n_segments - 1) for p in range(len(self.pieces))]
         self._piece_tokens = [[] for _ in self.pieces]
         self.opt_stream = None if os.environ.get("LAFS_SINGLE_STREAM") == "1" else torch.cuda.Stream(device=self.device)
         # large frozen tensors (Part-fViT's 30000 x 768 CosFace table: 92 MB of zeros per step on the wire otherwise) are cut out
@@ -324,6 +340,11 @@ class LafsPretrainEngine:
             self.bn_s.num_batches_tracked.add_(len(self.geom_s.groups))
         _, st_h = Fn.head_forward(sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)
         cur.wait_stream(side)
+        self._st = dict(vit=st_v, dfeat=self._head_loss_backward(st_h, st_ht))
+
+    def _head_loss_backward(self, st_h, st_ht):
+        """Last layer of both heads, DINO loss forward + backward, center column sums, student head backward.  Returns dfeat."""
+        sa, B = self.sa, self.B
         if self.fused_head:
             # last layer of both heads + loss forward + dL/dlogits + center column sums, the logits never stored
             ops.dino_head_loss(st_h.zn, st_ht.zn, st_h.wn, st_ht.wn, self.dino_loss.center.view(-1), self.ncrops, self.K,
@@ -336,16 +357,69 @@ class LafsPretrainEngine:
                                   loss=self.loss, dev_temps=self.temps)
             call("lafs_colsum_f32", _p(self._logits_t), self.Kpad, 2 * B, self.K, _p(self.colsum))
         train_g = self.student.head.last_layer.weight_g.requires_grad
-        dfeat = Fn.head_backward(sa, self.head_prefix_s, st_h, self.dlogits, train_g=train_g, overwrite_last=True)
-        self._st = dict(vit=st_v, dfeat=dfeat)
         self._head_states = (st_h, st_ht)
+        return Fn.head_backward(sa, self.head_prefix_s, st_h, self.dlogits, train_g=train_g, overwrite_last=True)
+
+    def _seg_forward_a(self):
+        """sync_bn, first forward segment: both trunks to their cls rows and this rank's partial statistics of every crop group, written
+        into this rank's slots of the (zeroed) exchange buffer.  A network in eval mode needs no exchange and runs its head here."""
+        sa, ta = self.sa, self.ta
+        call("lafs_zero_chunks", _p(sa.grad), _p(sa.chunk_seg), _p(sa.seg_flags), sa.n_chunks, _lib.SEG_OVERWRITTEN)
+        self.bn_x.clear()
+        cur = torch.cuda.current_stream()
+        side = self.side_stream if self.side_stream is not None else cur
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            pos_t = self._pos_tokens(ta, self.spec_t, self.pos_t)[:1]
+            vit_t = self.teacher.backbone
+            drop_t = self._drop_scales(self.keep_t, self.drop_t, 1) if vit_t.training else None
+            feat_t, st_t, _ = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False,
+                                             dropout=self._dropout_cfg(vit_t, self.dropout_seed_t), bn_training=vit_t.training,
+                                             bn_partial=self.bn_x.slot(1) if vit_t.training else None)
+        vit = self.student.backbone
+        drop = self._drop_scales(self.keep_s, self.drop_s, 0) if vit.training else None
+        imgs = [self.in_global_all] + ([self.in_local_all] if self.n_local else [])
+        feat_s, st_v, _ = Fn.vit_forward(sa, self.spec_s, self.geom_s, imgs, self._pos_tokens(sa, self.spec_s, self.pos_s), drop,
+                                         save=True, dropout=self._dropout_cfg(vit, self.dropout_seed_s), wgrad_overwrite=True,
+                                         wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0,
+                                         bn_training=vit.training, bn_partial=self.bn_x.slot(0) if vit.training else None)
+        cur.wait_stream(side)
+        self._st = dict(vit=st_v, vit_t=st_t, feat_s=feat_s, feat_t=feat_t)
+
+    def _seg_forward_b(self):
+        """sync_bn, second forward segment (the exchange buffer now holds the partials of all ranks): BatchNorm of both networks with
+        the combined statistics (running buffers and num_batches_tracked as in the one-rank forward), heads, loss, head backward and
+        this rank's two sums of the BatchNorm backward."""
+        sa, ta, st = self.sa, self.ta, self._st
+        cur = torch.cuda.current_stream()
+        side = self.side_stream if self.side_stream is not None else cur
+        side.wait_stream(cur)
+        with torch.cuda.stream(side):
+            feat_t = st["feat_t"]
+            if feat_t is None:
+                feat_t = Fn.vit_forward_sync_bn(ta, self.spec_t, st["vit_t"], self.bn_x.all(1), self.bn_total_t)
+                self.bn_t.num_batches_tracked.add_(1)
+            _, st_ht = Fn.head_forward(ta, self.head_prefix_t, feat_t, self.K, save=False, logits=self._logits_t, skip_logits=self.fused_head)
+        feat_s = st["feat_s"]
+        self._bn_sums_live = feat_s is None
+        if feat_s is None:
+            feat_s = Fn.vit_forward_sync_bn(sa, self.spec_s, st["vit"], self.bn_x.all(0), self.bn_total_s)
+            self.bn_s.num_batches_tracked.add_(len(self.geom_s.groups))
+        _, st_h = Fn.head_forward(sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)
+        cur.wait_stream(side)
+        dfeat = self._head_loss_backward(st_h, st_ht)
+        if self._bn_sums_live:
+            Fn.vit_backward_bn_sums(sa, self.spec_s, st["vit"], dfeat, self.bn_x.sums)
+        self._st = dict(vit=st["vit"], dfeat=dfeat)
 
     def _seg_trunk_backward(self, k):
         """Run k of the trunk backward: blocks cuts[k]-1 .. cuts[k+1]; run 0 starts with the final norm, the last run ends with
         the patch embedding and the position table."""
         sa = self.sa
         if k == 0:
-            self._st["g"] = Fn.vit_backward_begin(sa, self.spec_s, self._st["vit"], self._st["dfeat"])
+            sync = self.sync_bn and self._bn_sums_live       # (the sums of all ranks: all-reduced between the segments)
+            self._st["g"] = Fn.vit_backward_begin(sa, self.spec_s, self._st["vit"], self._st["dfeat"],
+                                                  bn_sums=self.bn_x.sums if sync else None, bn_total=self.bn_total_s if sync else None)
         Fn.vit_backward_layers(self._st["vit"], self._st["g"], self.cuts[k], self.cuts[k + 1], wgrad_stream=self.side_stream)
         if k == len(self.cuts) - 2:
             gpe = sa.view(sa.grad, self.spec_s.prefix + self.pos_name).view(-1, self.spec_s.trunk.dim)
@@ -376,7 +450,7 @@ class LafsPretrainEngine:
         """Segment k = `body` with the update pieces scheduled at k: on their own stream beside the body (forked at the start, joined
         at the end: the pattern hipGraph captures), or -- in the final segment -- in line, followed by the W^T shadow refresh."""
         here = [p for p, at in enumerate(self.piece_runs_at) if at == k]
-        last = k == len(self.cuts)
+        last = k == self.n_segments - 1
         cur = torch.cuda.current_stream()
         if here and not last and self.opt_stream is not None:
             self.opt_stream.wait_stream(cur)
@@ -394,7 +468,8 @@ class LafsPretrainEngine:
 
     # ------------------------------------------------------------------ step
     def _segments(self):
-        bodies = [self._seg_forward] + [(lambda k=k: self._seg_trunk_backward(k)) for k in range(len(self.cuts) - 1)] + [self._seg_update]
+        forward = [self._seg_forward_a, self._seg_forward_b] if self.sync_bn else [self._seg_forward]
+        bodies = forward + [(lambda k=k: self._seg_trunk_backward(k)) for k in range(len(self.cuts) - 1)] + [self._seg_update]
         return [(lambda k=k, b=b: self._with_pieces(k, b)) for k, b in enumerate(bodies)]
 
     def _capture(self):
@@ -469,12 +544,22 @@ class LafsPretrainEngine:
                     self.reducer.wait(self._piece_tokens[p])
             replay(i)
         run(0)
+        nf = self.n_fwd
+        bn_tok = None
+        if self.sync_bn:
+            # the partial statistics of both networks meet (one collective on the step's critical path), the second forward segment
+            # runs, and the BatchNorm backward's sums go out FIRST: the trunk backward waits for them alone
+            self.reducer.wait([self.bn_x.gather()])
+            run(1)
+            bn_tok = self.bn_x.reduce_sums()
         # head gradients + center sums go out over RCCL while the trunk backward runs; each run of blocks follows as soon as
         # its graph segment has been enqueued (arena order: [embed | blocks 0..depth-1 | norm | head])
         self._piece_tokens[0] = self._reduce_range(*self.pieces[0])
         center_tok = self.reducer.launch(self.colsum)
         for k in range(len(self.cuts) - 1):
-            run(1 + k)
+            if k == 0:
+                self.reducer.wait([bn_tok])
+            run(nf + k)
             if 1 + k < len(self.pieces):
                 self._piece_tokens[1 + k] = self._reduce_range(*self.pieces[1 + k])
         self.reducer.wait([center_tok])

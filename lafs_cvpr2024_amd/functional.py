@@ -170,11 +170,13 @@ def bn_group_rows(geom: PackedGeometry):
 
 def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, drop_scales=None, save=True,
                 ws=None, x_in=None, x_out=None, dropout=None, wgrad_overwrite=False, wgrad_workgroups=0, wgrad_defer=False,
-                bn_training=False):
+                bn_training=False, bn_partial=None):
     """imgs: list of fp32 NCHW tensors (one per group); pos_tokens: list of fp32 [npatch+1, D] per group.
     dropout: None or (p_trunk, p_embedding, seed[, step]): element dropout of Part-fViT (counter-based masks, see lafs_hip.h);
     `step`: a DEVICE float tensor whose value x 7919 is added to the seed inside the kernels (graph-captured steps).
     bn_training (BatchNorm1d head only): batch statistics over the n_seq cls rows + running-statistic update, else running statistics.
+    bn_partial (BatchNorm1d head in training only): f32 [G, 1 + 2 D] that receives this rank's partial statistics of the cls rows
+    (lafs_bn1d_groups_stats); the pass STOPS there -- feat is None until vit_forward_sync_bn has the partials of all ranks.
     Returns (feat f32 [n_seq, D], state)."""
     D = spec.trunk.dim
     dev = imgs[0].device
@@ -225,6 +227,12 @@ def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, dr
     st.cls_rows = torch.empty(geom.n_seq, D, device=dev, dtype=f32)
     call("lafs_gather_cls", _p(x_out), D, _p(geom.cu_seqlens), geom.n_seq, D, _p(st.cls_rows))
     st.bn_training = bool(bn_training)
+    if bn_partial is not None:
+        if spec.head != "batchnorm" or not st.bn_training:
+            raise _lib.LafsHipError("bn_partial: cross-rank statistics are those of a BatchNorm1d head in training mode")
+        ops.bn1d_groups_stats(st.cls_rows, bn_group_rows(geom), out=bn_partial)
+        st.stats = st.feat = None
+        return None, st, x_out
     if spec.head == "batchnorm":
         rm, rv = arena.module.get_buffer(pre + spec.bn_mean), arena.module.get_buffer(pre + spec.bn_var)
         bn_g, bn_b = arena.view(arena.master, pre + spec.final_g), arena.view(arena.master, pre + spec.final_b)
@@ -242,6 +250,26 @@ def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, dr
         raise _lib.LafsHipError(f"unknown head kind {spec.head!r}")
     st.feat = feat
     return feat, st, x_out
+
+
+def vit_forward_sync_bn(arena, spec: ViTSpec, st: ViTState, partials, group_total):
+    """Second half of a vit_forward that stopped at `bn_partial`: the BatchNorm1d head with the statistics of all ranks
+    (partials f32 [W, G, 1 + 2 D] after the exchange, group_total the groups' row counts over all ranks).  Returns feat."""
+    pre = spec.prefix
+    rm, rv = arena.module.get_buffer(pre + spec.bn_mean), arena.module.get_buffer(pre + spec.bn_var)
+    feat, mean, rstd = ops.bn1d_groups_sync_fwd(st.cls_rows, bn_group_rows(st.geom), group_total, partials,
+                                                arena.view(arena.master, pre + spec.final_g), arena.view(arena.master, pre + spec.final_b),
+                                                spec.bn_eps, spec.bn_momentum, rm, rv)
+    st.stats, st.feat = (mean, rstd), feat
+    return feat
+
+
+def vit_backward_bn_sums(arena, spec: ViTSpec, st: ViTState, dfeat, sums):
+    """First half of the cross-rank head backward: this rank's sums of dy and dy xhat per group into `sums` f32 [G, 2 D], and into the
+    (rank-local) gradients of the head's weight / bias.  vit_backward_begin(..., bn_sums=, bn_total=) continues after the all-reduce."""
+    gv = lambda n: arena.view(arena.grad, spec.prefix + n)
+    return ops.bn1d_groups_bwd_sums(dfeat.contiguous().float(), st.cls_rows, bn_group_rows(st.geom), st.stats[0], st.stats[1],
+                                    gv(spec.final_g), gv(spec.final_b), accumulate=True, out=sums)
 
 
 # ----------------------------------------------------------------------------------------------- forward-only read-outs
@@ -298,12 +326,17 @@ def vit_block_probs(arena, spec: ViTSpec, geom: PackedGeometry, x, layer, q_rows
     return ops.attention_probs(qkv, geom.cu_seqlens, geom.max_len, t.heads, t.attn_scale, q_rows)
 
 
-def vit_backward_begin(arena, spec: ViTSpec, st: ViTState, dfeat, g_buf=None):
-    """Final-LayerNorm backward on the cls rows and scatter into the (zeroed) residual-gradient buffer.  Returns g."""
+def vit_backward_begin(arena, spec: ViTSpec, st: ViTState, dfeat, g_buf=None, bn_sums=None, bn_total=None):
+    """Final-LayerNorm backward on the cls rows and scatter into the (zeroed) residual-gradient buffer.  Returns g.
+    bn_sums / bn_total: the all-reduced sums of vit_backward_bn_sums and the groups' row counts over all ranks -- the head backward is
+    then only lafs_bn1d_groups_sync_bwd (the weight / bias gradients were written with the sums)."""
     geom, D, pre = st.geom, spec.trunk.dim, spec.prefix
     dev = dfeat.device
     gv = lambda n: arena.view(arena.grad, pre + n)
-    if spec.head == "batchnorm" and len(geom.groups) > 1:
+    if bn_sums is not None:
+        dcls_rows = ops.bn1d_groups_sync_bwd(dfeat.contiguous().float(), st.cls_rows, bn_group_rows(geom), bn_total, st.stats[0], st.stats[1],
+                                             arena.view(arena.master, pre + spec.final_g), bn_sums)
+    elif spec.head == "batchnorm" and len(geom.groups) > 1:
         dcls_rows = ops.bn1d_groups_bwd(dfeat.contiguous().float(), st.cls_rows, bn_group_rows(geom), st.stats[0], st.stats[1],
                                         arena.view(arena.master, pre + spec.final_g), st.bn_training, gv(spec.final_g), gv(spec.final_b),
                                         accumulate=True)

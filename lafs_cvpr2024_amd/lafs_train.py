@@ -13,7 +13,8 @@ Differences from the reference, all forced by its own breakage or by scope (SURV
     crop shapes the landmark gather emits (2 x 112^2 + n x 48^2), or pass any Dataset through `train_lafs(args, dataset=...)`
     yielding lists of 2 + n crops;
   * --arch fvit pre-trains ViTs_face_overlap (the overlapping-patch fViT with its BatchNorm1d head; --fvit_dims, --fvit_window,
-    --fvit_dropout), single rank only: the reference's SyncBatchNorm conversion (:362-364) has no counterpart here;
+    --fvit_dropout); on more than one rank it needs --sync_bn true, the counterpart of the reference's SyncBatchNorm conversion
+    (:362-364): the BatchNorm1d head then normalises every crop group with the statistics of all ranks' cls rows;
   * the optimizer is the engine's fused per-tensor-clip + AdamW (the reference's default and only used one).
 """
 import argparse
@@ -95,6 +96,9 @@ def get_args_parser():
     p.add_argument('--saveckp_freq', default=10, type=int)
     p.add_argument('--seed', default=0, type=int)
     p.add_argument('--use_graph', default=True, type=utils.bool_flag, help="capture the step into hipGraphs")
+    p.add_argument('--sync_bn', default=False, type=utils.bool_flag,
+                   help="--arch fvit: BatchNorm1d statistics over the cls rows of all ranks (the reference's SyncBatchNorm conversion, "
+                        "lafs_train.py:362-364); required for --arch fvit on more than one rank")
     p.add_argument("--dist_url", default="env://", type=str)
     p.add_argument("--local_rank", default=0, type=int)
     return p
@@ -252,7 +256,7 @@ def train_lafs(args, dataset=None):
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
     device = torch.device("cuda", args.gpu)
     world = utils.get_world_size()
-    if args.arch == 'fvit' and world > 1:                 # (before anything is built: the engine would refuse the pair anyway)
+    if args.arch == 'fvit' and world > 1 and not args.sync_bn:      # (before anything is built: the engine would refuse the pair anyway)
         from .engine import FVIT_MULTI_RANK
         print(FVIT_MULTI_RANK, file=sys.stderr)
         sys.exit(FVIT_MULTI_RANK)
@@ -269,7 +273,7 @@ def train_lafs(args, dataset=None):
                          args.warmup_teacher_temp_epochs, args.epochs)
     engine = LafsPretrainEngine(student, teacher, dino_loss, args.batch_size_per_gpu, n_local=args.local_crops_number,
                                 clip_grad=args.clip_grad, freeze_last_layer=args.freeze_last_layer, use_graph=args.use_graph,
-                                device=device)
+                                device=device, sync_bn=args.sync_bn)
     print(f"Student and Teacher are built: they are both {args.arch} networks.")
 
     frontend = None

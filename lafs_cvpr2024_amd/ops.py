@@ -433,6 +433,92 @@ def bn1d_groups_bwd(dy, x, group_rows, mean, rstd, gamma, training, dgamma, dbet
     return dx
 
 
+def _group_totals(group_total, G):
+    tot = [int(v) for v in group_total]
+    if len(tot) != G:
+        raise _lib.LafsHipError(f"{len(tot)} total row counts for {G} groups")
+    return (C.c_int * max(G, 1))(*tot)
+
+
+def bn1d_groups_stats(x, group_rows, out=None):
+    """This rank's partial statistics of the grouped BatchNorm1d head (lafs_bn1d_groups_stats): f32 [G, 1 + 2 D], per group
+    {count, mean[D], M2[D]}.  out: contiguous f32 view of that shape (this rank's slot of the exchange buffer)."""
+    _chk(x, torch.float32, "x")
+    n, D = x.shape
+    tab, G = _group_rows(group_rows)
+    if G >= 1 and tab[G] != n:
+        raise _lib.LafsHipError(f"bn1d_groups_stats: the row table ends at {tab[G]}, x has {n} rows")
+    part = torch.empty(max(G, 1), 1 + 2 * D, device=x.device, dtype=torch.float32) if out is None else out
+    _chk(part, torch.float32, "out")
+    if tuple(part.shape) != (max(G, 1), 1 + 2 * D) or not part.is_contiguous():
+        raise _lib.LafsHipError(f"bn1d_groups_stats: out {tuple(part.shape)} must be a contiguous [{G}, {1 + 2 * D}]")
+    call("lafs_bn1d_groups_stats", _p(x), _ld(x), tab, G, D, _p(part))
+    return part
+
+
+def bn1d_groups_sync_fwd(x, group_rows, group_total, partials, gamma, beta, eps, momentum, running_mean, running_var, out=None):
+    """Training forward of the grouped head with the statistics of all ranks (lafs_bn1d_groups_sync_fwd).  partials: f32 [W, G, 1 + 2 D]
+    (the ranks' bn1d_groups_stats results, rank-major; any stride between the ranks, each rank's partial contiguous); group_total:
+    the groups' row counts over all ranks.  Returns (y, save_mean [G, D], save_rstd [G, D]); the running buffers are updated once per
+    group with the unbiased variance of the total count."""
+    _chk(x, torch.float32, "x"); _chk(partials, torch.float32, "partials")
+    n, D = x.shape
+    tab, G = _group_rows(group_rows)
+    if G >= 1 and tab[G] != n:
+        raise _lib.LafsHipError(f"bn1d_groups_sync_fwd: the row table ends at {tab[G]}, x has {n} rows")
+    if partials.dim() != 3 or tuple(partials.shape[1:]) != (G, 1 + 2 * D) or partials.stride(2) != 1 or partials.stride(1) != 1 + 2 * D:
+        raise _lib.LafsHipError(f"bn1d_groups_sync_fwd: partials {tuple(partials.shape)} / strides {partials.stride()} for "
+                                f"[W, {G}, {1 + 2 * D}] with contiguous rank slots")
+    W = partials.shape[0]
+    y = torch.empty(n, D, device=x.device, dtype=torch.float32) if out is None else out
+    _chk(y, torch.float32, "out")
+    if tuple(y.shape) != (n, D):
+        raise _lib.LafsHipError(f"bn1d_groups_sync_fwd: out {tuple(y.shape)} for x {tuple(x.shape)}")
+    mean = torch.empty(max(G, 1), D, device=x.device, dtype=torch.float32)
+    rstd = torch.empty(max(G, 1), D, device=x.device, dtype=torch.float32)
+    call("lafs_bn1d_groups_sync_fwd", _p(x), _ld(x), tab, _group_totals(group_total, G), G, D, _p(partials), W,
+         partials.stride(0) if W > 1 else G * (1 + 2 * D), _p(gamma), _p(beta), float(eps), float(momentum), _p(running_mean),
+         _p(running_var), _p(y), _ld(y), _p(mean), _p(rstd))
+    return y, mean, rstd
+
+
+def bn1d_groups_bwd_sums(dy, x, group_rows, mean, rstd, dgamma, dbeta, accumulate=True, out=None):
+    """First half of the cross-rank backward (lafs_bn1d_groups_bwd_sums): returns sums f32 [G, 2 D] = {sum dy, sum dy xhat} over this
+    rank's rows per group; dgamma / dbeta take the groups' sums in group order (rank-local)."""
+    _chk(dy, torch.float32, "dy"); _chk(x, torch.float32, "x")
+    n, D = x.shape
+    tab, G = _group_rows(group_rows)
+    if G >= 1 and (tab[G] != n or dy.shape[0] != n or mean.shape[0] != G or rstd.shape[0] != G):
+        raise _lib.LafsHipError(f"bn1d_groups_bwd_sums: row table ending at {tab[G]} / {G} groups against x {tuple(x.shape)}, "
+                                f"dy {tuple(dy.shape)}, statistics {tuple(mean.shape)}")
+    sums = torch.empty(max(G, 1), 2 * D, device=x.device, dtype=torch.float32) if out is None else out
+    _chk(sums, torch.float32, "out")
+    if tuple(sums.shape) != (max(G, 1), 2 * D) or not sums.is_contiguous():
+        raise _lib.LafsHipError(f"bn1d_groups_bwd_sums: out {tuple(sums.shape)} must be a contiguous [{G}, {2 * D}]")
+    call("lafs_bn1d_groups_bwd_sums", _p(dy), _ld(dy), _p(x), _ld(x), tab, G, D, _p(mean), _p(rstd), _p(sums), _p(dgamma), _p(dbeta),
+         1 if accumulate else 0)
+    return sums
+
+
+def bn1d_groups_sync_bwd(dy, x, group_rows, group_total, mean, rstd, gamma, sums, out=None):
+    """Second half (lafs_bn1d_groups_sync_bwd): dx of this rank's rows from the sums of ALL ranks (f32 [G, 2 D], already added up) and
+    the groups' total row counts."""
+    _chk(dy, torch.float32, "dy"); _chk(x, torch.float32, "x"); _chk(sums, torch.float32, "sums")
+    n, D = x.shape
+    tab, G = _group_rows(group_rows)
+    if G >= 1 and (tab[G] != n or dy.shape[0] != n or mean.shape[0] != G or rstd.shape[0] != G or tuple(sums.shape) != (G, 2 * D)
+                   or not sums.is_contiguous()):
+        raise _lib.LafsHipError(f"bn1d_groups_sync_bwd: row table ending at {tab[G]} / {G} groups against x {tuple(x.shape)}, "
+                                f"dy {tuple(dy.shape)}, statistics {tuple(mean.shape)}, sums {tuple(sums.shape)}")
+    dx = torch.empty(n, D, device=x.device, dtype=torch.float32) if out is None else out
+    _chk(dx, torch.float32, "out")
+    if tuple(dx.shape) != (n, D):
+        raise _lib.LafsHipError(f"bn1d_groups_sync_bwd: out {tuple(dx.shape)} for x {tuple(x.shape)}")
+    call("lafs_bn1d_groups_sync_bwd", _p(dy), _ld(dy), _p(x), _ld(x), tab, _group_totals(group_total, G), G, D, _p(mean), _p(rstd),
+         _p(gamma), _p(sums), _p(dx), _ld(dx))
+    return dx
+
+
 def dino_head_loss(zn_s, zn_t, wn_s, wn_t, center, ncrops, K, student_temp, teacher_temp, grad, loss=None, colsum=None, ws=None,
                    dev_temps=None, grad_scale=1.0):
     """DINOHead's last layer of both networks + DINO loss + centre row sums with the logits never stored (csrc/dino_head_loss.hip).

@@ -541,6 +541,7 @@ enum { LAFS_HP_LR = 0, LAFS_HP_WD, LAFS_HP_BETA1, LAFS_HP_BETA2, LAFS_HP_EPS, LA
        LAFS_HP_FREEZE_LAST, LAFS_HP_GRAD_SCALE, LAFS_HP_WD_LOW,
        LAFS_HP_STEP /* optimisation step count (as a float): seeds the per-step DropPath masks of a replayed graph */,
        LAFS_HP_MIX_LAM /* mixup lambda of this fine-tune micro-step (lam_dev of lafs_mixup_normalize / lafs_margin_softmax_ce_bf16) */,
+       LAFS_HP_LAND_W /* weight of the landmark-supervision term of this fine-tune micro-step (`weight` of lafs_landmark_mse) */,
        LAFS_HP_COUNT = 16 };
 /* seg_sumsq(f32)[n_seg] = sum of (grad_scale*g)^2 per segment -- the per-tensor norms of utils.clip_gradients
  * (utils.py:132-141).  Two passes through chunk_sumsq(f32)[n_chunks] scratch, fixed summation order: no atomics, nothing
@@ -1045,6 +1046,17 @@ int lafs_patch_gather_fwd(const float* img, const float* theta, int B, int S, in
 /* dtheta(f32) [B,n,2] from dmosaic; dimg (optional, pre-zeroed) accumulates the image gradient. */
 int lafs_patch_gather_bwd(const float* img, const float* theta, const float* dmosaic, int B, int S, int n,
                           float* dtheta, float* dimg, hipStream_t stream);
+/* Landmark supervision of the fine-tune step (train_largescale.py:807-812 the frozen stage-1 CNN's `land_label`, :815 `pred_land` =
+ * the backbone's own theta, :825-836 loss_land = MSELoss()(land_label / 111, pred_land / 111) and loss += land_loss_control * loss_land,
+ * :842-843 / acc_step).  pred, label f32 [B, n, 2] pixels (8-byte aligned); weight: DEVICE pointer to this epoch's land_loss_control,
+ * read when the kernel runs (&hyper[LAFS_HP_LAND_W]: one captured graph serves every epoch); grad_scale = 1 / acc_step > 0.
+ *   loss_land[0]  = mean((pred - label)^2) / 111^2 over all N = 2 B n values, unweighted (what :914-915 prints)
+ *   loss[0]      += weight * grad_scale * loss_land                                             (loss may be NULL)
+ *   dtheta[b,k,:] += weight * grad_scale * 2 (pred - label) / (111^2 N)                          (dtheta f32 [B, n, 2] may be NULL)
+ * `label` is a constant of the backward.  One workgroup, fixed summation order, no atomics: two launches give the same bits; weight 0
+ * adds exact zeros.  Nothing but the three outputs is written. */
+int lafs_landmark_mse(const float* pred, const float* label, int B, int n, const float* weight, float grad_scale, float* loss_land,
+                      float* loss, float* dtheta, hipStream_t stream);
 
 #ifdef __cplusplus
 }

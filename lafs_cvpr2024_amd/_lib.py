@@ -91,7 +91,7 @@ MLP_FWD, MLP_FWD_SAVE, MLP_BWD = range(3)
 PATCH_ORDER_CHW, PATCH_ORDER_HWC = 0, 1
 CHUNK = 1024
 SEG_DECAY, SEG_LAST_LAYER, SEG_TRAINABLE, SEG_LOW_DECAY, SEG_OVERWRITTEN = 1, 2, 4, 8, 16
-HP_LR, HP_WD, HP_BETA1, HP_BETA2, HP_EPS, HP_CLIP, HP_EMA_M, HP_FREEZE_LAST, HP_GRAD_SCALE, HP_WD_LOW, HP_STEP, HP_MIX_LAM = range(12)
+HP_LR, HP_WD, HP_BETA1, HP_BETA2, HP_EPS, HP_CLIP, HP_EMA_M, HP_FREEZE_LAST, HP_GRAD_SCALE, HP_WD_LOW, HP_STEP, HP_MIX_LAM, HP_LAND_W = range(13)
 HP_COUNT = 16
 # parameter row of lafs_mix_normalize / lafs_margin_softmax_ce_mix_bf16 (enum LAFS_MIX_* of lafs_hip.h)
 MIX_LAM, MIX_CUT, MIX_YL, MIX_YH, MIX_XL, MIX_XH, MIX_WORDS = range(7)
@@ -209,6 +209,7 @@ _PROTOS = {
     "lafs_unpatchify_f32": [vp, i32, i32, i32, vp],
     "lafs_patch_gather_fwd": [vp, vp, i32, i32, i32, vp],
     "lafs_patch_gather_bwd": [vp, vp, vp, i32, i32, i32, vp, vp],
+    "lafs_landmark_mse": [vp, vp, i32, i32, vp, f32, vp, vp, vp],
     "lafs_unfold_bf16": [vp, i32, i32, i32, i32, i32, vp, i32],
     "lafs_fold_f32": [vp, i32, i32, i32, i32, i32, i32, vp],
     "lafs_pad_cast_bf16": [vp, i32, i32, i32, vp, i32],

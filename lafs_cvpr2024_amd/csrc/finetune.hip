@@ -440,6 +440,44 @@ __global__ __launch_bounds__(256) void landmark_theta_kernel(const float* __rest
   }
 }
 
+// ---- landmark supervision of the fine-tune step (train_largescale.py:825-843): MSE of the backbone's landmarks against the frozen
+// stage-1 CNN's, both / 111, its weighted share of the loss and its gradient into theta.  At most 128 x 196 pairs: ONE workgroup, one
+// (x, y) pair per thread and round.  Fixed order, no atomics: a thread adds its pairs' squares in index order (x, then y, one fma
+// each), a 64-lane butterfly follows, thread 0 adds the 16 wave sums in wave order.  The gradient does not need the sum, so it is
+// added in the same pass.  weight == 0 adds exact zeros: fma(0, d, g) == g.
+#define LMSE_THREADS 1024
+__global__ __launch_bounds__(LMSE_THREADS) void landmark_mse_kernel(const float2* __restrict__ pred, const float2* __restrict__ label,
+                                                                    long long n_pairs, const float* __restrict__ weight, float grad_scale,
+                                                                    float inv, float* __restrict__ loss_land, float* __restrict__ loss,
+                                                                    float2* __restrict__ dtheta) {
+  __shared__ float part[LMSE_THREADS / LAFS_WAVE];
+  const float w = weight[0] * grad_scale;                // this epoch's land_loss_control, read when the kernel runs
+  const float coef = w * (2.f * inv);                    // d/dpred of w * mean((pred - label)^2 / 111^2)
+  float sq = 0.f;
+  for (long long i = threadIdx.x; i < n_pairs; i += LMSE_THREADS) {
+    const float2 p = pred[i], l = label[i];
+    const float dx = p.x - l.x, dy = p.y - l.y;
+    sq = __builtin_fmaf(dy, dy, __builtin_fmaf(dx, dx, sq));
+    if (dtheta != nullptr) {
+      float2 g = dtheta[i];
+      g.x = __builtin_fmaf(coef, dx, g.x);
+      g.y = __builtin_fmaf(coef, dy, g.y);
+      dtheta[i] = g;
+    }
+  }
+  sq = wave_sum(sq);
+  if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = sq;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < LMSE_THREADS / LAFS_WAVE; ++k) s += part[k];
+    const float mean = s * inv;
+    loss_land[0] = mean;
+    if (loss != nullptr) loss[0] = __builtin_fmaf(w, mean, loss[0]);
+  }
+}
+
 // the chunked form's three launches: partials, gradient + row losses, mean loss
 template <bool SMOOTH>
 int launch_margin_ce(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, const float* lam_rows, int lam_stride, float lam,
@@ -557,6 +595,21 @@ extern "C" int lafs_patch_gather_bwd(const float* img, const float* theta, const
   const int r = isqrt_exact(n);
   LAFS_CHECK_ARG(img && theta && dmosaic && dtheta && B > 0 && S > 0 && r > 0, "n must be a perfect square");
   hipLaunchKernelGGL(gather_bwd_kernel, dim3(n, B), dim3(64), 0, stream, img, theta, dmosaic, S, n, r, dtheta, dimg);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_landmark_mse(const float* pred, const float* label, int B, int n, const float* weight, float grad_scale,
+                                 float* loss_land, float* loss, float* dtheta, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(pred && label && weight && loss_land, "bad operand");
+  LAFS_CHECK_ARG(B > 0 && n > 0, "B and n must be positive");
+  LAFS_CHECK_ARG(grad_scale > 0.f, "grad_scale is 1 / acc_step: positive");
+  LAFS_CHECK_ARG(((uintptr_t)pred | (uintptr_t)label | (uintptr_t)dtheta) % 8 == 0, "landmark pairs must be 8-byte aligned");
+  const long long n_pairs = (long long)B * n;
+  const float inv = (float)(1.0 / (111.0 * 111.0 * 2.0 * (double)n_pairs));
+  hipLaunchKernelGGL(landmark_mse_kernel, dim3(1), dim3(LMSE_THREADS), 0, stream, (const float2*)pred, (const float2*)label, n_pairs, weight,
+                     grad_scale, inv, loss_land, loss, (float2*)dtheta);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }

@@ -18,6 +18,11 @@ graph as on one rank (deferred weight gradients included), and the window's LAST
 as the backward retires them -- is captured as one hipGraph per segment with the FlatReducer launches between the replays, exactly as
 LafsPretrainEngine does.  Only the class-sharded head keeps the eager form (its collectives sit inside the head itself).
 
+Landmark teacher (reference `pre_land` / `keep_land`, train_largescale.py:435-437, 565-582, 807-843): a frozen stage-1 CNN, run in line
+on the mixed batch as an inference plan, either supplies the patches the trunk is fed (mode A: backbone without a branch) or labels
+the batch for the backbone's own branch (mode B: lafs_landmark_mse between the gather's backward and the CNN's; the epoch's weight is
+read from the hyper-parameter vector, so the captured micro-step serves every epoch).  Without a teacher nothing changes.
+
 fViT (ViTs_face_overlap, `--net VITs`): the same step with the overlapping window embedding (lafs_unfold_bf16 in front of the embedding
 GEMM, the window geometry) and the BatchNorm1d head on the cls rows (lafs_bn1d_fwd / lafs_bn1d_bwd: batch statistics and the running-
 statistic update in training mode, running statistics in eval mode); no landmark branch.  `num_batches_tracked` is counted on the
@@ -55,13 +60,20 @@ def finetune_decay_group(name, param):
 class FinetuneEngine:
     def __init__(self, backbone: ViT_face_landmark_patch8, batch_size, acc_step=3, mixup_alpha=0.2, mixup_prob=0.1,
                  s=64.0, m=0.4, margin_type=0, image_size=112, device=None, sharded_head=None, use_graph=None,
-                 cutmix_alpha=0.0, cutmix_minmax=None, switch_prob=0.5, mix_mode="batch", label_smoothing=0.0):
+                 cutmix_alpha=0.0, cutmix_minmax=None, switch_prob=0.5, mix_mode="batch", label_smoothing=0.0,
+                 landmark_teacher=None, keep_land=False):
         """margin_type 0 = CosFace (the reference), 1 = ArcFace (parity unpinned), on the dense `backbone.loss.weight` head;
         `sharded_head` (a partial_fc.PartialFC) replaces it by the class-sharded head (CosFace: mixup targets as on the dense head).
         use_graph: None = capture the micro-step whenever it is capturable (single rank, dense head; LAFS_FT_GRAPH=0 disables).
         cutmix_alpha / cutmix_minmax / switch_prob / mix_mode / label_smoothing: util.mixup_my.Mixup's arguments of the same meaning
         (train_largescale.py:528-531).  Any of them away from the reference's default (0, None, -, 'batch', 0) selects the per-row
-        kernels; label smoothing needs the dense CosFace head."""
+        kernels; label smoothing needs the dense CosFace head.
+        landmark_teacher / keep_land: the reference's `pre_land` / `keep_land` (train_largescale.py:435-437, 565-582, 807-836).  The
+        teacher is any module with `.stn` and `.output_layer` (face_landmark_4simmin_glo_loc); its weights are frozen HERE into an
+        inference plan (eval mode, not in the optimizer).  keep_land=False (mode A, a backbone with with_land=False): the teacher's
+        landmarks gather the patches the trunk is fed, no gradient flows into them.  keep_land=True (mode B, with_land=True): the
+        backbone keeps its own branch, whose landmarks are regressed onto the teacher's (lafs_landmark_mse, weight `land_weight` of
+        micro_step): `loss` includes weight / acc_step * loss_land, `loss_land` holds the unweighted mean."""
         if mix_mode not in ("batch", "pair", "elem"):
             raise _lib.LafsHipError(f"mix_mode must be 'batch', 'pair' or 'elem', not {mix_mode!r}")
         if not 0.0 <= label_smoothing < 1.0:
@@ -71,6 +83,20 @@ class FinetuneEngine:
                                     "subset is not defined here): use the dense CosFace head")
         if label_smoothing > 0.0 and margin_type != 0:
             raise _lib.LafsHipError("label smoothing needs the CosFace margin: ArcFace has no margin for a dense target")
+        if keep_land and landmark_teacher is None:
+            raise _lib.LafsHipError("keep_land regresses the backbone's landmarks onto a teacher's: it needs a landmark_teacher")
+        if landmark_teacher is not None:
+            if isinstance(backbone, ViTs_face_overlap):
+                raise _lib.LafsHipError("a landmark teacher needs Part-fViT (ViT_face_landmark_patch8): fViT embeds overlapping windows of "
+                                        "the image, not landmark patches")
+            own = bool(getattr(backbone, "with_land", False))
+            if keep_land and not own:
+                raise _lib.LafsHipError("keep_land=True supervises the backbone's own landmark branch: it needs with_land=True")
+            if not keep_land and own:
+                raise _lib.LafsHipError("a landmark teacher without keep_land feeds the trunk the teacher's patches: the backbone must "
+                                        "have no branch of its own (with_land=False)")
+            if not (hasattr(landmark_teacher, "stn") and hasattr(landmark_teacher, "output_layer")):
+                raise _lib.LafsHipError("the landmark teacher needs `.stn` and `.output_layer` (face_landmark_4simmin_glo_loc)")
         if not isinstance(backbone, (ViT_face_landmark_patch8, ViTs_face_overlap)) or (sharded_head is None and not hasattr(backbone, "loss")):
             raise _lib.LafsHipError("FinetuneEngine drives ViT_face_landmark_patch8 or ViTs_face_overlap with loss_type='CosFace', or "
                                     "either of them with a sharded head")
@@ -179,7 +205,20 @@ class FinetuneEngine:
             self.dxn_ws = ops.wgrad_workspace(self.Cpad, B, D, dev)                 # d(emb_n): reduction over the classes
             self.dwn_ws = None if B % 32 == 0 else ops.wgrad_workspace(B, self.Cpad, D, dev)
         self.dmosaic = torch.empty(B, 3, S, S, device=dev, dtype=f32) if self.with_land else None
-        self.dth = None
+        self.dth, self.th, self.emb = None, None, None
+        # frozen stage-1 teacher (pre_land): its inference plan runs in line on the main stream, on the mixed batch `x`, no jitter, no
+        # selection (train_largescale.py:807-812); `land_label` is its min-max scaled theta in [0, 111]
+        self.teacher, self.keep_land, self.land_label, self.loss_land, self._land_fixed = None, bool(keep_land), None, None, None
+        self.land_weight = 1000.0                        # (the reference's weight of epoch 0 until micro_step is given one)
+        if landmark_teacher is not None:
+            from .landmark_cnn import HipLandmarkCNN
+            self.teacher = HipLandmarkCNN(landmark_teacher, dev)
+            self.land_n = self.teacher.n_out // 2
+            if 64 * self.land_n != S * S or (keep_land and self.land_n != m.row_num * m.row_num):
+                raise _lib.LafsHipError(f"the teacher regresses {self.land_n} landmarks: its 8 x 8 patches do not tile the trunk's "
+                                        f"{S}-pixel input" + (" / the backbone's branch regresses another number" if keep_land else ""))
+            self.land_label = torch.zeros(B, self.land_n, 2, device=dev, dtype=f32)
+            self.loss_land = torch.zeros(1, device=dev, dtype=f32)
         self.micro = 0                                   # micro-steps taken (seeds the per-step masks)
         self._since_opt = 0                              # ... since the last optimizer step
         # optimizer_step leaves the (dead) gradients in place: the next micro-step zeroes / overwrites them itself.  True restores
@@ -217,7 +256,7 @@ class FinetuneEngine:
         if use_graph is None:
             use_graph = os.environ.get("LAFS_FT_GRAPH", "1") != "0"
         self.use_graph = bool(use_graph) and sharded_head is None
-        self._graphs = {}
+        self._graphs, self._readout = {}, {}
         self._pool = None
         self._ws = None
 
@@ -302,12 +341,36 @@ class FinetuneEngine:
         m = self.model
         return self.use_graph and (not self.with_land or self.cnn is not None)
 
-    def micro_step(self, inputs_u8, labels, lam=None, mix=None):
+    def set_landmark_labels(self, labels):
+        """Parity hook (as set_droppath_scales of the LAFS engine): use `labels` f32 [B, n, 2] as the teacher's landmarks instead of
+        running its plan; None restores the plan.  Set it before the first capture: a captured micro-step keeps what it captured."""
+        if self.teacher is None:
+            raise _lib.LafsHipError("set_landmark_labels needs an engine built with a landmark_teacher")
+        if self._graphs:
+            raise _lib.LafsHipError("set_landmark_labels must be called before the micro-step is captured")
+        if labels is None:
+            self._land_fixed = None
+            return
+        if tuple(labels.shape) != tuple(self.land_label.shape):
+            raise _lib.LafsHipError(f"expected landmark labels of shape {tuple(self.land_label.shape)}")
+        self._land_fixed = labels.detach().to(self.device, f32).contiguous().clone()
+
+    def _teacher_labels(self):
+        """The frozen teacher on the mixed batch -> f32 [B, n, 2] landmarks in [0, 111] (a static buffer)."""
+        if self._land_fixed is not None:
+            return self._land_fixed
+        t = self.teacher(self.x)
+        call("lafs_landmark_theta", _p(t), self.B, self.land_n, None, 0.0, None, self.land_n, _p(self.land_label))
+        return self.land_label
+
+    def micro_step(self, inputs_u8, labels, lam=None, mix=None, land_weight=None):
         """One forward/backward on a uint8 NCHW batch.  Gradients accumulate in the arena (loss pre-divided by acc_step).
         lam: this micro-step's lambda instead of a draw (one blend lambda for the whole batch).  mix = (lam [B], cut [B] or None, box
         [B, 4] or None): explicit per-row parameters as Mixup.draw_params returns them (engines built with a per-row option only).
         The FIRST micro-step after an optimizer step overwrites / zeroes the gradients itself: between optimizer_step and the next
-        micro_step, arena.grad and p.grad hold the previous window's (stale) gradients unless `zero_after_step` is set."""
+        micro_step, arena.grad and p.grad hold the previous window's (stale) gradients unless `zero_after_step` is set.
+        land_weight: this epoch's land_loss_control (mode B); None keeps the last one.  It travels in the hyper-parameter vector and
+        is read by the kernel when it runs: a new weight is no new capture."""
         a, m = self.arena, self.model
         a.ensure_fresh()
         if mix is not None and not self.mix_rows:
@@ -323,7 +386,12 @@ class FinetuneEngine:
         self._stage(inputs_u8, labels)
         self._labels = labels
         # (the counter seeds the DropPath / dropout / CNN-dropout masks; fp32 holds integers exactly below 2^24: wrap like the LAFS engine)
-        self._upload_hyper({_lib.HP_MIX_LAM: lam, _lib.HP_STEP: float((self.micro + 1) % (1 << 24))})
+        if land_weight is not None:
+            self.land_weight = float(land_weight)
+        hyper = {_lib.HP_MIX_LAM: lam, _lib.HP_STEP: float((self.micro + 1) % (1 << 24))}
+        if self.teacher is not None and self.keep_land:
+            hyper[_lib.HP_LAND_W] = self.land_weight
+        self._upload_hyper(hyper)
         first = (self._since_opt == 0)                   # first micro-step since the last optimizer step: gradients are written, not accumulated
         if self._capturable():
             key = (first, bool(m.training), self._reduce_now())
@@ -331,6 +399,8 @@ class FinetuneEngine:
             if segs is None:
                 segs = self._capture(first)
                 self._graphs[key] = segs
+                self._readout[key] = (self.th, self.emb)     # (every captured variant writes buffers of its own)
+            self.th, self.emb = self._readout[key]
             for g, out in segs:                          # one graph per segment; the gradient range a segment completes goes out behind it
                 g.replay()
                 if out is not None:
@@ -429,11 +499,15 @@ class FinetuneEngine:
             dropout = (m.dropout_rate, m.emb_dropout_rate, m._drop_seed0, hp[_lib.HP_STEP:])
         img_in, theta, th = self.x, None, None
         self._cnn_hip = self.with_land and self.cnn is not None
+        land = self._land_now = self._teacher_labels() if self.teacher is not None else None
+        if land is not None and not self.keep_land:      # mode A: the trunk is fed the teacher's patches; theta carries no gradient
+            img_in = self.img_in
+            call("lafs_patch_gather_fwd", _p(self.x), _p(land), B, self.S, self.land_n, _p(img_in))
         if self.with_land:
             # trainable landmark regressor -> one-launch patch gather (ViT_face.py:679-711)
             theta = self.cnn.forward(self.x) if self._cnn_hip else m.landmarks(self.x)
             m.theta = theta
-            th = theta.detach().contiguous()
+            th = self.th = theta.detach().contiguous()   # (kept for read-out: the landmarks the gather used)
             img_in = self.img_in
             call("lafs_patch_gather_fwd", _p(self.x), _p(th), B, self.S, th.shape[1], _p(img_in))
         if self._ws is None:
@@ -445,6 +519,7 @@ class FinetuneEngine:
                                     x_in=self.x_in, x_out=self.x_out, wgrad_overwrite=first,
                                     wgrad_workgroups=self.wgrad_workgroups if defer else 0,
                                     wgrad_defer=defer, bn_training=m.training)
+        self.emb = emb                                   # (kept for read-out)
         if self.head is not None:
             # class-sharded head: all-gather embeddings, local logits, exchanged softmax statistics, reduce-scatter of dE.
             # demb is the gradient of the GLOBAL-batch mean loss, so the later all-reduce of the backbone gradients is a SUM.
@@ -547,6 +622,12 @@ class FinetuneEngine:
             if self.dth is None:
                 self.dth = torch.empty_like(th)
             call("lafs_patch_gather_bwd", _p(self.x), _p(th), _p(self.dmosaic), B, self.S, th.shape[1], _p(self.dth), None)
+            if self.teacher is not None:                 # mode B: + weight / acc_step * MSE(theta, teacher's) into the loss and into dth
+                # (class-sharded head: its gradients are those of the GLOBAL-batch mean and are summed over the ranks, so a rank's mean
+                # enters with 1 / world)
+                gs = 1.0 / self.acc_step / (self.world if self.head is not None else 1)
+                call("lafs_landmark_mse", _p(th), _p(self._land_now), B, th.shape[1], _p(self.hyper[_lib.HP_LAND_W:]), gs,
+                     _p(self.loss_land), _p(self.loss), _p(self.dth))
             if self._cnn_hip:
                 self.cnn.backward(self.dth)              # into the arena's stn.* / output_layer.* gradients
             else:
@@ -588,9 +669,9 @@ class FinetuneEngine:
         ops.zero_(self.arena.grad)
         self._since_opt = 0
 
-    def step(self, inputs_u8, labels, lr, weight_decay=0.1):
+    def step(self, inputs_u8, labels, lr, weight_decay=0.1, land_weight=None):
         """micro_step + optimizer step every acc_step micro-steps (train_largescale.py:842-891)."""
-        loss = self.micro_step(inputs_u8, labels)
+        loss = self.micro_step(inputs_u8, labels, land_weight=land_weight)
         if self.micro % self.acc_step == 0:
             self.optimizer_step(lr, weight_decay)
         return loss

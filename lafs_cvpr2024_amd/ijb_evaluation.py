@@ -463,9 +463,10 @@ def _decode(path):
 
 
 class IJBEvaluator:
-    def __init__(self, backbone, batch_size=360, device=None, norm="reference", workers=8):
+    def __init__(self, backbone, batch_size=360, device=None, norm="reference", workers=8, landmark_teacher=None):
         """backbone: ViT_face_landmark_patch8 (with or without the landmark branch) or ViTs_face_overlap; batch_size: loose crops per batch; norm:
-        'reference' (x/255 - 0.5, :235) or 'train' (the fine-tune feed); workers: decode threads (at most 16)."""
+        'reference' (x/255 - 0.5, :235) or 'train' (the fine-tune feed); workers: decode threads (at most 16); landmark_teacher: the
+        frozen stage-1 CNN whose patches feed a backbone without a branch of its own (verification.landmark_plan)."""
         import torch
         from .verification import NORMS
         from .vision_transformer import attach_arena
@@ -475,6 +476,7 @@ class IJBEvaluator:
             raise ValueError(f"norm must be one of {sorted(NORMS)}")
         self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
         self.model, self.B, self.norm = backbone, int(batch_size), norm
+        self.teacher = landmark_teacher
         self.workers = max(1, min(int(workers), MAX_WORKERS))
         self.arena = attach_arena(backbone, self.device)
         self.keep_aligned = False                  # test hook: keep the aligned uint8 crops (self.aligned [N,3,112,112], CPU)
@@ -483,7 +485,7 @@ class IJBEvaluator:
         self._stage = self._dev = None
         S = IMAGE_SIZE
         self._x = torch.empty(2 * self.B, 3, S, S, device=self.device, dtype=torch.float32)
-        self._mosaic = torch.empty_like(self._x) if getattr(backbone, "with_land", False) else None
+        self._mosaic = torch.empty_like(self._x) if getattr(backbone, "with_land", False) or landmark_teacher is not None else None
         self._al = torch.empty(self.B, 3, S, S, device=self.device, dtype=torch.uint8)
 
     def _staging(self, n_bytes):
@@ -539,7 +541,7 @@ class IJBEvaluator:
         self.aligned = torch.empty(N, 3, IMAGE_SIZE, IMAGE_SIZE, dtype=torch.uint8) if self.keep_aligned else None
         with torch.no_grad(), ThreadPoolExecutor(self.workers) as pool, ThreadPoolExecutor(1) as ahead:
             m._arena.ensure_fresh()
-            cnn = landmark_plan(m, dev)
+            cnn = landmark_plan(m, dev, self.teacher)
             load = lambda i0: list(pool.map(lambda v: _decode(v) if isinstance(v, (str, os.PathLike)) else np.asarray(v),
                                             images[i0:i0 + B]))
             nxt = ahead.submit(load, 0)
@@ -609,7 +611,8 @@ def main(argv=None):
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
         backbone.load_state_dict(sd)
         attach_arena(backbone, device)
-        ev = IJBEvaluator(backbone, args.batch_size, device, norm=args.val_norm, workers=args.workers)
+        ev = IJBEvaluator(backbone, args.batch_size, device, norm=args.val_norm, workers=args.workers,
+                          landmark_teacher=None if args.keep_land else tl.build_landmark_teacher(args))
         paths = [os.path.join(args.image_path, "loose_crop", n) for n in meta["names"]]
         feats = ev.features(paths, meta["landmarks"])
         torch.cuda.synchronize()

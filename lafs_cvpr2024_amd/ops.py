@@ -556,6 +556,22 @@ def dino_loss_fwd_bwd(student, teacher, center, ncrops, student_temp, teacher_te
     return loss, grad
 
 
+def landmark_mse(pred, label, weight, grad_scale=1.0, loss_land=None, loss=None, dtheta=None):
+    """lafs_landmark_mse: pred, label f32 [B, n, 2]; weight: a one-element f32 DEVICE tensor, read when the kernel runs.
+    -> loss_land f32 [1] (the unweighted mean); `loss` [1] and `dtheta` [B, n, 2], when given, are accumulated into."""
+    for t, name in ((pred, "pred"), (label, "label"), (weight, "weight"), (loss_land, "loss_land"), (loss, "loss"), (dtheta, "dtheta")):
+        _chk(t, torch.float32, name)
+    if pred.dim() != 3 or pred.shape[2] != 2 or label.shape != pred.shape or (dtheta is not None and dtheta.shape != pred.shape):
+        raise _lib.LafsHipError("landmark_mse: pred, label (and dtheta) are [B, n, 2]")
+    if not (pred.is_contiguous() and label.is_contiguous() and (dtheta is None or dtheta.is_contiguous())):
+        raise _lib.LafsHipError("landmark_mse: contiguous operands expected")
+    if loss_land is None:
+        loss_land = torch.empty(1, device=pred.device, dtype=torch.float32)
+    call("lafs_landmark_mse", _p(pred), _p(label), pred.shape[0], pred.shape[1], _p(weight), float(grad_scale), _p(loss_land), _p(loss),
+         _p(dtheta))
+    return loss_land
+
+
 def jpeg_decode(stream, images, tables, B, H, W, out=None, status=None, workspace=None):
     """One launch of lafs_jpeg_decode (csrc/jpeg.hip) over what jpeg.pack built: stream / images / tables are uint8 device tensors
     (scan bytes, B 64-byte records, 1600-byte table blocks).  Writes out u8 [B,3,H,W] and returns status i32 [B] (0 = decoded)."""

@@ -26,6 +26,10 @@ the divisor is clamped to >= 1 (the reference divides by zero on small datasets)
 with F = 1 never.
 `--net VITs` trains fViT (ViTs_face_overlap: overlapping 12/8/4 window embedding, BatchNorm1d head, no landmark branch) in the released
 configuration instead of Part-fViT (`--net VIT_land_8`, the default): the reference's names (:324-326).
+`--pre_land true` builds the frozen stage-1 landmark CNN of the reference (:565-582, weights from `--pretrain_path`): with
+`--with_land false` its patches feed the trunk, with `--keep_land true` (and the backbone's own branch) it labels every batch and
+`land_loss_control(epoch) * MSE` joins the loss (:825-836; `--land_loss_weight W` replaces the schedule by a constant), `loss_land` the
+progress line (:914-915).
 Out of scope here: tensorboard, IJB evaluation.
 """
 import argparse
@@ -62,6 +66,14 @@ def get_args_parser():
     p.add_argument("--partial_margin", default="CosFace", type=str, choices=["CosFace", "ArcFace"])
     p.add_argument("--sample_rate", default=1.0, type=float, help="PartialFC negative-class sampling rate")
     p.add_argument("--with_land", default=True, type=utils.bool_flag, help="trainable landmark branch (reference :432)")
+    p.add_argument("--pre_land", default=False, type=utils.bool_flag,
+                   help="frozen stage-1 landmark CNN (reference :435, 565-582), loaded from --pretrain_path.  Alone (with --with_land false): "
+                        "its patches feed the trunk, as in LAFS pre-training; with --keep_land: it labels every batch for the backbone's own branch")
+    p.add_argument("--keep_land", default=False, type=utils.bool_flag,
+                   help="landmark supervision (reference :437, 825-836): loss += land_loss_control(epoch) * MSE(teacher's landmarks / 111, "
+                        "the backbone's / 111); needs --pre_land true and --with_land true")
+    p.add_argument("--land_loss_weight", default=None, type=float,
+                   help="a constant weight of the landmark term instead of the reference's schedule over the epochs (short runs)")
     p.add_argument("--dropout", default=0.1, type=float, help="dropout = emb_dropout of the reference (:552-555)")
     p.add_argument("--landmark_ckpt", default="", type=str, help="stn./output_layer. weights (reference :659-661)")
     p.add_argument("--num_class", default=205990, type=int)
@@ -152,10 +164,49 @@ def get_time():
     return (str(datetime.now())[:-10]).replace(' ', '-').replace(':', '-')
 
 
+def land_loss_control(epoch):
+    """Weight of the landmark-supervision term over the 0-based epoch (reference train_largescale.py:825-834)."""
+    if epoch < 8:
+        return 1000
+    if epoch < 14:
+        return 100
+    if epoch < 21:
+        return 1
+    if epoch < 28:
+        return 0.11
+    return 0
+
+
 def check_net_args(args):
-    """An argument error for flags that have no meaning with the chosen --net."""
+    """An argument error for flags that have no meaning with the chosen --net, and for the landmark-teacher modes that cannot run."""
+    pre, keep = getattr(args, "pre_land", False), getattr(args, "keep_land", False)
+    if args.net == "VITs" and (pre or keep):
+        raise SystemExit("error: --pre_land / --keep_land feed or supervise landmark patches, which --net VITs does not embed")
     if args.net == "VITs" and (args.landmark_ckpt or args.pretrain_path):
         raise SystemExit("error: --landmark_ckpt / --pretrain_path load a landmark CNN, which --net VITs does not have")
+    if keep and not pre:
+        raise SystemExit("error: --keep_land regresses the backbone's landmarks onto the frozen CNN's: it needs --pre_land true")
+    if pre and keep and not args.with_land:
+        raise SystemExit("error: --pre_land true --keep_land true supervises the backbone's own landmark branch: it needs --with_land true")
+    if pre and not keep and args.with_land:
+        raise SystemExit("error: --pre_land true without --keep_land feeds the trunk the frozen CNN's patches: it needs --with_land false "
+                         "(the reference's hard-coded with_land=True cannot run this combination either)")
+
+
+def build_landmark_teacher(args):
+    """The frozen stage-1 landmark CNN of --pre_land with the reference's constructor arguments (:565-571), its `stn.*` /
+    `output_layer.*` tensors from --pretrain_path (:572-581), in eval mode; None without --pre_land."""
+    if not getattr(args, "pre_land", False):
+        return None
+    check_net_args(args)
+    from .face_pre_pro.ViT_face import face_landmark_4simmin_glo_loc
+    teacher = face_landmark_4simmin_glo_loc(loss_type="CosFace", GPU_ID=None, num_class=30000, num_patches=196, image_size=112,
+                                            patch_size=8, dim=512, depth=12, heads=11, mlp_dim=2560, dropout=0.1, emb_dropout=0.1)
+    if args.pretrain_path:
+        load_landmark_branch(teacher, args.pretrain_path)
+    else:
+        print("WARNING: --pre_land without --pretrain_path: the landmark teacher keeps its seeded initialisation")
+    return teacher.eval()
 
 
 def checkpoint_stem(args):
@@ -355,8 +406,9 @@ def main(args):
     backbone = build_backbone(args)
     if args.model_dir:
         load_ssl_teacher(backbone, args.model_dir)
-    if args.landmark_ckpt or args.pretrain_path:
+    if (args.landmark_ckpt or args.pretrain_path) and (args.with_land or not args.pre_land):      # (mode A: the path is the teacher's)
         load_landmark_branch(backbone, args.landmark_ckpt or args.pretrain_path)
+    teacher = build_landmark_teacher(args)
     head = None
     if sharded:
         from .partial_fc import PartialFC
@@ -366,7 +418,7 @@ def main(args):
                             mixup_prob=args.mixup_prob if mixing_active(args) else 0.0,
                             s=64.0, m=0.5 if arc else 0.4, margin_type=1 if arc else 0, device=device, sharded_head=head,
                             cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, switch_prob=args.mixup_switch_prob,
-                            mix_mode=args.mixup_mode, label_smoothing=args.smoothing)
+                            mix_mode=args.mixup_mode, label_smoothing=args.smoothing, landmark_teacher=teacher, keep_land=args.keep_land)
     # train_largescale.py:472:  lr = acc_step / 480 * lr * sqrt(world * BATCH_SIZE / 336) * 336
     base_lr = cfg["acc_step"] / 480.0 * args.lr * math.sqrt(world * args.batch_size / 336.0) * 336
     n_it = args.steps_per_epoch
@@ -393,7 +445,8 @@ def main(args):
         highest_acc = [0.0 for _ in vers]
         n_data = len(data.all_seq) if data is not None else args.steps_per_epoch * args.batch_size * world
         divisor = ver_divisor(n_data, world, args.batch_size, cfg["acc_step"], args.ver_freq)
-        evaluator = VerificationEvaluator(backbone, args.val_batch_size or args.batch_size, device, norm=args.val_norm)
+        evaluator = VerificationEvaluator(backbone, args.val_batch_size or args.batch_size, device, norm=args.val_norm,
+                                          landmark_teacher=teacher)
     eval_step = 0
     batch = 0
     t0 = time.time()
@@ -418,10 +471,14 @@ def main(args):
             if tensor_aug is not None:
                 x = tensor_aug(x, records=recs)
             lr = warmup_cosine(base_lr, epoch + it / n_it, cfg["WARMUP_EPOCH"], args.epochs)
-            loss = engine.step(x, y, lr=lr, weight_decay=args.weight_decay)
+            land_w = None
+            if args.keep_land:
+                land_w = land_loss_control(epoch) if args.land_loss_weight is None else args.land_loss_weight
+            loss = engine.step(x, y, lr=lr, weight_decay=args.weight_decay, land_weight=land_w)
             if it % 50 == 0:
+                land = f" loss_land {float(engine.loss_land.item()):.6f}" if args.keep_land else ""      # (reference :914-915)
                 print(f"Epoch {epoch} it {it}/{n_it} loss {float(loss.item()):.4f} lr {lr:.3e} "
-                      f"{(epoch * n_it + it + 1) * args.batch_size * world / (time.time() - t0):.1f} samples/s")
+                      f"{(epoch * n_it + it + 1) * args.batch_size * world / (time.time() - t0):.1f} samples/s{land}")
             if engine.micro % cfg["acc_step"] == 0:      # an optimizer step ran (reference :893)
                 eval_step += 1
                 if evaluator is not None and is_eval_step(eval_step, divisor):

@@ -182,10 +182,17 @@ def evaluate(hist, norm_sum, norm_count, thresholds=THRESHOLDS):
 
 
 # ----------------------------------------------------------------------------------------------------------------- device path
-def landmark_plan(model, device):
-    """The frozen-CNN inference plan of the landmark branch, built from the live weights and running statistics (None without one)."""
+def landmark_plan(model, device, landmark_teacher=None):
+    """The frozen-CNN inference plan of the landmark branch, built from the live weights and running statistics (None without one).
+    landmark_teacher: the frozen stage-1 CNN of a `pre_land` fine-tune without `keep_land` (reference util/utils.py:326-334): used
+    when the backbone has no branch of its own, so that such a model is validated on the feed it was trained on; a backbone with its
+    own branch ignores it."""
     from .landmark_cnn import HipLandmarkCNN
-    return HipLandmarkCNN(model, device) if getattr(model, "with_land", False) else None
+    if getattr(model, "with_land", False):
+        return HipLandmarkCNN(model, device)
+    if landmark_teacher is not None and not getattr(model._spec, "overlapping", False):
+        return HipLandmarkCNN(landmark_teacher, device)
+    return None
 
 
 @torch.no_grad()
@@ -211,15 +218,16 @@ def extract_features(model, arena, x, n, cnn, mosaic, device):
 
 
 class VerificationEvaluator:
-    def __init__(self, backbone, batch_size, device=None, norm="reference", n_folds=N_FOLDS):
+    def __init__(self, backbone, batch_size, device=None, norm="reference", n_folds=N_FOLDS, landmark_teacher=None):
         """backbone: ViT_face_landmark_patch8 (with or without the landmark branch) or ViTs_face_overlap; batch_size: images per batch (even);
-        norm: 'reference' (x/255 - 0.5, utils.py:314) or 'train' (x/255*2 - 1, the fine-tune feed)."""
+        norm: 'reference' (x/255 - 0.5, utils.py:314) or 'train' (x/255*2 - 1, the fine-tune feed); landmark_teacher: see landmark_plan."""
         if batch_size <= 0 or batch_size % 2:
             raise ValueError(f"the verification batch size must be even, got {batch_size}")
         if norm not in NORMS:
             raise ValueError(f"norm must be one of {sorted(NORMS)}")
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
         self.model, self.B, self.norm, self.n_folds = backbone, int(batch_size), norm, n_folds
+        self.teacher = landmark_teacher
         self.arena = attach_arena(backbone, self.device)
         self.thr = torch.tensor(THRESHOLDS, dtype=torch.float64, device=self.device)
         self.keep_features = False                 # test hook: keep every batch's per-copy embeddings (self.features [2, 2P, D])
@@ -231,11 +239,12 @@ class VerificationEvaluator:
             dev, B = self.device, self.B
             self._bufs = dict(S=S, u8=torch.empty(B, 3, S, S, device=dev, dtype=torch.uint8),
                               x=torch.empty(2 * B, 3, S, S, device=dev, dtype=f32),
-                              mosaic=torch.empty(2 * B, 3, S, S, device=dev, dtype=f32) if getattr(self.model, "with_land", False) else None)
+                              mosaic=(torch.empty(2 * B, 3, S, S, device=dev, dtype=f32)
+                                      if getattr(self.model, "with_land", False) or self.teacher is not None else None))
         return self._bufs
 
     def _landmark_plan(self):
-        return landmark_plan(self.model, self.device)
+        return landmark_plan(self.model, self.device, self.teacher)
 
     def _features(self, x, n, cnn):
         """x f32 [2n,3,S,S] -> trunk embeddings f32 [2n, D] (eval mode)."""
@@ -312,7 +321,8 @@ def main(argv=None):
     sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
     backbone.load_state_dict(sd)
     attach_arena(backbone, device)
-    ev = VerificationEvaluator(backbone, args.val_batch_size or args.batch_size, device, norm=args.val_norm)
+    ev = VerificationEvaluator(backbone, args.val_batch_size or args.batch_size, device, norm=args.val_norm,
+                               landmark_teacher=None if args.keep_land else tl.build_landmark_teacher(args))     # (a --pre_land checkpoint without a branch)
     for name, images, issame in get_val_data(args.val_path, args.target):
         t0 = time.time()
         res = ev(images, issame)

@@ -797,6 +797,19 @@ int lafs_bn_act_bwd_nchw(const float* x, const float* dy, const float* stat, con
 int lafs_augment_views(const uint8_t* images, const int32_t* params, const int32_t* table, int B, int K, float* views,
                        hipStream_t stream);
 
+/* The DINO-face baseline's views (DataAugmentationDINO, lafs_train.py:743-788: RandomResizedCrop(112 | 48, BICUBIC) :760,767,776,
+ * RandomHorizontalFlip + ColorJitter + RandomGrayscale :745-752, utils.GaussianBlur :762,769,778, utils.Solarization :770,
+ * ToTensor + Normalize :753-756; Pillow arithmetic, bit-exact).  ONE view per crop, the whole colour chain on every view.
+ * images u8 NCHW [B,3,112,112]; params i32 [B,2+n_local,20], the records of lafs_augment_views (crop 0, 1 = globals, 2.. = locals);
+ * table_g i32 [113,112,8] = the table of lafs_augment_views; table_l i32 [113,48,table_l_words] = the same for output size 48:
+ * per output index (first source index, taps, coefficients), table_l_words >= 2 + the most taps (10 for 112 -> 48);
+ * mean_std: 6 HOST floats {mean r,g,b, std r,g,b} of Normalize, (v / 255.f - mean) / std in fp32, each operation rounded.
+ * globals f32 [2B,3,112,112]: crop k of image b -> row k*B + b; locals f32 [n_local*B,3,48,48]: crop 2+k of image b -> row
+ * k*B + b (the crop-major input buffers of the pre-training engine).  Two launches of 1024-thread workgroups, 2B (112 KB of LDS each)
+ * and n_local*B (30 KB each); n_local = 0 launches the globals only (table_l and locals may then be null). */
+int lafs_dino_views(const uint8_t* images, const int32_t* params, const int32_t* table_g, const int32_t* table_l, int table_l_words,
+                    int B, int n_local, const float* mean_std, float* globals, float* locals, hipStream_t stream);
+
 /* RandAugment of the fine-tune loader (reference util/rand_aa_face.py:606-672 as FaceDataset builds it, face_pre_pro/
  * dataloader_web.py:240-243 -- 'rand-m1-mstd0.5-inc1', train_largescale.py:506 -- applied per decoded sample at
  * dataloader_web.py:342-346 / image_iter.py:324-329; Pillow arithmetic, bit-exact).  One record per image and layer, sampled on

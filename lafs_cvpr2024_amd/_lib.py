@@ -189,6 +189,7 @@ _PROTOS = {
     "lafs_cnn_cast_f16_f32": [vp, vp, i64],
     "lafs_landmark_theta_bwd": [vp, vp, i32, i32, vp],
     "lafs_augment_views": [vp, vp, vp, i32, i32, vp],
+    "lafs_dino_views": [vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_float), vp, vp],
     "lafs_randaug_apply": [vp, vp, vp, i32, i32, i32, i32, i32],
     "lafs_face_tensor_aug": [vp, vp, vp, i32, i32, i32, i32],
     "lafs_jpeg_decode": [vp, i64, vp, vp, i64, i32, i32, i32, vp, vp, vp],

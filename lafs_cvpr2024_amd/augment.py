@@ -19,7 +19,10 @@ from .ops import _p, call
 
 PRECISION_BITS = 32 - 8 - 2
 OUT = 112
-MAX_TAPS = 6
+LOCAL_OUT = 48                                      # side of a DINO local view
+MIN_TAPS = 6                                        # coefficient slots of the 112-output table: [113,112,2+6]
+IMAGENET_NORM = ((0.485, 0.456, 0.406), (0.229, 0.224, 0.225))      # DataAugmentationDINO's Normalize (lafs_train.py:755)
+HALF_NORM = ((0.5, 0.5, 0.5), (0.5, 0.5, 0.5))                      # what the fine-tune and evaluation tools feed
 P_WORDS = 20                                        # int32 words per (image, crop) parameter record
 
 
@@ -33,10 +36,12 @@ def _bicubic(x, a=-0.5):
     return 0.0
 
 
-def coeff_table(max_in=OUT, out_size=OUT):
+def coeff_table(max_in=OUT, out_size=OUT, min_taps=MIN_TAPS):
     """Pillow's precompute_coeffs (Resample.c, bicubic, 8-bit fixed point) for every source extent 1..max_in -> out_size.
-    int32 [max_in + 1, out_size, 2 + MAX_TAPS]: (first source index, number of taps, coefficients)."""
-    tab = np.zeros((max_in + 1, out_size, 2 + MAX_TAPS), np.int32)
+    int32 [max_in + 1, out_size, 2 + taps]: (first source index, number of taps, coefficients); `taps` is the most any entry
+    needs (4 when only upsampling, 10 for 112 -> 48), at least min_taps: the 112-output table keeps the [113,112,8] layout
+    lafs_augment_views reads."""
+    rows = {}
     for n in range(1, max_in + 1):
         scale = n / out_size
         filterscale = max(scale, 1.0)
@@ -48,10 +53,12 @@ def coeff_table(max_in=OUT, out_size=OUT):
             k = [_bicubic((x + xmin - center + 0.5) / filterscale) for x in range(xmax)]
             ww = sum(k)
             k = [v / ww if ww != 0.0 else v for v in k]
-            assert xmax <= MAX_TAPS
-            tab[n, xx, 0], tab[n, xx, 1] = xmin, xmax
-            for t, v in enumerate(k):
-                tab[n, xx, 2 + t] = int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS))
+            rows[n, xx] = (xmin, [int(-0.5 + v * (1 << PRECISION_BITS)) if v < 0 else int(0.5 + v * (1 << PRECISION_BITS)) for v in k])
+    taps = max(min_taps, max(len(k) for _, k in rows.values()))
+    tab = np.zeros((max_in + 1, out_size, 2 + taps), np.int32)
+    for (n, xx), (xmin, k) in rows.items():
+        tab[n, xx, 0], tab[n, xx, 1] = xmin, len(k)
+        tab[n, xx, 2:2 + len(k)] = k
     return tab
 
 
@@ -93,13 +100,14 @@ def _resized_crop_params(rng, H, W, scale, ratio=(3.0 / 4.0, 4.0 / 3.0)):
     return (H - h) // 2, (W - w) // 2, h, w
 
 
-def sample_view_params(rng, n_local=8, size=OUT, crops_scale=(0.4, 1.0)):
-    """Parameter dicts of the 2 + n_local crops of ONE image, in the loader's order (global 1, global 2, locals).
-    Probabilities and ranges: lafs_train.py:792-840 (ColorJitter(0.4, 0.4, 0.2, 0.1) with p 0.8, RandomGrayscale 0.2,
-    GaussianBlur p = 1.0 / 0.1 / 0.5 with radius U(0.1, 2), Solarization 0.2 on the second global view)."""
+def _sample_crops(rng, scales, size):
+    """One parameter dict per entry of `scales` (the RandomResizedCrop scale of that crop), in the loader's order (global 1,
+    global 2, locals): both pre-training loaders draw the same chain (lafs_train.py:745-780 and :792-840: ColorJitter(0.4, 0.4,
+    0.2, 0.1) with p 0.8, RandomGrayscale 0.2, GaussianBlur p = 1.0 / 0.1 / 0.5 with radius U(0.1, 2), Solarization 0.2 on the
+    second global view)."""
     out = []
-    for k in range(2 + n_local):
-        i, j, h, w = _resized_crop_params(rng, size, size, crops_scale)
+    for k, scale in enumerate(scales):
+        i, j, h, w = _resized_crop_params(rng, size, size, scale)
         p = dict(i=i, j=j, h=h, w=w, flip=bool(rng.rand() < 0.5))
         p["jitter"] = bool(rng.rand() < 0.8)
         p["order"] = [int(v) for v in rng.permutation(4)]
@@ -112,6 +120,17 @@ def sample_view_params(rng, n_local=8, size=OUT, crops_scale=(0.4, 1.0)):
         p["solarize"] = bool(k == 1 and rng.rand() < 0.2)
         out.append(p)
     return out
+
+
+def sample_view_params(rng, n_local=8, size=OUT, crops_scale=(0.4, 1.0)):
+    """Parameter dicts of the 2 + n_local crops of ONE image of DataAugmentation_LAFS: every crop with the same scale."""
+    return _sample_crops(rng, [crops_scale] * (2 + n_local), size)
+
+
+def sample_dino_params(rng, n_local=8, size=OUT, global_scale=(0.4, 1.0), local_scale=(0.05, 0.4)):
+    """Parameter dicts of the 2 + n_local crops of ONE image of DataAugmentationDINO (lafs_train.py:743-788): the globals draw
+    RandomResizedCrop.get_params with global_scale, the locals (resized to 48x48) with local_scale."""
+    return _sample_crops(rng, [global_scale] * 2 + [local_scale] * n_local, size)
 
 
 def pack_params(per_image):
@@ -137,11 +156,21 @@ def pack_params(per_image):
 def sample_packed(rng, B, n_local=8, size=OUT, crops_scale=(0.4, 1.0), return_dicts=False):
     """Vectorised sample_view_params + pack_params for a whole batch (same distributions, one numpy call per quantity instead
     of ~15 Python-level draws per crop: 640 crops per step would otherwise cost ~10 ms of host time)."""
-    K = 2 + n_local
+    return _sample_packed(rng, B, [crops_scale] * (2 + n_local), size, return_dicts)
+
+
+def sample_dino_packed(rng, B, n_local=8, size=OUT, global_scale=(0.4, 1.0), local_scale=(0.05, 0.4), return_dicts=False):
+    """Vectorised sample_dino_params + pack_params for a whole batch."""
+    return _sample_packed(rng, B, [global_scale] * 2 + [local_scale] * n_local, size, return_dicts)
+
+
+def _sample_packed(rng, B, scales, size, return_dicts):
+    K = len(scales)
     n = B * K
     area = float(size * size)
     lr0, lr1 = math.log(3.0 / 4.0), math.log(4.0 / 3.0)
-    target = area * rng.uniform(crops_scale[0], crops_scale[1], (n, 10))
+    sc = np.tile(np.asarray(scales, np.float64), (B, 1))                       # [n, 2]: the scale range of each crop
+    target = area * rng.uniform(sc[:, :1], sc[:, 1:], (n, 10))
     aspect = np.exp(rng.uniform(lr0, lr1, (n, 10)))
     w = np.rint(np.sqrt(target * aspect)).astype(np.int64)
     h = np.rint(np.sqrt(target / aspect)).astype(np.int64)
@@ -220,3 +249,75 @@ class DeviceAugmenter:
         self.params_ring.upload(self.params_dev, lambda buf: buf.copy_(torch.from_numpy(rec)))
         call("lafs_augment_views", _p(images_u8.contiguous()), _p(self.params_dev), _p(self.table), self.B, self.K, _p(self.views))
         return self.views
+
+
+class DeviceDinoAugmenter:
+    """DataAugmentationDINO (reference lafs_train.py:743-788) on the device: uint8 NCHW batch [B,3,112,112] -> the 2 global
+    112x112 and n_local local 48x48 views per image the pre-training engine consumes, crop-major (crop k of image b in row
+    k*B + b), one lafs_dino_views call per batch.
+
+    The two-phase contract of the landmark front-end: `prefetch` runs the kernels on a private stream into staging buffers, so the
+    views of batch i+1 are built underneath training step i; `commit` orders the hand-over into the engine's (graph-captured)
+    input buffers on the compute stream."""
+
+    def __init__(self, batch_size, n_local=8, global_scale=(0.4, 1.0), local_scale=(0.05, 0.4), mean=IMAGENET_NORM[0],
+                 std=IMAGENET_NORM[1], device=None, seed=0):
+        import ctypes
+        self.device = dev = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
+        self.B, self.n_local, self.K = batch_size, n_local, 2 + n_local
+        self.global_scale, self.local_scale = tuple(global_scale), tuple(local_scale)
+        if len(self.global_scale) != 2 or len(self.local_scale) != 2 or len(mean) != 3 or len(std) != 3:
+            raise ValueError("DeviceDinoAugmenter: scales are (low, high) pairs, mean and std have one value per channel")
+        self.mean_std = (ctypes.c_float * 6)(*mean, *std)
+        self.rng = np.random.RandomState(seed)
+        self.table_g = torch.from_numpy(coeff_table(OUT, OUT)).to(dev)
+        self.table_l = torch.from_numpy(coeff_table(OUT, LOCAL_OUT)).to(dev)
+        self.stage_g = torch.empty(2 * batch_size, 3, OUT, OUT, device=dev, dtype=torch.float32)
+        self.stage_l = torch.empty(max(n_local, 1) * batch_size, 3, LOCAL_OUT, LOCAL_OUT, device=dev, dtype=torch.float32)
+        self.params_dev = torch.empty(batch_size, self.K, P_WORDS, device=dev, dtype=torch.int32)
+        from .utils import PinnedRing
+        self.params_ring = PinnedRing((batch_size, self.K, P_WORDS), torch.int32)      # see PinnedRing: the host runs ahead
+        self.stream = torch.cuda.Stream(device=dev)
+        self.ready = torch.cuda.Event()
+        self.consumed = torch.cuda.Event()
+        self.consumed.record()
+
+    def sample(self):
+        return [sample_dino_params(self.rng, self.n_local, OUT, self.global_scale, self.local_scale) for _ in range(self.B)]
+
+    def prefetch(self, images_u8, produced=None, params=None):
+        """images_u8: uint8 [B,3,112,112] device tensor.  `produced`: event recorded when the batch became valid; without it the
+        side stream waits for everything enqueued on the current stream so far.  params: explicit per-image parameter lists."""
+        if images_u8.dtype != torch.uint8 or not images_u8.is_cuda or tuple(images_u8.shape) != (self.B, 3, OUT, OUT):
+            raise _lib.LafsHipError("DeviceDinoAugmenter expects a uint8 device tensor [B,3,112,112]")
+        rec = pack_params(params) if params is not None else \
+            sample_dino_packed(self.rng, self.B, self.n_local, OUT, self.global_scale, self.local_scale)
+        if tuple(rec.shape) != (self.B, self.K, P_WORDS):
+            raise _lib.LafsHipError(f"DeviceDinoAugmenter expects {self.K} parameter records for each of {self.B} images")
+        if produced is not None:
+            self.stream.wait_event(produced)
+        else:
+            self.stream.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(self.stream):
+            self.stream.wait_event(self.consumed)              # staging buffers free again
+            images_u8 = images_u8.contiguous()
+            images_u8.record_stream(self.stream)               # allocated on the caller's stream, consumed here
+            self.params_ring.upload(self.params_dev, lambda buf: buf.copy_(torch.from_numpy(rec)))
+            call("lafs_dino_views", _p(images_u8), _p(self.params_dev), _p(self.table_g), _p(self.table_l), self.table_l.shape[-1],
+                 self.B, self.n_local, self.mean_std, _p(self.stage_g), _p(self.stage_l))
+            self.ready.record(self.stream)
+
+    def commit(self, engine):
+        """Hand the staged views to the engine's input buffers on the current (compute) stream."""
+        cur = torch.cuda.current_stream(self.device)
+        cur.wait_event(self.ready)
+        engine.in_global_all.copy_(self.stage_g)
+        if self.n_local:
+            engine.in_local_all.copy_(self.stage_l)
+        self.consumed.record(cur)
+
+    def __call__(self, images_u8, params=None):
+        """-> (globals [2B,3,112,112], locals [n_local*B,3,48,48]): the staging buffers, valid on the current stream (tests)."""
+        self.prefetch(images_u8, params=params)
+        torch.cuda.current_stream(self.device).wait_event(self.ready)
+        return self.stage_g, self.stage_l[:self.n_local * self.B]

@@ -4,6 +4,9 @@
 // augmented view.  Every arithmetic convention (8-bit intermediates, truncations, float vs double) follows Pillow's C code so
 // that the result is bit-identical to the PIL pipeline torchvision drives (oracle/augment.py is pinned against Pillow; this
 // kernel against the oracle).  The image never leaves the CU between the ten-odd PIL calls the reference makes per view.
+// lafs_dino_views builds the views of the DINO-face baseline from the same pieces (reference lafs_train.py:743-788,
+// DataAugmentationDINO): one view per crop, the colour chain on every view, 112x112 globals and 48x48 locals -- a local is a
+// DOWNscaling resample of up to 10 taps --, so every piece below takes the view's side as a template parameter.
 #include "common.hpp"
 #include "lafs_hip.h"
 
@@ -13,10 +16,11 @@
 
 namespace {
 
-constexpr int S = 112, NPIX = S * S, NBYTE = NPIX * 3;
+constexpr int SRC = 112;               // side of the source image
 constexpr int PW = 20;                 // int32 words per parameter record (lafs_cvpr2024_amd/augment.py: pack_params)
-constexpr int TW = 8;                  // table words per output index: first source index, taps, 6 coefficients
+constexpr int TW = 8;                  // words per output index of the 112-output table: first source index, taps, 6 coefficient slots
 constexpr int PREC = 22;               // Resample.c PRECISION_BITS for 8-bit images
+constexpr int THREADS = 1024;          // 16 waves per workgroup, at either view size (the measurements: DESIGN.md kernel table)
 
 __device__ __forceinline__ int clip8(int v) { return v < 0 ? 0 : (v > 255 ? 255 : v); }
 __device__ __forceinline__ int luma(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
@@ -73,22 +77,29 @@ __device__ void hsv2rgb(int h, int s, int v, int& r, int& g, int& b) {          
   }
 }
 
-__device__ __forceinline__ float norm_px(int v) {                                    // ToTensor + Normalize(0.5, 0.5)
+struct Norm { float m0, m1, m2, s0, s1, s2; };                                      // Normalize(mean, std), r g b
+
+__device__ __forceinline__ float norm_px(int v, float mean, float std) {             // ToTensor + Normalize(mean, std)
 #pragma clang fp contract(off)
   const float x = (float)v / 255.0f;
-  const float y = x - 0.5f;
-  return y / 0.5f;
+  const float y = x - mean;
+  return y / std;
 }
 
-__device__ void write_view(const unsigned char* img, float* __restrict__ out) {      // HWC uint8 in LDS -> CHW float in HBM
+// Everything below is written once for an S x S view: S = 112 (both entry points) and S = 48 (the local views of lafs_dino_views).
+template <int S>
+__device__ void write_view(const unsigned char* img, float* __restrict__ out, const Norm nm) {   // HWC uint8 in LDS -> CHW float in HBM
+  constexpr int NPIX = S * S, NBYTE = NPIX * 3;
   for (int e = threadIdx.x; e < NBYTE; e += blockDim.x) {
     const int c = e / NPIX, p = e - c * NPIX;
-    out[e] = norm_px(img[p * 3 + c]);
+    out[e] = norm_px(img[p * 3 + c], c == 0 ? nm.m0 : (c == 1 ? nm.m1 : nm.m2), c == 0 ? nm.s0 : (c == 1 ? nm.s1 : nm.s2));
   }
 }
 
 // one ImagingHorizontalBoxBlur pass along x (vertical == 0) or along y (vertical == 1): src -> dst (both HWC uint8 in LDS)
+template <int S>
 __device__ void box_pass(const unsigned char* src, unsigned char* dst, int radius, unsigned ww, unsigned fw, int vertical) {
+  constexpr int NBYTE = S * S * 3;
   for (int e = threadIdx.x; e < NBYTE; e += blockDim.x) {
     const int p = e / 3, c = e - p * 3, y = p / S, x = p - y * S;
     const int pos = vertical ? y : x;
@@ -102,30 +113,23 @@ __device__ void box_pass(const unsigned char* src, unsigned char* dst, int radiu
   }
 }
 
-__global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __restrict__ images, const int* __restrict__ params,
-                                                      const int* __restrict__ table, int B, int K, float* __restrict__ views) {
-  extern __shared__ unsigned char lds[];
-  unsigned char* bufA = lds;
-  unsigned char* bufB = lds + NBYTE;
-  unsigned char* tmp = lds + 2 * NBYTE;
-  __shared__ int red[16];
-  __shared__ int pr[PW];
-  const int b = blockIdx.x / K, k = blockIdx.x % K;
-  if (threadIdx.x < PW) pr[threadIdx.x] = params[((size_t)b * K + k) * PW + threadIdx.x];
-  __syncthreads();
-  const int ci = pr[0], cj = pr[1], ch = pr[2], cw = pr[3], flags = pr[4], order = pr[5];
-  const unsigned char* src = images + (size_t)b * 3 * NPIX;
-
-  // ---- crop + horizontal pass: tmp[y][xx][c], y < ch (Resample.c ImagingResampleHorizontal_8bpc) ----
-  const int* tw = table + (size_t)cw * S * TW;
+// img.crop(box).resize((S, S), BICUBIC) + horizontal flip of one record: src (u8 CHW planes of SRC x SRC in HBM) -> bufA (HWC in LDS).
+// table: [SRC + 1][S][tw] words, per source extent and output index (first source index, taps, coefficients); tmp holds ch x S x 3.
+template <int S>
+__device__ void resized_crop(const unsigned char* __restrict__ src, const int* pr, const int* __restrict__ table, int tw,
+                             unsigned char* tmp, unsigned char* bufA) {
+  constexpr int NBYTE = S * S * 3;
+  const int ci = pr[0], cj = pr[1], ch = pr[2], cw = pr[3], flags = pr[4];
+  // ---- crop + horizontal pass: tmp[y][xx][c], y < ch (Resample.c ImagingResampleHorizontal_8bpc); skipped when cw == S ----
+  const int* twd = table + (size_t)cw * S * tw;
   for (int e = threadIdx.x; e < ch * S * 3; e += blockDim.x) {
     const int c = e % 3, q = e / 3, xx = q % S, y = q / S;
-    const unsigned char* row = src + ((size_t)c * S + (ci + y)) * S + cj;
+    const unsigned char* row = src + ((size_t)c * SRC + (ci + y)) * SRC + cj;
     int v;
     if (cw == S) {
       v = row[xx];
     } else {
-      const int* t = tw + xx * TW;
+      const int* t = twd + xx * tw;
       int acc = 1 << (PREC - 1);
       for (int n = 0; n < t[1]; ++n) acc += (int)row[t[0] + n] * t[2 + n];
       v = clip8(acc >> PREC);
@@ -133,15 +137,15 @@ __global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __re
     tmp[(y * S + xx) * 3 + c] = (unsigned char)v;
   }
   __syncthreads();
-  // ---- vertical pass (+ horizontal flip of the result) -> bufA ----
-  const int* th = table + (size_t)ch * S * TW;
+  // ---- vertical pass (skipped when ch == S) + horizontal flip of the result -> bufA ----
+  const int* th = table + (size_t)ch * S * tw;
   for (int e = threadIdx.x; e < NBYTE; e += blockDim.x) {
     const int c = e % 3, q = e / 3, xx = q % S, yy = q / S;
     int v;
     if (ch == S) {
       v = tmp[(yy * S + xx) * 3 + c];
     } else {
-      const int* t = th + yy * TW;
+      const int* t = th + yy * tw;
       int acc = 1 << (PREC - 1);
       for (int n = 0; n < t[1]; ++n) acc += (int)tmp[((t[0] + n) * S + xx) * 3 + c] * t[2 + n];
       v = clip8(acc >> PREC);
@@ -150,9 +154,14 @@ __global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __re
     bufA[(yy * S + xo) * 3 + c] = (unsigned char)v;
   }
   __syncthreads();
-  write_view(bufA, views + ((size_t)(2 * k) * B + b) * NBYTE);
-  __syncthreads();                                           // the colour operations below rewrite bufA in place
+}
 
+// ColorJitter in its sampled order / RandomGrayscale / GaussianBlur / Solarization of one record, in place on bufA (bufB: the
+// blur's second buffer; red: 16 words for the contrast mean)
+template <int S>
+__device__ void colour_chain(unsigned char* bufA, unsigned char* bufB, const int* pr, int* red) {
+  constexpr int NPIX = S * S, NBYTE = NPIX * 3;
+  const int flags = pr[4], order = pr[5];
   // ---- ColorJitter in its sampled order ----
   if (flags & 2) {
     for (int step = 0; step < 4; ++step) {
@@ -206,7 +215,7 @@ __global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __re
     const unsigned ww = (unsigned)pr[11], fw = (unsigned)pr[12];
     unsigned char* a = bufA; unsigned char* o = bufB;
     for (int pass = 0; pass < 6; ++pass) {
-      box_pass(a, o, radius, ww, fw, pass >= 3);
+      box_pass<S>(a, o, radius, ww, fw, pass >= 3);
       __syncthreads();
       unsigned char* t = a; a = o; o = t;
     }                                                        // 6 swaps: the result is back in bufA
@@ -215,7 +224,55 @@ __global__ __launch_bounds__(1024) void augment_kernel(const unsigned char* __re
     for (int e = threadIdx.x; e < NBYTE; e += blockDim.x) { const int v = bufA[e]; bufA[e] = (unsigned char)(v < 128 ? v : 255 - v); }
     __syncthreads();
   }
-  write_view(bufA, views + ((size_t)(2 * k + 1) * B + b) * NBYTE);
+}
+
+constexpr size_t lds_bytes(int s) { return (size_t)(2 * s * s + SRC * s) * 3; }     // bufA, bufB, tmp[SRC][s][3]
+
+__global__ __launch_bounds__(THREADS) void augment_kernel(const unsigned char* __restrict__ images, const int* __restrict__ params,
+                                                      const int* __restrict__ table, int B, int K, float* __restrict__ views) {
+  constexpr int S = 112, NBYTE = S * S * 3;
+  extern __shared__ unsigned char lds[];
+  unsigned char* bufA = lds;
+  unsigned char* bufB = lds + NBYTE;
+  unsigned char* tmp = lds + 2 * NBYTE;
+  __shared__ int red[16];
+  __shared__ int pr[PW];
+  const int b = blockIdx.x / K, k = blockIdx.x % K;
+  if (threadIdx.x < PW) pr[threadIdx.x] = params[((size_t)b * K + k) * PW + threadIdx.x];
+  __syncthreads();
+  const Norm half = {0.5f, 0.5f, 0.5f, 0.5f, 0.5f, 0.5f};
+  resized_crop<S>(images + (size_t)b * 3 * SRC * SRC, pr, table, TW, tmp, bufA);
+  write_view<S>(bufA, views + ((size_t)(2 * k) * B + b) * NBYTE, half);
+  __syncthreads();                                           // the colour operations below rewrite bufA in place
+  colour_chain<S>(bufA, bufB, pr, red);
+  write_view<S>(bufA, views + ((size_t)(2 * k + 1) * B + b) * NBYTE, half);
+}
+
+// One DINO view per workgroup: row = blockIdx.x of `out` [n_crops * B, 3, S, S] is crop k0 + row / B of image row % B.
+template <int S>
+__global__ __launch_bounds__(THREADS) void dino_kernel(const unsigned char* __restrict__ images, const int* __restrict__ params,
+                                                       const int* __restrict__ table, int tw, int B, int K, int k0, Norm nm,
+                                                       float* __restrict__ out) {
+  constexpr int NBYTE = S * S * 3;
+  extern __shared__ unsigned char lds[];
+  unsigned char* bufA = lds;
+  unsigned char* bufB = lds + NBYTE;
+  unsigned char* tmp = lds + 2 * NBYTE;
+  __shared__ int red[16];
+  __shared__ int pr[PW];
+  const int row = blockIdx.x, b = row % B, k = k0 + row / B;
+  if (threadIdx.x < PW) pr[threadIdx.x] = params[((size_t)b * K + k) * PW + threadIdx.x];
+  __syncthreads();
+  resized_crop<S>(images + (size_t)b * 3 * SRC * SRC, pr, table, tw, tmp, bufA);
+  colour_chain<S>(bufA, bufB, pr, red);
+  write_view<S>(bufA, out + (size_t)row * NBYTE, nm);
+}
+
+template <typename Kern>
+int reserve_lds(Kern kern, size_t lds, const char* who) {       // per call (per-device attribute, cheap call): no process-wide flag
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) { lafs_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, lds, hipGetErrorString(e)); return (int)e; }
+  return LAFS_OK;
 }
 
 }  // namespace
@@ -224,13 +281,34 @@ extern "C" int lafs_augment_views(const uint8_t* images, const int32_t* params, 
                                   hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(images && params && table && views && B > 0 && K > 0, "bad operand");
-  const size_t lds = 3 * (size_t)NBYTE;
-  {                                                   // per call (per-device attribute, cheap call): no process-wide flag
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(augment_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { lafs_set_error("lafs_augment_views: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return (int)e; }
-  }
+  const size_t lds = lds_bytes(112);
+  if (const int rc = reserve_lds(augment_kernel, lds, "lafs_augment_views")) return rc;
   // one workgroup per CU (3 x 37 KB of LDS): 16 waves each to keep the CU busy
-  hipLaunchKernelGGL(augment_kernel, dim3(B * K), dim3(1024), lds, stream, images, params, table, B, K, views);
+  hipLaunchKernelGGL(augment_kernel, dim3(B * K), dim3(THREADS), lds, stream, images, params, table, B, K, views);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_dino_views(const uint8_t* images, const int32_t* params, const int32_t* table_g, const int32_t* table_l,
+                               int table_l_words, int B, int n_local, const float* mean_std, float* globals, float* locals,
+                               hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(images && params && table_g && mean_std && globals && B > 0 && n_local >= 0, "bad operand");
+  LAFS_CHECK_ARG(n_local == 0 || (table_l && locals && table_l_words >= 3), "local views without a table or an output");
+  const Norm nm = {mean_std[0], mean_std[1], mean_std[2], mean_std[3], mean_std[4], mean_std[5]};
+  const int K = 2 + n_local;
+  // globals: as lafs_augment_views, one workgroup of 16 waves per CU (3 x 37 KB of LDS)
+  if (const int rc = reserve_lds(dino_kernel<112>, lds_bytes(112), "lafs_dino_views")) return rc;
+  hipLaunchKernelGGL((dino_kernel<112>), dim3(2 * B), dim3(THREADS), lds_bytes(112), stream, images, params, table_g, TW, B, K, 0, nm,
+                     globals);
+  LAFS_LAUNCH_CHECK();
+  if (n_local == 0) return LAFS_OK;
+  // locals: 2 x 6.9 KB + 16 KB of LDS = 30 KB per workgroup.  n_local * B = 512 workgroups are two per CU, so the waves of a CU
+  // come from the workgroup's size, not from stacking small ones: measured at B = 64, n_local = 8, the local launch takes
+  // 201 / 110 / 76 / 71 us with 128 / 256 / 512 / 1024 threads
+  if (const int rc = reserve_lds(dino_kernel<48>, lds_bytes(48), "lafs_dino_views")) return rc;
+  hipLaunchKernelGGL((dino_kernel<48>), dim3(n_local * B), dim3(THREADS), lds_bytes(48), stream, images, params, table_l, table_l_words,
+                     B, K, 2, nm, locals);
   LAFS_LAUNCH_CHECK();
   return LAFS_OK;
 }

@@ -12,6 +12,9 @@ Differences from the reference, all forced by its own breakage or by scope (SURV
   * the data pipeline (MXNet recordio + PIL augmentations + landmark CNN) is out of scope: `--data synthetic` feeds the
     crop shapes the landmark gather emits (2 x 112^2 + n x 48^2), or pass any Dataset through `train_lafs(args, dataset=...)`
     yielding lists of 2 + n crops;
+  * --views dino trains the paper's DINO-face baseline: the reference's DataAugmentationDINO (:743-788; 2 global 112^2 + n local
+    48^2 views, each with the whole colour chain) built on the device from the uint8 batch, for every --arch, with no landmark
+    CNN; --views_norm picks its Normalize;
   * --arch fvit pre-trains ViTs_face_overlap (the overlapping-patch fViT with its BatchNorm1d head; --fvit_dims, --fvit_window,
     --fvit_dropout); on more than one rank it needs --sync_bn true, the counterpart of the reference's SyncBatchNorm conversion
     (:362-364): the BatchNorm1d head then normalises every crop group with the statistics of all ranks' cls rows;
@@ -81,6 +84,15 @@ def get_args_parser():
                         "the 20 views, then the landmark front-end -- the whole input pipeline of the reference on the GPU; "
                         "'recordio': the same from --data_path/train.rec (MXNet RecordIO, InsightFace layout; JPEG decode on "
                         "--num_workers CPU workers unless --decode device, everything after it on the device)")
+    p.add_argument('--views', default='lafs', type=str, choices=['lafs', 'dino'],
+                   help="'lafs': DataAugmentation_LAFS + the landmark front-end (landmark mosaics); 'dino': the DINO-face baseline's "
+                        "DataAugmentationDINO (reference :743-788) on the device -- 2 global 112x112 + --local_crops_number local 48x48 "
+                        "views per image with --global_crops_scale / --local_crops_scale, no landmark CNN (--landmark_ckpt is not read); "
+                        "needs uint8 images: --data recordio or synthetic_u8")
+    p.add_argument('--views_norm', default='imagenet', type=str, choices=['imagenet', 'half'],
+                   help="--views dino: Normalize of the views.  'imagenet' = the reference's (0.485, 0.456, 0.406) / (0.229, 0.224, "
+                        "0.225); 'half' = 0.5 / 0.5, the [-1, 1] range train_largescale.py and the evaluation tools feed: use 'half' for "
+                        "a checkpoint meant for train_largescale.py --model_dir, so that fine-tuning sees the pre-training's input range")
     p.add_argument('--landmark_ckpt', '--landmark_path', dest='landmark_ckpt', default='', type=str,
                    help="state_dict of the frozen landmark CNN (reference --landmark_path, :112, :262-268)")
     # flags of the reference's PIL / recordio input pipeline: parsed for command-line compatibility, unused with synthetic data
@@ -89,8 +101,8 @@ def get_args_parser():
     p.add_argument('--decode', default='pillow', type=str, choices=['pillow', 'device'],
                    help="--data recordio: 'pillow' decodes the JPEG records on the CPU workers; 'device' decodes each batch in one launch "
                         "(jpeg.DeviceJpegDecoder, byte-identical; records the device does not take still go through Pillow)")
-    p.add_argument('--global_crops_scale', type=float, nargs='+', default=(0.4, 1.))
-    p.add_argument('--local_crops_scale', type=float, nargs='+', default=(0.05, 0.4))
+    p.add_argument('--global_crops_scale', type=float, nargs='+', default=(0.4, 1.), help="--views dino: RandomResizedCrop scale of the globals")
+    p.add_argument('--local_crops_scale', type=float, nargs='+', default=(0.05, 0.4), help="--views dino: RandomResizedCrop scale of the locals")
     p.add_argument('--steps_per_epoch', default=100, type=int, help="iterations per epoch for --data synthetic")
     p.add_argument('--output_dir', default=".", type=str)
     p.add_argument('--saveckp_freq', default=10, type=int)
@@ -140,13 +152,13 @@ class SyntheticViews:
 
 class SyntheticU8Views:
     """uint8 images [B,3,112,112] (what the recordio reader yields after decoding, lafs_train.py:176) -> 20 views through the
-    device-side DataAugmentation_LAFS."""
+    device-side DataAugmentation_LAFS; with augment=False the raw uint8 batch (--views dino builds its views from it)."""
 
-    def __init__(self, steps, batch, n_local, device, seed):
+    def __init__(self, steps, batch, n_local, device, seed, augment=True):
         from .augment import DeviceAugmenter
         self.steps, self.batch, self.device = steps, batch, device
         self.gen = torch.Generator(device=device).manual_seed(seed)
-        self.aug = DeviceAugmenter(batch, n_local=n_local, device=device, seed=seed)
+        self.aug = DeviceAugmenter(batch, n_local=n_local, device=device, seed=seed) if augment else (lambda u8: u8)
 
     def __len__(self):
         return self.steps
@@ -167,9 +179,10 @@ def epoch_shard(n, rank, world, seed, epoch):
 
 class RecordIOViews:
     """--data_path/train.rec (reference lafs_train.py:157-191: FaceDataset over MXNet recordio + DataLoader) -> decoded uint8
-    batches -> device-side DataAugmentation_LAFS.  One pass over the dataset per epoch, sharded over the ranks."""
+    batches -> device-side DataAugmentation_LAFS (augment=False: the raw uint8 batches, for --views dino).  One pass over the
+    dataset per epoch, sharded over the ranks."""
 
-    def __init__(self, path, batch, n_local, device, seed, num_workers, rank=0, world=1, decode="pillow"):
+    def __init__(self, path, batch, n_local, device, seed, num_workers, rank=0, world=1, decode="pillow", augment=True):
         from .augment import DeviceAugmenter
         from .recordio import FaceRecordDataset
         self.ds = FaceRecordDataset(os.path.join(path, 'train.rec'))
@@ -182,7 +195,7 @@ class RecordIOViews:
         self.per_rank = len(self.all_seq) // world
         self.batch, self.device, self.seed, self.workers = batch, device, seed, num_workers
         self.decode = decode
-        self.aug = DeviceAugmenter(batch, n_local=n_local, device=device, seed=seed)
+        self.aug = DeviceAugmenter(batch, n_local=n_local, device=device, seed=seed) if augment else (lambda u8: u8)
         self.epoch = 0
         self.set_epoch(0)
         print(f"Data loaded: there are {len(self.all_seq)} images ({self.per_rank} per rank).")
@@ -213,6 +226,26 @@ def build_landmark_frontend(args, device):
         sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
         print("=> landmark CNN:", cnn.load_state_dict(sd, strict=False))
     return LandmarkFrontEnd(cnn, args.batch_size_per_gpu, n_local=args.local_crops_number, device=device)
+
+
+def check_views(args):
+    """--views dino builds its views from uint8 images: the two synthetic sources of float crops / views have none."""
+    if getattr(args, 'views', 'lafs') == 'dino' and args.data not in ('recordio', 'synthetic_u8'):
+        raise SystemExit(f"--views dino needs uint8 images (--data recordio or synthetic_u8), not --data {args.data}")
+    for name in ('global_crops_scale', 'local_crops_scale'):
+        v = tuple(getattr(args, name))
+        if getattr(args, 'views', 'lafs') == 'dino' and not (len(v) == 2 and 0.0 < v[0] <= v[1] <= 1.0):
+            raise SystemExit(f"--{name} takes two values, 0 < low <= high <= 1")
+
+
+def build_dino_views(args, device):
+    """The DataAugmentationDINO of the reference (lafs_train.py:743-788) on the device; it takes the landmark
+    front-end's place behind the loader."""
+    from .augment import HALF_NORM, IMAGENET_NORM, DeviceDinoAugmenter
+    mean, std = IMAGENET_NORM if args.views_norm == 'imagenet' else HALF_NORM
+    return DeviceDinoAugmenter(args.batch_size_per_gpu, n_local=args.local_crops_number, global_scale=args.global_crops_scale,
+                               local_scale=args.local_crops_scale, mean=mean, std=std, device=device,
+                               seed=args.seed + utils.get_rank())
 
 
 def build_backbones(args):
@@ -251,6 +284,9 @@ def build_backbones(args):
 
 
 def train_lafs(args, dataset=None):
+    if dataset is None:
+        check_views(args)                                      # (before the process group and the networks are built)
+    dino_views = dataset is None and getattr(args, 'views', 'lafs') == 'dino'
     utils.init_distributed_mode(args)
     utils.fix_random_seeds(args.seed)
     print("\n".join("%s: %s" % (k, str(v)) for k, v in sorted(dict(vars(args)).items())))
@@ -281,11 +317,16 @@ def train_lafs(args, dataset=None):
         data_loader = dataset
     elif args.data == 'recordio':
         data_loader = RecordIOViews(args.data_path, args.batch_size_per_gpu, args.local_crops_number, device,
-                                    args.seed + utils.get_rank(), args.num_workers, utils.get_rank(), world, decode=args.decode)
-        frontend = build_landmark_frontend(args, device)
-    elif args.data in ('synthetic_views', 'synthetic_u8'):
-        cls = SyntheticViews if args.data == 'synthetic_views' else SyntheticU8Views
-        data_loader = cls(args.steps_per_epoch, args.batch_size_per_gpu, args.local_crops_number, device, args.seed + utils.get_rank())
+                                    args.seed + utils.get_rank(), args.num_workers, utils.get_rank(), world, decode=args.decode,
+                                    augment=not dino_views)
+        frontend = build_dino_views(args, device) if dino_views else build_landmark_frontend(args, device)
+    elif args.data == 'synthetic_u8':
+        data_loader = SyntheticU8Views(args.steps_per_epoch, args.batch_size_per_gpu, args.local_crops_number, device,
+                                       args.seed + utils.get_rank(), augment=not dino_views)
+        frontend = build_dino_views(args, device) if dino_views else build_landmark_frontend(args, device)
+    elif args.data == 'synthetic_views':
+        data_loader = SyntheticViews(args.steps_per_epoch, args.batch_size_per_gpu, args.local_crops_number, device,
+                                     args.seed + utils.get_rank())
         frontend = build_landmark_frontend(args, device)
     else:
         data_loader = SyntheticCrops(args.steps_per_epoch, args.batch_size_per_gpu, args.local_crops_number, device,
@@ -351,7 +392,8 @@ def _load_checkpoint(path, student, teacher, dino_loss, engine, run_variables):
 class _Pipelined:
     """Software pipeline over the view loader: batch i+1 is fetched (and its `produced` event recorded) BEFORE step i is
     launched and handed to the landmark front-end right AFTER, so the frozen CNN + gathers of the next batch run on the
-    front-end stream underneath the training step."""
+    front-end stream underneath the training step.  With --views dino the front-end is the DeviceDinoAugmenter (same
+    prefetch / commit contract) and the loader yields the raw uint8 batch."""
 
     def __init__(self, data_loader, frontend, engine):
         self.loader, self.fe, self.engine = data_loader, frontend, engine

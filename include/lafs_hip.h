@@ -472,6 +472,21 @@ int lafs_bn1d_groups_bwd_sums(const float* dy, int lddy, const float* x, int ldx
 int lafs_bn1d_groups_sync_bwd(const float* dy, int lddy, const float* x, int ldx, const int* group_rows, const int* group_total, int G,
                               int D, const float* save_mean, const float* save_rstd, const float* gamma, const float* sums, float* dx,
                               int lddx, hipStream_t stream);
+/* DINOHead(use_bn=True): nn.BatchNorm1d(hidden_dim) + nn.GELU() behind a hidden Linear (vision_transformer.py:272-281: :274-275 and
+ * :279-280), fused.  u f32 [n, D] (row stride ldu) is the Linear's output; a bf16 [n, D] (row stride lda) = gelu(xhat gamma + beta),
+ * the erf GELU of the GEMM epilogues; the BatchNorm output itself is never stored.  Statistics, rstd = 1 / sqrt(var + eps), the
+ * running-buffer update (both or neither; unbiased variance), training == 0 and save_mean / save_rstd f32 [D] are exactly those of
+ * lafs_bn1d_fwd (the same device functions: same bits); training needs n >= 2, checked before any launch.  Columns >= D and rows >= n
+ * are neither read nor written; D needs no alignment.  No atomics: two runs give the same bits. */
+int lafs_bn1d_gelu_fwd(const float* u, int ldu, int n, int D, const float* gamma, const float* beta, float eps, float momentum,
+                       int training, float* running_mean, float* running_var, void* a_bf16, int lda, float* save_mean,
+                       float* save_rstd, hipStream_t stream);
+/* Backward: xhat = (u - save_mean) save_rstd and y = xhat gamma + beta are recomputed, g = da gelu'(y) (da f32 [n, D], the gradient of
+ * a); dbeta = (accumulate ? dbeta : 0) + sum_r g, dgamma likewise + sum_r g xhat; du bf16 [n, D] = gamma rstd (g - sum g / n -
+ * xhat sum(g xhat) / n) in training, gamma rstd g in eval.  One launch, two passes over the rows; g is never stored. */
+int lafs_bn1d_gelu_bwd(const float* da, int ldda, const float* u, int ldu, int n, int D, const float* save_mean, const float* save_rstd,
+                       const float* gamma, const float* beta, int training, void* du_bf16, int lddu, float* dgamma, float* dbeta,
+                       int accumulate, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * DINO head pieces  (vision_transformer.py:284-287, 299-300)

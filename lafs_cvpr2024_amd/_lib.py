@@ -223,6 +223,8 @@ _PROTOS = {
     "lafs_bn1d_groups_sync_fwd": [vp, i32, vp, vp, i32, i32, vp, i32, i64, vp, vp, f32, f32, vp, vp, vp, i32, vp, vp],
     "lafs_bn1d_groups_bwd_sums": [vp, i32, vp, i32, vp, i32, i32, vp, vp, vp, vp, vp, i32],
     "lafs_bn1d_groups_sync_bwd": [vp, i32, vp, i32, vp, vp, i32, i32, vp, vp, vp, vp, vp, i32],
+    "lafs_bn1d_gelu_fwd": [vp, i32, i32, i32, vp, vp, f32, f32, i32, vp, vp, vp, i32, vp, vp],
+    "lafs_bn1d_gelu_bwd": [vp, i32, vp, i32, i32, i32, vp, vp, vp, vp, i32, vp, i32, vp, vp, i32],
 }
 _NO_STREAM = {
     "lafs_version": ([], i32),

@@ -40,6 +40,13 @@ def _is_fvit(m):
 FVIT_MULTI_RANK = ("fViT pre-training on more than one rank needs SyncBatchNorm statistics across the ranks (reference "
                    "lafs_train.py:362-364): pass sync_bn=True (lafs_train.py --sync_bn true), or run --arch fvit on a single rank")
 
+# The same conversion reaches the two BatchNorm1d of a DINOHead(use_bn=True): on several ranks the reference's head normalises its
+# hidden activations with the statistics of all ranks.  The fused head kernels (lafs_bn1d_gelu_fwd / _bwd) see one rank's rows and
+# have no cross-rank form yet; `sync_bn` covers fViT's own head only and does not lift this.
+HEAD_BN_MULTI_RANK = ("a DINO head with BatchNorm (use_bn_in_head) on more than one rank needs SyncBatchNorm statistics across the ranks "
+                      "(the reference converts both networks, lafs_train.py:362-364), which the head kernels do not exchange yet "
+                      "(--sync_bn covers fViT's own head only): run --use_bn_in_head true on a single rank")
+
 f32, bf16 = torch.float32, torch.bfloat16
 
 
@@ -80,6 +87,13 @@ class LafsPretrainEngine:
             raise _lib.LafsHipError("LafsPretrainEngine drives a VisionTransformer, a ViT_face_landmark_patch8 or a ViTs_face_overlap pair")
         if self.fvit and self.world > 1 and not sync_bn:
             raise _lib.LafsHipError(FVIT_MULTI_RANK)
+        # DINOHead(use_bn=True): both heads run their BatchNorm1d pair in whatever mode the head module is in -- the reference never
+        # calls teacher.eval(), so by default the teacher too normalises its 2B rows with batch statistics and steps its own buffers
+        self.head_bn = bool(getattr(student.head, "use_bn", False))
+        if self.head_bn != bool(getattr(teacher.head, "use_bn", False)):
+            raise _lib.LafsHipError("student and teacher heads must both be built with, or both without, use_bn")
+        if self.head_bn and self.world > 1:
+            raise _lib.LafsHipError(HEAD_BN_MULTI_RANK)
         # sync_bn (fViT pairs only): the head normalises every crop group with the statistics of the cls rows of ALL ranks.  The forward
         # segment is cut twice around the exchange of the partial statistics, the head backward once around the all-reduce of its two
         # sums (_seg_forward_a / _seg_forward_b / _seg_trunk_backward).  One rank has nobody to exchange with: it takes this segmented
@@ -585,10 +599,13 @@ class LafsPretrainEngine:
         return runs
 
     # warm-up/capture executes real optimisation steps on whatever is in the buffers: snapshot and restore the state -- fViT's
-    # BatchNorm buffers (running_mean, running_var, num_batches_tracked of both networks) included, which those passes update
+    # BatchNorm buffers (running_mean, running_var, num_batches_tracked of both networks) included, which those passes update, and
+    # those of a BatchNorm DINO head (head_forward steps them, the counters by a device add inside the captured forward)
     def _state_tensors(self):
         sa, ta = self.sa, self.ta
         bn = [b for m in ((self.bn_s, self.bn_t) if self.fvit else ()) for b in (m.running_mean, m.running_var, m.num_batches_tracked)]
+        if self.head_bn:                             # the four BatchNorm1d of the two heads (mlp.1 / mlp.4)
+            bn += [b for net in (self.student, self.teacher) for b in net.head.buffers()]
         return [sa.master, sa.exp_avg, sa.exp_avg_sq, sa.seg_step, ta.master, self.dino_loss.center] + bn
 
     def _snapshot(self):

@@ -455,21 +455,58 @@ def vit_backward(arena, spec: ViTSpec, st: ViTState, dfeat, g_buf=None, wgrad_st
 
 # ----------------------------------------------------------------------------------------------- DINO head
 class HeadState:
-    __slots__ = ("x_bf", "u1", "a1", "u2", "a2", "z", "zn", "inv_z", "wn", "wn_t", "inv_v", "logits", "K", "Kpad")
+    __slots__ = ("x_bf", "u1", "a1", "u2", "a2", "z", "zn", "inv_z", "wn", "wn_t", "inv_v", "logits", "K", "Kpad",
+                 "bn", "bn_training", "stats1", "stats2")       # BatchNorm head: u1 / u2 are f32, stats = (save_mean, save_rstd)
 
 
-def head_forward(arena, prefix, x, K, save=True, logits=None, skip_logits=False):
+def head_has_bn(arena, prefix):
+    """DINOHead(use_bn=True) keeps its Linears at mlp.0 / 3 / 6 and its BatchNorm1d at mlp.1 / 4 (vision_transformer.py:272-281)."""
+    return (prefix + "mlp.6.weight") in arena.offsets
+
+
+def _head_module(arena, prefix):
+    return arena.module.get_submodule(prefix[:-1]) if prefix else arena.module
+
+
+def _head_mlp_bn_forward(arena, prefix, st: HeadState, save, bn_training):
+    """The BatchNorm head's MLP: Linear -> BatchNorm1d + GELU (lafs_bn1d_gelu_fwd on the f32 GEMM output) twice, then the bottleneck
+    Linear.  In training mode both BatchNorms update their running buffers and their num_batches_tracked (a device add: capturable)."""
+    m = lambda k: arena.view(arena.master, prefix + k)
+    head = _head_module(arena, prefix)
+    st.bn = True
+    st.bn_training = bool(head.training if bn_training is None else bn_training)
+    bn1, bn2 = head.mlp[1], head.mlp[4]
+    u1 = ops.gemm_nt(st.x_bf, arena.bf(prefix + "mlp.0.weight"), _lib.EPI_F32, bias=m("mlp.0.bias"))
+    st.a1, mean1, rstd1 = ops.bn1d_gelu_fwd(u1, m("mlp.1.weight"), m("mlp.1.bias"), bn1.eps, bn1.momentum, st.bn_training,
+                                            bn1.running_mean, bn1.running_var)
+    u2 = ops.gemm_nt(st.a1, arena.bf(prefix + "mlp.3.weight"), _lib.EPI_F32, bias=m("mlp.3.bias"))
+    st.a2, mean2, rstd2 = ops.bn1d_gelu_fwd(u2, m("mlp.4.weight"), m("mlp.4.bias"), bn2.eps, bn2.momentum, st.bn_training,
+                                            bn2.running_mean, bn2.running_var)
+    if st.bn_training:
+        bn1.num_batches_tracked.add_(1)
+        bn2.num_batches_tracked.add_(1)
+    st.u1, st.u2, st.stats1, st.stats2 = (u1, u2, (mean1, rstd1), (mean2, rstd2)) if save else (None, None, None, None)
+    return ops.gemm_nt(st.a2, arena.bf(prefix + "mlp.6.weight"), _lib.EPI_F32, bias=m("mlp.6.bias"))
+
+
+def head_forward(arena, prefix, x, K, save=True, logits=None, skip_logits=False, bn_training=None):
     """DINOHead: x f32 [n, in_dim] -> logits f32 [n, Kpad] (columns >= K are zero).  skip_logits: stop in front of the last GEMM
-    (st.zn / st.wn are its operands): the training engine forms the logits inside the fused loss (ops.dino_head_loss)."""
+    (st.zn / st.wn are its operands): the training engine forms the logits inside the fused loss (ops.dino_head_loss).
+    A head built with use_bn=True (told by its arena names) runs the BatchNorm form; bn_training: batch statistics and buffer
+    updates, or the running statistics (None: the head module's own `training`)."""
     n = x.shape[0]
     dev = x.device
     st = HeadState()
     st.K, st.Kpad = K, (K + 127) // 128 * 128
     m = lambda k: arena.view(arena.master, prefix + k)
     st.x_bf = ops.scale_cast_bf16(x.contiguous())
-    st.u1, st.a1 = ops.gemm_nt(st.x_bf, arena.bf(prefix + "mlp.0.weight"), _lib.EPI_BF16_GELU, bias=m("mlp.0.bias"))
-    st.u2, st.a2 = ops.gemm_nt(st.a1, arena.bf(prefix + "mlp.2.weight"), _lib.EPI_BF16_GELU, bias=m("mlp.2.bias"))
-    st.z = ops.gemm_nt(st.a2, arena.bf(prefix + "mlp.4.weight"), _lib.EPI_F32, bias=m("mlp.4.bias"))
+    st.bn = head_has_bn(arena, prefix)
+    if st.bn:
+        st.z = _head_mlp_bn_forward(arena, prefix, st, save, bn_training)
+    else:
+        st.u1, st.a1 = ops.gemm_nt(st.x_bf, arena.bf(prefix + "mlp.0.weight"), _lib.EPI_BF16_GELU, bias=m("mlp.0.bias"))
+        st.u2, st.a2 = ops.gemm_nt(st.a1, arena.bf(prefix + "mlp.2.weight"), _lib.EPI_BF16_GELU, bias=m("mlp.2.bias"))
+        st.z = ops.gemm_nt(st.a2, arena.bf(prefix + "mlp.4.weight"), _lib.EPI_F32, bias=m("mlp.4.bias"))
     Db = st.z.shape[1]
     st.zn = torch.empty(n, Db, device=dev, dtype=bf16)
     st.inv_z = torch.empty(n, device=dev, dtype=f32)
@@ -516,6 +553,8 @@ def head_backward(arena, prefix, st: HeadState, dlogits_bf, train_g=False, overw
     dz = torch.empty(n, Db, device=dev, dtype=f32)
     call("lafs_l2norm_bwd", _p(st.z), Db, _p(dzn), Db, _p(st.inv_z), _p(dz), Db, n, Db)
     dz_bf = ops.scale_cast_bf16(dz)
+    if st.bn:
+        return _head_mlp_bn_backward(arena, prefix, st, dz_bf)
     du2 = ops.gemm_nt(dz_bf, arena.tview(prefix + "mlp.4.weight"), _lib.EPI_DGELU_BF16, aux=st.u2)
     du1 = ops.gemm_nt(du2, arena.tview(prefix + "mlp.2.weight"), _lib.EPI_DGELU_BF16, aux=st.u1)
     dx = ops.gemm_nt(du1, arena.tview(prefix + "mlp.0.weight"), _lib.EPI_F32)
@@ -523,5 +562,25 @@ def head_backward(arena, prefix, st: HeadState, dlogits_bf, train_g=False, overw
     # (three 128x128-tile launches of ~39 us each before: 640 token rows leave each of them a fraction of the chip)
     ops.wgrad_group([(dz_bf, st.a2, gv("mlp.4.weight").view(p2("mlp.4.weight")), True, gv("mlp.4.bias")),
                      (du2, st.a1, gv("mlp.2.weight").view(p2("mlp.2.weight")), True, gv("mlp.2.bias")),
+                     (du1, st.x_bf, gv("mlp.0.weight").view(p2("mlp.0.weight")), True, gv("mlp.0.bias"))])
+    return dx
+
+
+def _head_mlp_bn_backward(arena, prefix, st: HeadState, dz_bf):
+    """Backward of _head_mlp_bn_forward: each input-gradient GEMM leaves f32, lafs_bn1d_gelu_bwd turns it into the bf16 gradient of the
+    Linear output in front (and adds the BatchNorm weight / bias gradients); the three Linear weight + bias gradients are one grouped
+    launch as in the plain head."""
+    m = lambda k: arena.view(arena.master, prefix + k)
+    gv = lambda k: arena.view(arena.grad, prefix + k)
+    p2 = lambda k: arena.params[arena.names.index(prefix + k)].shape
+    da2 = ops.gemm_nt(dz_bf, arena.tview(prefix + "mlp.6.weight"), _lib.EPI_F32)
+    du2 = ops.bn1d_gelu_bwd(da2, st.u2, st.stats2[0], st.stats2[1], m("mlp.4.weight"), m("mlp.4.bias"), st.bn_training,
+                            gv("mlp.4.weight"), gv("mlp.4.bias"), accumulate=True)
+    da1 = ops.gemm_nt(du2, arena.tview(prefix + "mlp.3.weight"), _lib.EPI_F32)
+    du1 = ops.bn1d_gelu_bwd(da1, st.u1, st.stats1[0], st.stats1[1], m("mlp.1.weight"), m("mlp.1.bias"), st.bn_training,
+                            gv("mlp.1.weight"), gv("mlp.1.bias"), accumulate=True)
+    dx = ops.gemm_nt(du1, arena.tview(prefix + "mlp.0.weight"), _lib.EPI_F32)
+    ops.wgrad_group([(dz_bf, st.a2, gv("mlp.6.weight").view(p2("mlp.6.weight")), True, gv("mlp.6.bias")),
+                     (du2, st.a1, gv("mlp.3.weight").view(p2("mlp.3.weight")), True, gv("mlp.3.bias")),
                      (du1, st.x_bf, gv("mlp.0.weight").view(p2("mlp.0.weight")), True, gv("mlp.0.bias"))])
     return dx

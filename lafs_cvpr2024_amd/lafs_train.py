@@ -238,6 +238,15 @@ def check_views(args):
             raise SystemExit(f"--{name} takes two values, 0 < low <= high <= 1")
 
 
+def refuse_head_bn_on_several_ranks(args, world):
+    """--use_bn_in_head true on more than one rank: the reference's head would run SyncBatchNorm (lafs_train.py:362-364), the head
+    kernels here normalise one rank's rows.  Exits with the engine's message before anything is built; --sync_bn does not lift it."""
+    if args.use_bn_in_head and world > 1:
+        from .engine import HEAD_BN_MULTI_RANK
+        print(HEAD_BN_MULTI_RANK, file=sys.stderr)
+        sys.exit(HEAD_BN_MULTI_RANK)
+
+
 def build_dino_views(args, device):
     """The DataAugmentationDINO of the reference (lafs_train.py:743-788) on the device; it takes the landmark
     front-end's place behind the loader."""
@@ -296,6 +305,7 @@ def train_lafs(args, dataset=None):
         from .engine import FVIT_MULTI_RANK
         print(FVIT_MULTI_RANK, file=sys.stderr)
         sys.exit(FVIT_MULTI_RANK)
+    refuse_head_bn_on_several_ranks(args, world)
 
     # ---- student / teacher: MultiCropWrapper(backbone, DINOHead), as reference lafs_train.py:200-356 ----
     student_b, teacher_b, embed_dim = build_backbones(args)

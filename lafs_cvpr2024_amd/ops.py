@@ -388,6 +388,38 @@ def bn1d_bwd(dy, x, mean, rstd, gamma, training, dgamma, dbeta, accumulate=True)
     return dx
 
 
+def bn1d_gelu_fwd(u, gamma, beta, eps, momentum, training, running_mean, running_var, out=None):
+    """a = bf16(gelu(BatchNorm1d(u))) on f32 [n, D] (lafs_bn1d_gelu_fwd; the BatchNorm output is never stored).  Returns
+    (a bf16 [n, D], save_mean, save_rstd); training updates the running buffers in place.  `out`: a bf16 [n, D] view to write into."""
+    _chk(u, torch.float32, "u")
+    n, D = u.shape
+    a = out if out is not None else torch.empty(n, D, device=u.device, dtype=bf16)
+    _chk(a, bf16, "out")
+    if a.shape != u.shape:
+        raise _lib.LafsHipError(f"bn1d_gelu_fwd: out {tuple(a.shape)} for u {tuple(u.shape)}")
+    mean = torch.empty(D, device=u.device, dtype=torch.float32)
+    rstd = torch.empty(D, device=u.device, dtype=torch.float32)
+    call("lafs_bn1d_gelu_fwd", _p(u), _ld(u), n, D, _p(gamma), _p(beta), float(eps), float(momentum), 1 if training else 0,
+         _p(running_mean), _p(running_var), _p(a), _ld(a), _p(mean), _p(rstd))
+    return a, mean, rstd
+
+
+def bn1d_gelu_bwd(da, u, mean, rstd, gamma, beta, training, dgamma, dbeta, accumulate=True, out=None):
+    """Backward of bn1d_gelu_fwd (lafs_bn1d_gelu_bwd): da f32 [n, D] is the gradient of a; returns du bf16 [n, D] (written into `out`
+    when given); dgamma / dbeta are accumulated into or overwritten."""
+    _chk(da, torch.float32, "da"); _chk(u, torch.float32, "u")
+    n, D = u.shape
+    if da.shape != u.shape:
+        raise _lib.LafsHipError(f"bn1d_gelu_bwd: da {tuple(da.shape)} for u {tuple(u.shape)}")
+    du = out if out is not None else torch.empty(n, D, device=u.device, dtype=bf16)
+    _chk(du, bf16, "out")
+    if du.shape != u.shape:
+        raise _lib.LafsHipError(f"bn1d_gelu_bwd: out {tuple(du.shape)} for u {tuple(u.shape)}")
+    call("lafs_bn1d_gelu_bwd", _p(da), _ld(da), _p(u), _ld(u), n, D, _p(mean), _p(rstd), _p(gamma), _p(beta), 1 if training else 0,
+         _p(du), _ld(du), _p(dgamma), _p(dbeta), 1 if accumulate else 0)
+    return du
+
+
 def _group_rows(group_rows):
     """Host row table of the grouped BatchNorm entry points as a C int array (the entry point validates it)."""
     rows = [int(r) for r in group_rows]

@@ -264,15 +264,23 @@ class _WeightNormLinear(nn.Module):
 
 class DINOHead(nn.Module):
     """DINO projection head (reference vision_transformer.py:265-301): 3-layer GELU MLP, L2 normalisation and a
-    weight-normalised bias-free last layer.  nlayers=3 / use_bn=False only (the LAFS configuration)."""
+    weight-normalised bias-free last layer, nlayers=3.  use_bn=True puts an nn.BatchNorm1d in front of each GELU (:272-281): the
+    modules hold the parameters and running buffers under the reference's keys (mlp.1.* / mlp.4.*, Linears at mlp.0 / 3 / 6), the
+    fused lafs_bn1d_gelu_fwd / _bwd kernels compute.  Training mode normalises with batch statistics, steps the running buffers
+    and adds 1 to both num_batches_tracked per forward; eval mode normalises with the running statistics."""
 
     def __init__(self, in_dim, out_dim, use_bn=False, norm_last_layer=True, nlayers=3, hidden_dim=2048, bottleneck_dim=256):
         super().__init__()
-        if use_bn or nlayers != 3:
-            raise NotImplementedError("the HIP DINO head implements the LAFS configuration: nlayers=3, use_bn=False")
-        self.in_dim, self.out_dim = in_dim, out_dim
-        self.mlp = nn.Sequential(nn.Linear(in_dim, hidden_dim), nn.GELU(), nn.Linear(hidden_dim, hidden_dim), nn.GELU(),
-                                 nn.Linear(hidden_dim, bottleneck_dim))
+        if nlayers != 3:
+            raise NotImplementedError("the HIP DINO head implements nlayers=3")
+        self.in_dim, self.out_dim, self.use_bn = in_dim, out_dim, bool(use_bn)
+        if use_bn:
+            self.mlp = nn.Sequential(nn.Linear(in_dim, hidden_dim), nn.BatchNorm1d(hidden_dim), nn.GELU(),
+                                     nn.Linear(hidden_dim, hidden_dim), nn.BatchNorm1d(hidden_dim), nn.GELU(),
+                                     nn.Linear(hidden_dim, bottleneck_dim))
+        else:
+            self.mlp = nn.Sequential(nn.Linear(in_dim, hidden_dim), nn.GELU(), nn.Linear(hidden_dim, hidden_dim), nn.GELU(),
+                                     nn.Linear(hidden_dim, bottleneck_dim))
         for m in self.mlp:
             if isinstance(m, nn.Linear):
                 nn.init.trunc_normal_(m.weight, std=.02)

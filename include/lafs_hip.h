@@ -366,6 +366,23 @@ int lafs_attention_bwd(const void* qkv, int ldqkv, const void* out_bf16, int ldo
  * scale * log2(e)-folded scores, fp32 maximum / sum / normalisation); P is not rounded to bf16 and the forward's lse is not needed. */
 int lafs_attention_probs(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
                          float scale, int q_rows, float* probs, hipStream_t stream);
+/* Attention of the cls query alone (the last block of a trunk whose output is read through x[:, 0], vision_transformer.py:209-215): for
+ * every (sequence s, head h) query row 0 of the sequence against its len_s keys.  Row s of the COMPACT outputs belongs to sequence s of
+ * the call: out_c(bf16) [n_seq, ldo >= H*64], lse_c(f32) [n_seq, H] (natural log-sum-exp of the scaled scores).  Plain fp32 arithmetic
+ * on the bf16 operands -- scores, maximum, sum and P V in fp32 -- with the un-normalised P rounded to bf16 in front of P V and the
+ * normaliser summed from the unrounded P, exactly where lafs_attention_fwd rounds: the two forwards differ by fp32 summation order
+ * only.  16 bits are STORED exactly once: out_c.
+ * Reads only the q columns of the first row and the k | v columns of every row of the call's sequences; lengths 1..256. */
+int lafs_attention_cls_fwd(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
+                           float scale, void* out_c_bf16, int ldo, float* lse_c, hipStream_t stream);
+/* Its backward: from dout_c(bf16) [n_seq, H*64], out_c and lse_c it writes the WHOLE dqkv(bf16) [T, 3*H*64] range of the call's
+ * sequences -- dK and dV of every token, dQ of the cls row, exact ZEROS in every other dQ row (the dense qkv input-gradient GEMM and
+ * weight gradient read them) -- and no row outside them.  P is recomputed in fp32 from lse_c, delta = sum(dO * O) from the stored
+ * bf16 O; the sums are fp32; P and dS (formed from the unrounded P) are rounded to bf16 in registers where lafs_attention_bwd
+ * rounds them (in front of the products that give dV and dK / dQ), and 16 bits are STORED exactly once per value of dqkv. */
+int lafs_attention_cls_bwd(const void* qkv, int ldqkv, const void* out_c_bf16, int ldo, const void* dout_c_bf16, int lddo,
+                           const float* lse_c, const int32_t* cu_seqlens, int n_seq, int max_len, int heads, float scale,
+                           void* dqkv, int lddqkv, hipStream_t stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Patch embedding front end  (vision_transformer.py:126-131, 196-207; face_pre_pro/ViT_face.py:760-766)
@@ -629,6 +646,19 @@ typedef struct lafs_trunk_desc {
                                          until lafs_trunk_wgrad launches them, e.g. beside work that leaves the chip idle (the
                                          fine-tune step's landmark-CNN backward, train_largescale.py:785-891) */
   lafs_ctx* ctx;                      /* side streams / events / options of these passes (NULL: caller's stream only, default options) */
+  int cls_only_last;                  /* != 0 (opt-in; 0 = every block dense, as before): the caller reads x_out only through the FIRST row of
+                                         every sequence (the cls token) and hands lafs_trunk_backward a gradient that is zero in every other
+                                         row.  The last block then runs LayerNorm 1 and the qkv GEMM on all rows (K and V are needed of every
+                                         token) and everything behind them -- attention output, projection, LayerNorm 2, MLP -- on the n_seq cls
+                                         rows only, forward and backward; its fc2 / fc1 / proj weight gradients sum over n_seq rows.  Of x_out
+                                         ONLY the first row of every sequence is then defined.  Honoured where the plan allows
+                                         (lafs_trunk_plan_info::cls_only_last).  The row-local compact activations live in the first n_seq rows of
+                                         the block's own buffers (layer 0's set in a forward-only pass; written after the row chains have
+                                         joined); the workspace grows by an n_seq identity table (written by the forward, read by the
+                                         backward), two f32 [n_seq, dim] row sets and the cls attention's o_c [n_seq, inner] (bf16) /
+                                         lse_c [n_seq, heads] -- the row chains write these while other chains may still run earlier blocks
+                                         on the shared buffer set, so they alias nothing -- and, when saving, by what the n_seq-row
+                                         weight-gradient launch's slice partials need beyond the dense launch's */
 } lafs_trunk_desc;
 
 /* Bytes of activation workspace for a forward with (1) / without (0) saving activations for backward.  The LayerNorm backward's
@@ -661,20 +691,31 @@ typedef struct lafs_trunk_plan_info {
   int mlp_merged;                      /* forward: the ranges meet in front of every MLP, which is ONE launch over `whole` */
   lafs_trunk_range_plan range[4];      /* [n_ranges]; with mlp_merged their fwd_* describe the merged launch */
   lafs_trunk_range_plan whole;         /* all rows as one range (= range[0] when n_ranges == 1) */
+  int cls_only_last;                   /* the last block runs on the cls rows behind its qkv GEMM: lafs_trunk_desc::cls_only_last is set, and
+                                          dropout_p == 0 (element-dropout masks are indexed by absolute row: a compacted row loses it), and
+                                          wgrad_defer == 0 (the deferred weight gradients read dense operand slots), and the pass includes
+                                          block depth - 1 (every forward; a backward with layer_hi == depth).  Its LayerNorm-2 backward then
+                                          writes lafs_layernorm_bwd_parts(n_seq, dim) gamma / beta slots into chain 0's buffer and none elsewhere */
 } lafs_trunk_plan_info;
 int lafs_trunk_plan(const lafs_trunk_desc* d, int save_for_backward, lafs_trunk_plan_info* out);
+/* The plan of a pass over blocks layer_hi-1 .. layer_lo only (lafs_trunk_backward walks the trunk in such slices); lafs_trunk_plan is
+ * the whole trunk, (depth, 0).  The range decides cls_only_last, nothing else. */
+int lafs_trunk_plan_layers(const lafs_trunk_desc* d, int save_for_backward, int layer_hi, int layer_lo, lafs_trunk_plan_info* out);
 /* The plan's n_ranges; -1 for a refused descriptor. */
 int lafs_trunk_row_ranges(const lafs_trunk_desc* d);
 /* x_in(f32) [n_tok, dim] -> x_out(f32) [n_tok, dim]: residual stream after the last block.  With
  * save_for_backward != 0 x_in must stay untouched until lafs_trunk_backward has run (it is layer 0's saved input)
- * and must not alias x_out. */
+ * and must not alias x_out.  With the plan's cls_only_last only the first row of every sequence of x_out is defined (the other rows
+ * keep whatever the buffer held or received as a ping-pong buffer of the earlier blocks). */
 int lafs_trunk_forward(const lafs_trunk_desc* d, const float* x_in, float* x_out, void* workspace,
                        int save_for_backward, hipStream_t stream);
 /* g(f32) [n_tok, dim]: dL/dx_out on entry, dL/dx_in on exit.  Parameter gradients are ACCUMULATED into d->grad.
  * Blocks layer_hi-1 .. layer_lo run; pass (depth, 0) for the whole trunk, or walk it in slices to start the
  * gradient all-reduce of finished blocks early.  wgrad_stream (optional, may be NULL or == stream): the weight-gradient
  * GEMMs are enqueued there and overlap the dgrad / attention / LayerNorm chain on `stream` (forked and joined with
- * events, so the call is still hipGraph-capturable and complete on `stream` when it returns to stream order). */
+ * events, so the call is still hipGraph-capturable and complete on `stream` when it returns to stream order).
+ * With the plan's cls_only_last (layer_hi == depth) g must be zero on entry outside the first row of every sequence: the last block's
+ * residual branches take their upstream gradient from those rows alone. */
 int lafs_trunk_backward(const lafs_trunk_desc* d, const float* x_in, float* g, void* workspace, int layer_hi,
                         int layer_lo, hipStream_t wgrad_stream, hipStream_t stream);
 /* The weight gradients (and bias gradients) of blocks layer_hi-1 .. layer_lo that a lafs_trunk_backward with d->wgrad_defer set

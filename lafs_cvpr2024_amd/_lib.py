@@ -73,7 +73,8 @@ class TrunkDesc(C.Structure):
                 ("master", C.c_void_p), ("shadow", C.c_void_p), ("shadow_t", C.c_void_p), ("grad", C.c_void_p),
                 ("blocks", C.POINTER(BlockOffsets)),
                 ("n_groups", C.c_int), ("group_n_seq", C.c_int * 4), ("group_max_len", C.c_int * 4), ("wgrad_workgroups", C.c_int),
-                ("dropout_step", C.c_void_p), ("wgrad_overwrite", C.c_int), ("wgrad_defer", C.c_int), ("ctx", C.c_void_p)]
+                ("dropout_step", C.c_void_p), ("wgrad_overwrite", C.c_int), ("wgrad_defer", C.c_int), ("ctx", C.c_void_p),
+                ("cls_only_last", C.c_int)]
 
 
 class TrunkRangePlan(C.Structure):
@@ -82,7 +83,8 @@ class TrunkRangePlan(C.Structure):
 
 
 class TrunkPlanInfo(C.Structure):
-    _fields_ = [("n_ranges", C.c_int), ("attention", C.c_int), ("mlp_merged", C.c_int), ("range", TrunkRangePlan * 4), ("whole", TrunkRangePlan)]
+    _fields_ = [("n_ranges", C.c_int), ("attention", C.c_int), ("mlp_merged", C.c_int), ("range", TrunkRangePlan * 4), ("whole", TrunkRangePlan),
+                ("cls_only_last", C.c_int)]
 
 
 EPI_BF16, EPI_BF16_GELU, EPI_RESID_F32, EPI_F32, EPI_DGELU_BF16, EPI_ATOMIC_F32, EPI_EMBED_F32, EPI_BF16_ACT = range(8)
@@ -126,6 +128,8 @@ _PROTOS = {
     "lafs_attention_fwd": [vp, i32, vp, i32, i32, i32, f32, vp, i32, vp],
     "lafs_attention_bwd": [vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, f32, vp, i32],
     "lafs_attention_probs": [vp, i32, vp, i32, i32, i32, f32, i32, vp],
+    "lafs_attention_cls_fwd": [vp, i32, vp, i32, i32, i32, f32, vp, i32, vp],
+    "lafs_attention_cls_bwd": [vp, i32, vp, i32, vp, i32, vp, vp, i32, i32, i32, f32, vp, i32],
     "lafs_patchify": [vp, i32, i32, i32, vp],
     "lafs_embed_cls": [vp, vp, vp, i32, i32, i32, i32],
     "lafs_embed_bwd": [vp, i32, i32, i32, i32, vp, vp, vp, vp],
@@ -246,6 +250,7 @@ _NO_STREAM = {
     "lafs_dino_head_loss_workspace": ([i32, i32, i32], i64),
     "lafs_trunk_workspace_bytes": ([C.POINTER(TrunkDesc), i32], i64),
     "lafs_trunk_plan": ([C.POINTER(TrunkDesc), i32, C.POINTER(TrunkPlanInfo)], i32),
+    "lafs_trunk_plan_layers": ([C.POINTER(TrunkDesc), i32, i32, i32, C.POINTER(TrunkPlanInfo)], i32),
     "lafs_trunk_row_ranges": ([C.POINTER(TrunkDesc)], i32),
     "lafs_layernorm_bwd_parts": ([i32, i32], i32),
     "lafs_ijb_search_workspace": ([i32, i32, i32], i64),
@@ -290,7 +295,8 @@ def lib():
 class Ctx:
     """Owner of one lafs_ctx (include/lafs_hip.h): the side streams / events of the trunk passes and the kernel-selection options.
     One per engine; the environment is read HERE, never inside the library: LAFS_SINGLE_STREAM=1 / LAFS_ATTN_STREAM=0 (no side
-    streams), LAFS_ROW_CHAINS, LAFS_KRES, LAFS_KRES_MIN_ITEMS, LAFS_NT_WIDE, LAFS_NT_TALL, LAFS_NT_BIG, LAFS_MLP_FUSED, LAFS_COMM_CUS."""
+    streams), LAFS_ROW_CHAINS, LAFS_KRES, LAFS_KRES_MIN_ITEMS, LAFS_NT_WIDE, LAFS_NT_TALL, LAFS_NT_BIG, LAFS_MLP_FUSED, LAFS_COMM_CUS; and
+    LAFS_CLS_ONLY_LAST (env_cls_only_last: a switch of the trunk descriptor, not an option of the context)."""
 
     def __init__(self, device=None, options=None, from_env=True):
         import torch
@@ -316,6 +322,11 @@ class Ctx:
             if e.get(name) not in (None, ""):
                 o[key] = int(e[name])
         return o
+
+    @staticmethod
+    def env_cls_only_last():
+        """A/B switch of the pre-training engine: LAFS_CLS_ONLY_LAST=0 keeps the last block of both trunks dense (lafs_trunk_desc::cls_only_last)."""
+        return os.environ.get("LAFS_CLS_ONLY_LAST", "1") != "0"
 
     def set(self, opt, value):
         check(lib().lafs_ctx_set(self.handle, int(opt), int(value)), "lafs_ctx_set")

@@ -872,6 +872,162 @@ int dispatch_probs(const ProbsArgs& a, hipStream_t s) {
   return launch_attn(attn_probs_kernel<NT, PPB, NW>, a.n_seq * a.heads, PPB, NW * 64, lds, a, s);
 }
 
+// ------------------------------------------------------------------------------------------------ cls query alone
+// The last block of a trunk that is read through x[:, 0] needs the attention output of ONE query per (sequence, head): 2 x 64 x len
+// multiply-adds against 2 x 128 x len bytes of K | V -- bound by reading K / V (forward) and by writing dqkv (backward), so plain
+// fp32 HIP without MFMA or LDS staging.  One wave per pair, CLS_NW pairs per workgroup.  A wave instruction covers 8 keys x 128
+// bytes: lane = (key slot g = lane >> 3, 16-byte channel chunk c = lane & 7), i.e. eight whole 128-byte rows per load or store; the
+// dot products close over the 8 chunk lanes (xor 1, 2, 4), the sums over the keys over the 8 key slots (xor 8, 16, 32).
+// 16 bits are stored once per output value: o_c (forward), every dqkv value (backward); the forward also rounds the un-normalised P
+// to bf16 in registers where the dense forward does, the backward P and dS.  compact row = sequence index of the call.
+constexpr int CLS_NW = 4;
+
+struct ClsArgs {
+  const bf16_t* qkv; int ldqkv;
+  const int* __restrict__ cu; int n_seq, heads; float scale;
+  bf16_t* o_c; int ldo; float* lse_c;                       // forward: outputs; backward: inputs
+  const bf16_t* do_c; int lddo; bf16_t* dqkv; int lddqkv;
+};
+
+__device__ __forceinline__ void unpack8(const uint4& v, float (&f)[8]) {
+  f[0] = bf_lo(v.x); f[1] = bf_hi(v.x); f[2] = bf_lo(v.y); f[3] = bf_hi(v.y);
+  f[4] = bf_lo(v.z); f[5] = bf_hi(v.z); f[6] = bf_lo(v.w); f[7] = bf_hi(v.w);
+}
+__device__ __forceinline__ float dot8(const float (&a)[8], const float (&b)[8]) {
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) s = fmaf(a[i], b[i], s);
+  return s;
+}
+__device__ __forceinline__ uint4 pack8(const float (&f)[8]) {
+  return make_uint4(pack_bf2(f[0], f[1]), pack_bf2(f[2], f[3]), pack_bf2(f[4], f[5]), pack_bf2(f[6], f[7]));
+}
+__device__ __forceinline__ float sum_chunks(float v) {        // over the 8 chunk lanes of a key slot: every lane ends with the sum
+  v += __shfl_xor(v, 1); v += __shfl_xor(v, 2); v += __shfl_xor(v, 4);
+  return v;
+}
+__device__ __forceinline__ float sum_slots(float v) {         // over the 8 key slots of a chunk
+  v += __shfl_xor(v, 8); v += __shfl_xor(v, 16); v += __shfl_xor(v, 32);
+  return v;
+}
+
+__global__ __launch_bounds__(CLS_NW * 64) void attn_cls_fwd_kernel(ClsArgs a) {
+  __shared__ float sc[CLS_NW][256];                          // the pair's scaled scores, then exp(score - max)
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 3, c = lane & 7;
+  const int pair = blockIdx.x * CLS_NW + wave;
+  const bool live = pair < a.n_seq * a.heads;                // (no early exit: every wave of the workgroup meets the barriers)
+  const int s = live ? pair / a.heads : 0, h = live ? pair % a.heads : 0;
+  const int tok0 = a.cu[s];
+  const int len = live ? min(max(a.cu[s + 1] - tok0, 0), 256) : 0;
+  const int inner = a.heads * 64;
+  const bf16_t* base = a.qkv + (size_t)tok0 * a.ldqkv + h * 64 + c * 8;
+  float q[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  if (len > 0) unpack8(*reinterpret_cast<const uint4*>(base), q);
+  float* my = sc[wave];
+  for (int j0 = 0; j0 < len; j0 += 8) {                      // scores: 8 keys per step
+    const int j = j0 + g;
+    float part = 0.f;
+    if (j < len) {
+      float k[8];
+      unpack8(*reinterpret_cast<const uint4*>(base + (size_t)j * a.ldqkv + inner), k);
+      part = dot8(q, k);
+    }
+    part = sum_chunks(part);
+    if (c == 0 && j < len) my[j] = part * a.scale;
+  }
+  __syncthreads();
+  float mx = -INFINITY;
+  for (int j = lane; j < len; j += 64) mx = fmaxf(mx, my[j]);
+  mx = wave_max(mx);
+  float sum = 0.f;
+  for (int j = lane; j < len; j += 64) {
+    const float p = __expf(my[j] - mx);
+    // P V takes P rounded to bf16 and the normaliser the unrounded sum, as attn_fwd_kernel does in front of its second MFMA: the two
+    // forwards then differ by fp32 summation order only (first loss of a captured step 1.4e-7 apart; 3.3e-5 with fp32 P, enough
+    // for Adam's first steps to move the small oracle comparisons of tests/test_gpu_step.py past their gates)
+    my[j] = bf2f(f2bf(p)); sum += p;
+  }
+  sum = wave_sum(sum);
+  __syncthreads();
+  float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int j0 = 0; j0 < len; j0 += 8) {                      // O = P V: 8 keys per step, 8 channels per lane
+    const int j = j0 + g;
+    if (j < len) {
+      float v[8];
+      unpack8(*reinterpret_cast<const uint4*>(base + (size_t)j * a.ldqkv + 2 * inner), v);
+      const float p = my[j];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) acc[i] = fmaf(p, v[i], acc[i]);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) acc[i] = sum_slots(acc[i]);
+  if (len > 0 && g == 0) {
+    const float inv = 1.f / sum;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] *= inv;
+    *reinterpret_cast<uint4*>(a.o_c + (size_t)s * a.ldo + h * 64 + c * 8) = pack8(acc);
+    if (c == 0) a.lse_c[(size_t)s * a.heads + h] = mx + __logf(sum);
+  }
+}
+
+__global__ __launch_bounds__(CLS_NW * 64) void attn_cls_bwd_kernel(ClsArgs a) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 3, c = lane & 7;
+  const int pair = blockIdx.x * CLS_NW + wave;
+  if (pair >= a.n_seq * a.heads) return;                     // (no barrier in this kernel)
+  const int s = pair / a.heads, h = pair % a.heads;
+  const int tok0 = a.cu[s];
+  const int len = min(max(a.cu[s + 1] - tok0, 0), 256);
+  if (len == 0) return;
+  const int inner = a.heads * 64;
+  const bf16_t* base = a.qkv + (size_t)tok0 * a.ldqkv + h * 64 + c * 8;
+  bf16_t* dbase = a.dqkv + (size_t)tok0 * a.lddqkv + h * 64 + c * 8;
+  float q[8], d_o[8], o[8];
+  unpack8(ld_once16(base), q);
+  unpack8(ld_once16(a.do_c + (size_t)s * a.lddo + h * 64 + c * 8), d_o);
+  unpack8(ld_once16(a.o_c + (size_t)s * a.ldo + h * 64 + c * 8), o);
+  const float delta = sum_chunks(dot8(d_o, o));
+  const float lse = a.lse_c[(size_t)s * a.heads + h];
+  float dq[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  const uint4 zero = make_uint4(0, 0, 0, 0);
+  for (int j0 = 0; j0 < len; j0 += 8) {
+    const int j = j0 + g;
+    const bool in = j < len;
+    float k[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, v[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (in) {
+      unpack8(ld_once16(base + (size_t)j * a.ldqkv + inner), k);
+      unpack8(ld_once16(base + (size_t)j * a.ldqkv + 2 * inner), v);
+    }
+    const float sj = sum_chunks(dot8(q, k)) * a.scale;       // (all 64 lanes take part in the shuffles)
+    const float dp = sum_chunks(dot8(d_o, v));
+    if (in) {
+      // (P and dS rounded to bf16 in registers where attn_bwd's MFMAs take them: the pruned step stays within rounding-order noise
+      // of the dense one, which the two-step oracle comparisons of the small configurations need -- Adam's first steps amplify more)
+      const float pf = __expf(sj - lse);
+      const float ds = bf2f(f2bf(pf * (dp - delta) * a.scale));  // dL/d(q . k_j), from the unrounded P as in attn_bwd
+      const float p = bf2f(f2bf(pf));
+      float dk[8], dv[8];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) { dk[i] = ds * q[i]; dv[i] = p * d_o[i]; dq[i] = fmaf(ds, k[i], dq[i]); }
+      bf16_t* row = dbase + (size_t)j * a.lddqkv;
+      if (j > 0) *reinterpret_cast<uint4*>(row) = zero;      // dQ of a row that is no query here
+      *reinterpret_cast<uint4*>(row + inner) = pack8(dk);
+      *reinterpret_cast<uint4*>(row + 2 * inner) = pack8(dv);
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) dq[i] = sum_slots(dq[i]);
+  if (g == 0) *reinterpret_cast<uint4*>(dbase) = pack8(dq);
+}
+
+int check_cls(const ClsArgs& a, int max_len) {
+  LAFS_CHECK_ARG(a.qkv && a.cu && a.o_c && a.lse_c, "null operand");
+  LAFS_CHECK_ARG(a.n_seq > 0 && a.heads > 0 && max_len > 0 && max_len <= 256, "sequence length must be in 1..256");
+  LAFS_CHECK_ARG(a.ldqkv % 8 == 0 && a.ldo % 8 == 0 && a.ldqkv >= 3 * a.heads * 64 && a.ldo >= a.heads * 64,
+                 "row strides must be multiples of 8 elements and hold every head");
+  return LAFS_OK;
+}
+
 }  // namespace
 
 extern "C" int lafs_attention_fwd(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
@@ -919,4 +1075,35 @@ extern "C" int lafs_attention_probs(const void* qkv, int ldqkv, const int32_t* c
   if (nt <= 10) return dispatch_probs<10, 1>(a, stream);
   if (nt <= 13) return dispatch_probs<13, 1>(a, stream);
   return dispatch_probs<16, 1>(a, stream);
+}
+
+extern "C" int lafs_attention_cls_fwd(const void* qkv, int ldqkv, const int32_t* cu_seqlens, int n_seq, int max_len, int heads,
+                                      float scale, void* out_c_bf16, int ldo, float* lse_c, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  ClsArgs a = {};
+  a.qkv = (const bf16_t*)qkv; a.ldqkv = ldqkv; a.cu = cu_seqlens; a.n_seq = n_seq; a.heads = heads; a.scale = scale;
+  a.o_c = (bf16_t*)out_c_bf16; a.ldo = ldo; a.lse_c = lse_c;
+  const int rc = check_cls(a, max_len);
+  if (rc != LAFS_OK) return rc;
+  hipLaunchKernelGGL(attn_cls_fwd_kernel, dim3(ceil_div(n_seq * heads, CLS_NW)), dim3(CLS_NW * 64), 0, stream, a);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_attention_cls_bwd(const void* qkv, int ldqkv, const void* out_c_bf16, int ldo, const void* dout_c_bf16, int lddo,
+                                      const float* lse_c, const int32_t* cu_seqlens, int n_seq, int max_len, int heads, float scale,
+                                      void* dqkv, int lddqkv, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  ClsArgs a = {};
+  a.qkv = (const bf16_t*)qkv; a.ldqkv = ldqkv; a.cu = cu_seqlens; a.n_seq = n_seq; a.heads = heads; a.scale = scale;
+  a.o_c = (bf16_t*)const_cast<void*>(out_c_bf16); a.ldo = ldo; a.lse_c = const_cast<float*>(lse_c);
+  a.do_c = (const bf16_t*)dout_c_bf16; a.lddo = lddo; a.dqkv = (bf16_t*)dqkv; a.lddqkv = lddqkv;
+  const int rc = check_cls(a, max_len);
+  if (rc != LAFS_OK) return rc;
+  LAFS_CHECK_ARG(a.do_c && a.dqkv, "null operand");
+  LAFS_CHECK_ARG(lddo % 8 == 0 && lddqkv % 8 == 0 && lddo >= heads * 64 && lddqkv >= 3 * heads * 64,
+                 "row strides must be multiples of 8 elements and hold every head");
+  hipLaunchKernelGGL(attn_cls_bwd_kernel, dim3(ceil_div(n_seq * heads, CLS_NW)), dim3(CLS_NW * 64), 0, stream, a);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
 }

@@ -30,6 +30,11 @@ struct Carve {
   std::vector<float*> ln_part;    // [layer][norm 1 | 2][row chain 0..3]: per-workgroup gamma / beta sums of the LayerNorm backward
   float* ln_slot(int l, int norm2, int chain) const { return ln_part[((size_t)l * 2 + norm2) * 4 + chain]; }
   float* xalt;                    // ping-pong residual buffer for the no-save path
+  // lafs_trunk_desc::cls_only_last (else NULL): the identity row -> sequence table of the compact cls rows (DropPath scales) and two
+  // f32 [n_seq, dim] row sets (forward: the block input's cls rows | the block's output rows; backward: the gradient stream's)
+  // and the cls attention's outputs o_c (bf16 [n_seq, inner]) | lse_c (f32 [n_seq, heads]): the row chains write them while other chains
+  // may still run earlier blocks -- in a forward-only pass on the ONE buffer set all blocks share -- so they alias no dense buffer
+  int32_t* seq_id; float* xc0; float* xc1; bf16_t* oc; float* lsec;
   Scratch s;
   void* wg_ws; size_t wg_bytes;   // slice partials of the grouped weight-gradient launch (lafs_wgrad_group)
   size_t bytes;
@@ -72,6 +77,14 @@ Carve carve(const lafs_trunk_desc* d, void* ws, int save) {
     b.a = (bf16_t*)take(T * M * 2);
   }
   c.xalt = save ? nullptr : (float*)take(T * D * 4);
+  c.seq_id = nullptr; c.xc0 = c.xc1 = nullptr; c.oc = nullptr; c.lsec = nullptr;
+  if (d->cls_only_last) {
+    c.seq_id = (int32_t*)take((size_t)d->n_seq * 4);
+    c.xc0 = (float*)take((size_t)d->n_seq * D * 4);
+    c.xc1 = (float*)take((size_t)d->n_seq * D * 4);
+    c.oc = (bf16_t*)take((size_t)d->n_seq * I * 2);
+    c.lsec = (float*)take((size_t)d->n_seq * H * 4);
+  }
   if (save) {
     const int nslot = d->wgrad_defer ? d->depth : 2;
     c.s.gbm.resize(nslot); c.s.gba.resize(nslot); c.s.du.resize(nslot); c.s.dqkv.resize(nslot);
@@ -91,8 +104,11 @@ Carve carve(const lafs_trunk_desc* d, void* ws, int save) {
     lafs_wgrad_item it[4];
     block_wgrad_shapes(d, it);
     // (the single-stream backward uses the whole chip: size for whichever plan needs more)
-    const int64_t wb = std::max(lafs_wgrad_group_workspace_bytes(it, 4, d->n_tok, d->wgrad_workgroups),
-                                lafs_wgrad_group_workspace_bytes(it, 4, d->n_tok, 0));
+    int64_t wb = std::max(lafs_wgrad_group_workspace_bytes(it, 4, d->n_tok, d->wgrad_workgroups),
+                          lafs_wgrad_group_workspace_bytes(it, 4, d->n_tok, 0));
+    if (d->cls_only_last)     // the last block's two launches: fc2 / fc1 / proj over the n_seq cls rows, qkv over all rows
+      for (int wg : {d->wgrad_workgroups, 0})
+        wb = std::max({wb, lafs_wgrad_group_workspace_bytes(it, 3, d->n_seq, wg), lafs_wgrad_group_workspace_bytes(it + 3, 1, d->n_tok, wg)});
     c.wg_bytes = wb > 0 ? (size_t)wb : 0;
     c.wg_ws = take(c.wg_bytes > 0 ? c.wg_bytes : 256);
   } else {
@@ -159,9 +175,13 @@ void plan_mlp(const lafs_trunk_desc* d, int save, Range& r) {
   r.ln2_parts = r.bwd_ln2_inside ? lafs_mlp_fused_ln_parts(r.rows) : r.ln1_parts;
 }
 
-int plan(const lafs_trunk_desc* d, int save, lafs_trunk_plan_info* p) {
+// layer_hi: the pass covers blocks below it (a forward covers them all: depth)
+int plan(const lafs_trunk_desc* d, int save, lafs_trunk_plan_info* p, int layer_hi) {
   RUN(check_desc(d));
   *p = lafs_trunk_plan_info{};
+  // The last block on the cls rows alone (include/lafs_hip.h: cls_only_last).  Element-dropout masks are indexed by absolute row,
+  // which a compacted row has lost; the deferred weight gradients (lafs_trunk_wgrad) read dense per-layer operand slots.
+  p->cls_only_last = d->cls_only_last != 0 && d->dropout_p == 0.f && d->wgrad_defer == 0 && layer_hi == d->depth;
   p->whole = Range{0, d->n_tok, 0, 0, d->n_seq, 0};
   plan_mlp(d, save, p->whole);
   // Row ranges.  Nothing in a pass mixes token rows of different sequences: with two crop-resolution groups of full-length sequences
@@ -273,6 +293,98 @@ int attention(const Pass& ps, const Range& r, Launch&& launch) {
   return forked(d, st, fork ? 2 : 1, ng, [&](int k) {
     return launch(d->cu_seqlens + s0[k], ng == 1 ? r.n_seq : d->group_n_seq[r.group + k], d->group_max_len[r.group + k],
                   (fork && k > 0) ? d->ctx->side[0] : st);
+  });
+}
+
+// ---- The last block on the cls rows (plan: cls_only_last).  Compact row i = sequence i; the compact activations live in the first
+// n_seq rows of the layer's own buffers (x1, st2, h2, u, a: written on `stream` once the chains have joined) and of the weight-gradient
+// operand slots; o_c / lse_c, which the chains write, have storage of their own (Carve::oc, lsec).
+__global__ __launch_bounds__(256) void seq_id_kernel(int32_t* __restrict__ t, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) t[i] = i;
+}
+int fill_seq_id(const Pass& ps) {
+  hipLaunchKernelGGL(seq_id_kernel, dim3(ceil_div(ps.d->n_seq, 256)), dim3(256), 0, ps.stream, ps.c.seq_id, ps.d->n_seq);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+// Forward, per row chain: LayerNorm 1 and the qkv GEMM on every row (K and V are needed of every token), then the cls query's attention
+int fwd_cls_chain(const Pass& ps, const Range& r) {
+  const lafs_trunk_desc* d = ps.d;
+  const int l = d->depth - 1;
+  const lafs_block_offsets& o = d->blocks[l];
+  const LayerBuf& b = ps.c.layers[ps.save ? l : 0];
+  const int D = d->dim, I = d->inner, R = r.rows;
+  const size_t rD = (size_t)r.row0 * D, rI = (size_t)r.row0 * I;
+  const bf16_t* sh = reinterpret_cast<const bf16_t*>(d->shadow);
+  hipStream_t st = ps.st(r);
+  if (l == 0 || !r.fwd_next_ln1)
+    RUN(lafs_layernorm_fwd(ps.lay_in[l] + rD, D, d->master + o.ln1_g, d->master + o.ln1_b, d->ln_eps, b.h1 + rD, D, nullptr, 0,
+                           b.st1 + 2 * (size_t)r.row0, R, D, st));
+  RUN(gemm(d->ctx, b.h1 + rD, D, sh + o.w_qkv, D, R, 3 * I, D, LAFS_EPI_BF16, b.qkv + 3 * rI, 3 * I, o.b_qkv >= 0 ? d->master + o.b_qkv : nullptr, st));
+  return attention(ps, r, [&](const int32_t* cu, int nseq, int len, hipStream_t s) {
+    const size_t s0 = (size_t)(cu - d->cu_seqlens);
+    return lafs_attention_cls_fwd(b.qkv, 3 * I, cu, nseq, len, d->heads, d->attn_scale, ps.c.oc + s0 * I, I, ps.c.lsec + s0 * d->heads, s);
+  });
+}
+
+// ... and, once the chains have joined, the row-local rest of the block on all n_seq cls rows at once (on `stream`)
+int fwd_cls_rows(const Pass& ps) {
+  const lafs_trunk_desc* d = ps.d;
+  const int l = d->depth - 1;
+  const lafs_block_offsets& o = d->blocks[l];
+  const LayerBuf& b = ps.c.layers[ps.save ? l : 0];
+  const Carve& c = ps.c;
+  const int D = d->dim, I = d->inner, M = d->mlp, S = d->n_seq;
+  const bf16_t* sh = reinterpret_cast<const bf16_t*>(d->shadow);
+  hipStream_t st = ps.stream;
+  RUN(fill_seq_id(ps));
+  RUN(lafs_gather_cls(ps.lay_in[l], D, d->cu_seqlens, S, D, c.xc0, st));
+  RUN(gemm(d->ctx, c.oc, I, sh + o.w_proj, I, S, D, I, LAFS_EPI_RESID_F32, b.x1, D, d->master + o.b_proj, st, nullptr, 0, c.xc0, D, ps.scale(l, 0),
+           c.seq_id));
+  RUN(lafs_layernorm_fwd(b.x1, D, d->master + o.ln2_g, d->master + o.ln2_b, d->ln_eps, b.h2, D, nullptr, 0, b.st2, S, D, st));
+  RUN(gemm(d->ctx, b.h2, D, sh + o.w_fc1, D, S, M, D, LAFS_EPI_BF16_GELU, ps.save ? b.u : nullptr, M, d->master + o.b_fc1, st, b.a, M, nullptr, 0,
+           nullptr, nullptr, nullptr, 0, 0.f, 0u, LAFS_GELU_SAVE_GRAD));
+  RUN(gemm(d->ctx, b.a, M, sh + o.w_fc2, M, S, D, M, LAFS_EPI_RESID_F32, c.xc1, D, d->master + o.b_fc2, st, nullptr, 0, b.x1, D, ps.scale(l, 1),
+           c.seq_id));
+  return lafs_scatter_cls(c.xc1, d->cu_seqlens, S, D, ps.lay_out[l], D, st);
+}
+
+// Backward, on `stream` in front of the chains: the cls rows of g through the MLP, LayerNorm 2 and the projection
+int bwd_cls_rows(const Pass& ps) {
+  const lafs_trunk_desc* d = ps.d;
+  const int l = d->depth - 1;
+  const lafs_block_offsets& o = d->blocks[l];
+  const LayerBuf& b = ps.c.layers[l];
+  const Carve& c = ps.c;
+  const Scratch& s = c.s;
+  const int p = wg_slot(d, l), D = d->dim, I = d->inner, M = d->mlp, S = d->n_seq;
+  const bf16_t* sht = reinterpret_cast<const bf16_t*>(d->shadow_t);
+  hipStream_t st = ps.stream;
+  // (c.seq_id: the identity table the forward of this workspace wrote)
+  RUN(lafs_gather_cls(ps.g, D, d->cu_seqlens, S, D, c.xc0, st));
+  RUN(lafs_scale_cast_bf16(c.xc0, D, s.gbm[p], D, ps.scale(l, 1), c.seq_id, S, D, 0.f, 0u, nullptr, 0, st));
+  RUN(gemm(d->ctx, s.gbm[p], D, sht + o.w_fc2_t, D, S, M, D, LAFS_EPI_DGELU_BF16, s.du[p], M, nullptr, st, nullptr, 0, nullptr, 0, nullptr, nullptr,
+           b.u, M, 0.f, 0u, LAFS_GELU_SAVE_GRAD));
+  RUN(gemm(d->ctx, s.du[p], M, sht + o.w_fc1_t, M, S, D, M, LAFS_EPI_BF16, s.dh, D, nullptr, st));
+  RUN(lafs_layernorm_bwd(s.dh, D, nullptr, 0, b.x1, D, b.st2, d->master + o.ln2_g, c.xc0, D, 1, s.gba[p], D, ps.scale(l, 0), c.seq_id,
+                         d->grad + o.ln2_g, d->grad + o.ln2_b, S, D, 0.f, 0u, nullptr, 0, c.ln_slot(l, 1, 0), st));
+  RUN(gemm(d->ctx, s.gba[p], D, sht + o.w_proj_t, D, S, I, D, LAFS_EPI_BF16, s.d_o, I, nullptr, st));
+  return lafs_scatter_cls(c.xc0, d->cu_seqlens, S, D, ps.g, D, st);
+}
+
+// ... then per row chain: the cls query's attention backward fills the chain's whole dqkv range (dK, dV; dQ zero off the cls rows)
+int bwd_cls_chain(const Pass& ps, const Range& r) {
+  const lafs_trunk_desc* d = ps.d;
+  const int l = d->depth - 1, I = d->inner;
+  const LayerBuf& b = ps.c.layers[l];
+  const Scratch& s = ps.c.s;
+  bf16_t* dqkv = s.dqkv[wg_slot(d, l)];
+  return attention(ps, r, [&](const int32_t* cu, int nseq, int len, hipStream_t as) {
+    const size_t s0 = (size_t)(cu - d->cu_seqlens);
+    return lafs_attention_cls_bwd(b.qkv, 3 * I, ps.c.oc + s0 * I, I, s.d_o + s0 * I, I, ps.c.lsec + s0 * d->heads, cu, nseq, len, d->heads, d->attn_scale,
+                                  dqkv, 3 * I, as);
   });
 }
 
@@ -415,19 +527,26 @@ extern "C" int64_t lafs_trunk_workspace_bytes(const lafs_trunk_desc* d, int save
 
 extern "C" int lafs_trunk_plan(const lafs_trunk_desc* d, int save_for_backward, lafs_trunk_plan_info* out) {
   LAFS_CHECK_ARG(out != nullptr, "null plan");
-  return plan(d, save_for_backward, out);
+  return plan(d, save_for_backward, out, d != nullptr ? d->depth : 0);
+}
+
+extern "C" int lafs_trunk_plan_layers(const lafs_trunk_desc* d, int save_for_backward, int layer_hi, int layer_lo, lafs_trunk_plan_info* out) {
+  LAFS_CHECK_ARG(out != nullptr, "null plan");
+  RUN(check_desc(d));
+  LAFS_CHECK_ARG(0 <= layer_lo && layer_lo < layer_hi && layer_hi <= d->depth, "bad layer range");
+  return plan(d, save_for_backward, out, layer_hi);
 }
 
 extern "C" int lafs_trunk_row_ranges(const lafs_trunk_desc* d) {
   lafs_trunk_plan_info p;
-  return plan(d, 0, &p) == LAFS_OK ? p.n_ranges : -1;
+  return plan(d, 0, &p, d != nullptr ? d->depth : 0) == LAFS_OK ? p.n_ranges : -1;
 }
 
 extern "C" int lafs_trunk_forward(const lafs_trunk_desc* d, const float* x_in, float* x_out, void* workspace,
                                   int save_for_backward, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   lafs_trunk_plan_info p;
-  RUN(plan(d, save_for_backward, &p));
+  RUN(plan(d, save_for_backward, &p, d != nullptr ? d->depth : 0));
   LAFS_CHECK_ARG(x_in && x_out && workspace, "null buffer");
   const Carve c = carve(d, workspace, save_for_backward);
   Pass ps{d, c, p, stream, save_for_backward, x_in, nullptr, std::vector<const float*>(d->depth), std::vector<float*>(d->depth)};
@@ -439,24 +558,31 @@ extern "C" int lafs_trunk_forward(const lafs_trunk_desc* d, const float* x_in, f
     else nxt = (cur == c.xalt) ? x_out : c.xalt;            // ping-pong; never aliases x_in
     ps.lay_in[l] = cur; ps.lay_out[l] = nxt; cur = nxt;
   }
-  if (!p.mlp_merged)          // every range runs all layers on its stream; the side streams join behind everything `stream` has enqueued
-    return forked(d, stream, p.n_ranges, p.n_ranges, [&](int i) {
-      for (int l = 0; l < d->depth; ++l) {
+  const int dense = p.cls_only_last ? d->depth - 1 : d->depth;      // blocks that run on every row
+  if (!p.mlp_merged) {        // every range runs all layers on its stream; the side streams join behind everything `stream` has enqueued
+    RUN(forked(d, stream, p.n_ranges, p.n_ranges, [&](int i) {
+      for (int l = 0; l < dense; ++l) {
         RUN(fwd_attn_branch(ps, p.range[i], l));
         RUN(fwd_mlp_branch(ps, p.range[i], l));
       }
+      if (p.cls_only_last) RUN(fwd_cls_chain(ps, p.range[i]));
       return LAFS_OK;
-    });
-  for (int l = 0; l < d->depth; ++l) {
-    RUN(forked(d, stream, p.n_ranges, p.n_ranges, [&](int i) { return fwd_attn_branch(ps, p.range[i], l); }));
-    RUN(fwd_mlp_branch(ps, p.whole, l));
+    }));
+  } else {
+    for (int l = 0; l < dense; ++l) {
+      RUN(forked(d, stream, p.n_ranges, p.n_ranges, [&](int i) { return fwd_attn_branch(ps, p.range[i], l); }));
+      RUN(fwd_mlp_branch(ps, p.whole, l));
+    }
+    if (p.cls_only_last) RUN(forked(d, stream, p.n_ranges, p.n_ranges, [&](int i) { return fwd_cls_chain(ps, p.range[i]); }));
   }
-  return LAFS_OK;
+  return p.cls_only_last ? fwd_cls_rows(ps) : LAFS_OK;
 }
 
 // The block's four weight gradients: ONE grouped launch, once all their operands exist.  Its 48 (ViT-S) output tiles x 5 token
 // slices fill the chip together: 4x fewer slices -> 4x less partial-sum traffic than four separate launches (csrc/wgrad.hip)
-static int block_wgrad(const lafs_trunk_desc* d, const Carve& c, int l, int max_wg, hipStream_t st) {
+// (cls_rows: the last block under the plan's cls_only_last -- fc2 / fc1 / proj sum over the n_seq compact rows of the same buffers, qkv
+// over all rows: two launches, in order on the one stream that owns the slice workspace)
+static int block_wgrad(const lafs_trunk_desc* d, const Carve& c, int l, int max_wg, hipStream_t st, bool cls_rows = false) {
   const lafs_block_offsets& o = d->blocks[l];
   const LayerBuf& b = c.layers[l];
   const Scratch& s = c.s;
@@ -469,6 +595,11 @@ static int block_wgrad(const lafs_trunk_desc* d, const Carve& c, int l, int max_
   it[2].A = s.gba[p]; it[2].B = b.o; it[2].C = gr + o.w_proj; it[2].colsum_a = gr + o.b_proj;
   it[3].A = s.dqkv[p]; it[3].B = b.h1; it[3].C = gr + o.w_qkv; it[3].colsum_a = o.b_qkv >= 0 ? gr + o.b_qkv : nullptr;
   for (auto& x : it) x.accumulate = d->wgrad_overwrite ? 0 : 1;
+  if (cls_rows) {
+    it[2].B = c.oc;
+    RUN(lafs_wgrad_group(it, 3, d->n_seq, max_wg, c.wg_ws, (int64_t)c.wg_bytes, st));
+    return lafs_wgrad_group(it + 3, 1, d->n_tok, max_wg, c.wg_ws, (int64_t)c.wg_bytes, st);
+  }
   return lafs_wgrad_group(it, 4, d->n_tok, max_wg, c.wg_ws, (int64_t)c.wg_bytes, st);
 }
 
@@ -476,9 +607,10 @@ extern "C" int lafs_trunk_backward(const lafs_trunk_desc* d, const float* x_in, 
                                    int layer_lo, hipStream_t wgrad_stream, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   lafs_trunk_plan_info p;
-  RUN(plan(d, 1, &p));
-  LAFS_CHECK_ARG(x_in && g && workspace && d->shadow_t && d->grad, "null buffer");
+  RUN(check_desc(d));
   LAFS_CHECK_ARG(0 <= layer_lo && layer_lo < layer_hi && layer_hi <= d->depth, "bad layer range");
+  RUN(plan(d, 1, &p, layer_hi));
+  LAFS_CHECK_ARG(x_in && g && workspace && d->shadow_t && d->grad, "null buffer");
   const Carve c = carve(d, workspace, 1);
   const Pass ps{d, c, p, stream, 1, x_in, g};
   const bool defer = d->wgrad_defer != 0;     // no weight-gradient launches here: lafs_trunk_wgrad issues them later from the per-layer slots
@@ -497,8 +629,11 @@ extern "C" int lafs_trunk_backward(const lafs_trunk_desc* d, const float* x_in, 
     if (hipEventRecord(e, stream) != hipSuccess || hipStreamWaitEvent(s2, e, 0) != hipSuccess) ev_failed = true;
   };
   std::vector<hipEvent_t> done(d->depth, nullptr);
-  RUN(lafs_scale_cast_bf16(g, d->dim, c.s.gbm[wg_slot(d, layer_hi - 1)], d->dim, ps.scale(layer_hi - 1, 1), d->row2seq, d->n_tok, d->dim,
-                           d->dropout_p, ps.seed(layer_hi - 1, 2), d->dropout_step, 0, stream));
+  const bool cls = p.cls_only_last != 0;      // (layer_hi == depth) the first block of this walk runs on the cls rows behind its qkv GEMM
+  if (cls) RUN(bwd_cls_rows(ps));
+  else
+    RUN(lafs_scale_cast_bf16(g, d->dim, c.s.gbm[wg_slot(d, layer_hi - 1)], d->dim, ps.scale(layer_hi - 1, 1), d->row2seq, d->n_tok, d->dim,
+                             d->dropout_p, ps.seed(layer_hi - 1, 2), d->dropout_step, 0, stream));
   // One forked section = the tail of layer l2 and the head of layer l1 = l2 - 1 for every row range: with two crop-resolution
   // groups of full-length sequences the row ranges run beside each other (range i on stream i), forked and joined once per layer
   // -- the pattern hipGraph captures; a chain that stays forked across layers and meets the weight-gradient stream's events does
@@ -506,7 +641,7 @@ extern "C" int lafs_trunk_backward(const lafs_trunk_desc* d, const float* x_in, 
   auto section = [&](int l2, int l1) -> int {
     return forked(d, stream, p.n_ranges, p.n_ranges, [&](int i) {
       if (l2 >= 0) RUN(bwd_tail(ps, p.range[i], l2));
-      if (l1 >= 0) RUN(bwd_head(ps, p.range[i], l1));
+      if (l1 >= 0) RUN((cls && l1 == d->depth - 1) ? bwd_cls_chain(ps, p.range[i]) : bwd_head(ps, p.range[i], l1));
       return LAFS_OK;
     });
   };
@@ -514,7 +649,7 @@ extern "C" int lafs_trunk_backward(const lafs_trunk_desc* d, const float* x_in, 
   auto wgrad = [&](int l) -> int {
     if (defer) return LAFS_OK;
     fork();
-    RUN(block_wgrad(d, c, l, two ? d->wgrad_workgroups : 0, s2));
+    RUN(block_wgrad(d, c, l, two ? d->wgrad_workgroups : 0, s2, cls && l == d->depth - 1));
     if (two) { done[l] = ev[evi++]; if (hipEventRecord(done[l], s2) != hipSuccess) ev_failed = true; }
     return LAFS_OK;
   };
@@ -539,6 +674,10 @@ extern "C" int lafs_trunk_backward(const lafs_trunk_desc* d, const float* x_in, 
       for (int i = 0; i < p.n_ranges; ++i) {
         it.part[i] = c.ln_slot(l, k, i);
         it.n_parts[i] = k == 0 ? p.range[i].ln1_parts : p.range[i].ln2_parts;
+      }
+      if (cls && l == d->depth - 1 && k == 1) {       // LayerNorm 2 of the cls rows: one launch over n_seq rows, chain 0's slots
+        for (int i = 0; i < 4; ++i) { it.part[i] = nullptr; it.n_parts[i] = 0; }
+        it.part[0] = c.ln_slot(l, 1, 0); it.n_parts[0] = lafs_layernorm_bwd_parts(d->n_seq, d->dim);
       }
       it.dgamma = d->grad + (k == 0 ? o.ln1_g : o.ln2_g); it.dbeta = d->grad + (k == 0 ? o.ln1_b : o.ln2_b);
       items.push_back(it);

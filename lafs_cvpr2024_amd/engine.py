@@ -109,6 +109,9 @@ class LafsPretrainEngine:
         # the library's side streams / events / kernel options of THIS engine (created now: nothing is created inside a capture;
         # two engines share no stream or event).  The environment's A/B switches are read by _lib.Ctx, not by the library.
         self.ctx = _lib.Ctx(self.device)
+        # Both trunks are read through their cls rows alone (head on x[:, 0]): the last block runs on those rows behind its qkv GEMM
+        # (lafs_trunk_desc::cls_only_last; the plan keeps trunks with element dropout dense).  LAFS_CLS_ONLY_LAST=0: dense, for A/B.
+        self.cls_only_last = _lib.Ctx.env_cls_only_last()
         # The row chains (long / short sequences on two streams) pay on the ViT-S trunk, whose K = 384 kernels leave CUs idle; the
         # Part-fViT trunk's wide GEMMs run on one-workgroup-per-CU persistent tiles (gemm_big.hip) that want the whole chip and the
         # merged 44 160 rows (753 tiles of 176x256 = 2.94 rounds): `mynet` pair 36.1 ms with two chains, 35.4-35.5 with one.
@@ -337,7 +340,7 @@ class LafsPretrainEngine:
             drop_t = self._drop_scales(self.keep_t, self.drop_t, 1) if vit_t.training else None   # rate 0 for the DINO ViT teacher
             dd_t = self._dropout_cfg(vit_t, self.dropout_seed_t)
             feat_t, _, _ = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False, dropout=dd_t,
-                                          bn_training=vit_t.training)
+                                          bn_training=vit_t.training, cls_only_last=self.cls_only_last)
             if self.fvit and vit_t.training:           # one forward of one group (device add: no host sync, capturable)
                 self.bn_t.num_batches_tracked.add_(1)
             _, st_ht = Fn.head_forward(ta, self.head_prefix_t, feat_t, self.K, save=False, logits=self._logits_t, skip_logits=self.fused_head)
@@ -349,7 +352,7 @@ class LafsPretrainEngine:
         feat_s, st_v, _ = Fn.vit_forward(sa, self.spec_s, self.geom_s, imgs, self._pos_tokens(sa, self.spec_s, self.pos_s), drop,
                                          save=True, dropout=dd_s, wgrad_overwrite=True,
                                          wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0,
-                                         bn_training=vit.training)
+                                         bn_training=vit.training, cls_only_last=self.cls_only_last)
         if self.fvit and vit.training:                 # the reference's forward runs the head once per crop group (:1556-1569)
             self.bn_s.num_batches_tracked.add_(len(self.geom_s.groups))
         _, st_h = Fn.head_forward(sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)
@@ -389,14 +392,15 @@ class LafsPretrainEngine:
             drop_t = self._drop_scales(self.keep_t, self.drop_t, 1) if vit_t.training else None
             feat_t, st_t, _ = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False,
                                              dropout=self._dropout_cfg(vit_t, self.dropout_seed_t), bn_training=vit_t.training,
-                                             bn_partial=self.bn_x.slot(1) if vit_t.training else None)
+                                             bn_partial=self.bn_x.slot(1) if vit_t.training else None, cls_only_last=self.cls_only_last)
         vit = self.student.backbone
         drop = self._drop_scales(self.keep_s, self.drop_s, 0) if vit.training else None
         imgs = [self.in_global_all] + ([self.in_local_all] if self.n_local else [])
         feat_s, st_v, _ = Fn.vit_forward(sa, self.spec_s, self.geom_s, imgs, self._pos_tokens(sa, self.spec_s, self.pos_s), drop,
                                          save=True, dropout=self._dropout_cfg(vit, self.dropout_seed_s), wgrad_overwrite=True,
                                          wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0,
-                                         bn_training=vit.training, bn_partial=self.bn_x.slot(0) if vit.training else None)
+                                         bn_training=vit.training, bn_partial=self.bn_x.slot(0) if vit.training else None,
+                                         cls_only_last=self.cls_only_last)
         cur.wait_stream(side)
         self._st = dict(vit=st_v, vit_t=st_t, feat_s=feat_s, feat_t=feat_t)
 

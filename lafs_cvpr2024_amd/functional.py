@@ -86,8 +86,9 @@ class TrunkSpec:
 
 
 def make_trunk_desc(arena, spec: TrunkSpec, geom: PackedGeometry, drop_scales=None, with_grad=True, dropout_p=0.0, dropout_seed=0,
-                    wgrad_overwrite=False, wgrad_workgroups=0, dropout_step=None, wgrad_defer=False):
-    """Build the C descriptor (keeps the ctypes block array alive on the returned object)."""
+                    wgrad_overwrite=False, wgrad_workgroups=0, dropout_step=None, wgrad_defer=False, cls_only_last=False):
+    """Build the C descriptor (keeps the ctypes block array alive on the returned object).
+    cls_only_last: the caller reads the trunk's output through the cls rows alone (lafs_trunk_desc::cls_only_last)."""
     blocks = (_lib.BlockOffsets * spec.depth)()
     for i, nm in enumerate(spec.block_names):
         b = blocks[i]
@@ -110,6 +111,7 @@ def make_trunk_desc(arena, spec: TrunkSpec, geom: PackedGeometry, drop_scales=No
     d.wgrad_overwrite = 1 if wgrad_overwrite else 0
     d.wgrad_defer = 1 if wgrad_defer else 0
     d.wgrad_workgroups = int(wgrad_workgroups)
+    d.cls_only_last = 1 if cls_only_last else 0
     if 1 < len(geom.groups) <= 4:                        # one attention launch per crop resolution
         d.n_groups = len(geom.groups)
         for gi, (n_img, side) in enumerate(geom.groups):
@@ -170,14 +172,16 @@ def bn_group_rows(geom: PackedGeometry):
 
 def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, drop_scales=None, save=True,
                 ws=None, x_in=None, x_out=None, dropout=None, wgrad_overwrite=False, wgrad_workgroups=0, wgrad_defer=False,
-                bn_training=False, bn_partial=None):
+                bn_training=False, bn_partial=None, cls_only_last=False):
     """imgs: list of fp32 NCHW tensors (one per group); pos_tokens: list of fp32 [npatch+1, D] per group.
     dropout: None or (p_trunk, p_embedding, seed[, step]): element dropout of Part-fViT (counter-based masks, see lafs_hip.h);
     `step`: a DEVICE float tensor whose value x 7919 is added to the seed inside the kernels (graph-captured steps).
     bn_training (BatchNorm1d head only): batch statistics over the n_seq cls rows + running-statistic update, else running statistics.
     bn_partial (BatchNorm1d head in training only): f32 [G, 1 + 2 D] that receives this rank's partial statistics of the cls rows
     (lafs_bn1d_groups_stats); the pass STOPS there -- feat is None until vit_forward_sync_bn has the partials of all ranks.
-    Returns (feat f32 [n_seq, D], state)."""
+    cls_only_last: the last block runs on the cls rows alone where the trunk's plan allows (lafs_trunk_desc::cls_only_last): of the
+    returned x_out only the cls rows are then defined, and the backward takes a gradient that is zero elsewhere (vit_backward_begin's).
+    Returns (feat f32 [n_seq, D], state, x_out)."""
     D = spec.trunk.dim
     dev = imgs[0].device
     pre = spec.prefix
@@ -188,7 +192,8 @@ def vit_forward(arena, spec: ViTSpec, geom: PackedGeometry, imgs, pos_tokens, dr
     dstep = dropout[3] if (dropout is not None and len(dropout) > 3) else None
     st.dropout = (p_trunk, p_emb, dseed, dstep)
     st.desc = make_trunk_desc(arena, spec.trunk, geom, drop_scales, with_grad=save, dropout_p=p_trunk, dropout_seed=dseed,
-                              wgrad_overwrite=wgrad_overwrite, wgrad_workgroups=wgrad_workgroups, dropout_step=dstep, wgrad_defer=wgrad_defer)
+                              wgrad_overwrite=wgrad_overwrite, wgrad_workgroups=wgrad_workgroups, dropout_step=dstep, wgrad_defer=wgrad_defer,
+                              cls_only_last=cls_only_last)
     st.ws = ws if ws is not None else trunk_workspace(st.desc, save, dev)
     st.x_in = x_in if x_in is not None else torch.empty(geom.n_tok, D, device=dev, dtype=f32)
     if x_out is None:

@@ -57,7 +57,7 @@ enum {
   LAFS_OPT_SIDE_STREAMS = 0,   /* 1: row chains / attention groups / weight gradients may use the context's side streams; 0: caller's stream only */
   LAFS_OPT_ROW_CHAINS = 1,     /* 1, 2 (default) or 4 chains of launches over the crop-resolution groups' rows (csrc/engine.hip) */
   LAFS_OPT_KRES_MASK = 2,      /* epilogues routed to the K-resident GEMM: 1 plain, 2 GELU, 4 residual, 8 GELU' (default 15) */
-  LAFS_OPT_KRES_MIN_ITEMS = 3, /* least items per workgroup run of the K-resident GEMM (default 4) */
+  LAFS_OPT_KRES_MIN_ITEMS = 3, /* accepted and unused: the K-resident GEMM's runs are no longer bounded from below (kres_partition, csrc/gemm_kres.hip) */
   LAFS_OPT_NT_WIDE = 4,        /* tiled GEMM: 128x384 tiles where they fit one round of the chip (default 1) */
   LAFS_OPT_NT_TALL = 5,        /* tiled GEMM: 160-row tiles where they save a round of workgroup slots (default 1) */
   LAFS_OPT_COMM_CUS = 6,       /* data-parallel runs: CUs left to the collective library's kernels by the K-resident GEMM (default 0) */

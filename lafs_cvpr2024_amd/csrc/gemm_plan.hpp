@@ -8,6 +8,7 @@ struct NtPlan {
   lafs_gemm_nt_plan_info info;     // route, tile, stage depth, threads, K slices, workgroups: what lafs_gemm_nt_plan reports
   int inst, klen;                  // tiled kernel: the gemm_nt_kernel instantiation (NtInst of gemm.hip), length of a K slice
   int geo;                         // gemm_big: 1 = 192 x 256, 2 = 256 x 256 (two waves per SIMD), 3 = 176 x 256, 4 = 160 x 256
+  int kres_parts;                  // K-resident kernel: contiguous parts a row unit's column blocks are split into, one workgroup each
 };
 
 // *_eligible: whether this kernel is the one to run a request that plan() has VALIDATED (the measured shape and option thresholds

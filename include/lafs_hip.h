@@ -1015,6 +1015,39 @@ int lafs_ijb_search(const double* unit, int n_templates, int D, const int32_t* p
                     int n_gallery, const int32_t* mate, int k, double* top_score, int32_t* top_idx, double* mate_score,
                     int32_t* mate_rank, double* best_nonmate, void* workspace, size_t workspace_bytes, hipStream_t stream);
 
+/* Weighted k-NN on frozen float32 features (csrc/knn.hip): every query row against every bank row, the first k bank positions per
+ * query, then DINO's exp(score / T)-weighted class vote.  The n_query x n_bank scores are never stored.  No counterpart in the
+ * reference; the vote restates the formula of DINO's eval_knn.py knn_classifier.
+ *   bank f32 [n_bank, ldb] and query f32 [n_query, ldq], of which the first D columns are used (only those are read); D in
+ *   [1, 1024], k in [1, 256], bank_pos0 >= 0 and bank_pos0 + n_bank < 2^31.  Alignment rule: ldb % 4 == 0, ldq % 4 == 0 and both
+ *   base pointers 16-byte aligned (rows are read 16 bytes at a time).  Rows are taken as given: the host normalises them.
+ * Score: the float32 dot product on v_mfma_f32_32x32x2_f32, a k-ordered fmaf chain from 0: columns in ascending order, zeros from D
+ *   up to the next multiple of 32.  The order is a function of D alone: the same two rows give the same 32 bits wherever they sit
+ *   -- in a tile, a workgroup, a bank chunk or a split.  A NaN score is returned as the canonical quiet NaN.
+ * Ranking order of one query's bank positions (bank_pos0 + row): larger score first; equal scores: smaller position first; NaN after
+ *   every number, among NaNs the smaller position first.
+ * top_score f32 / top_idx i32 [n_query, k]: the first k entries of that order; with fewer than k candidates the tail is idx -1,
+ *   score NaN.  exclude i32 [n_query] or NULL: the one position never returned for that query (-1: none) -- leave-one-out when the
+ *   bank holds the queries.
+ * merge != 0: top_score / top_idx already hold a valid result over OTHER positions (earlier bank chunks); this call's candidates are
+ *   merged into it in the same order.  A bank presented in any number of chunks, in any chunk order, gives the same bits as one call.
+ * splits: the bank of one call is divided among `splits` workgroups per 64 queries (0: chosen from n_query, n_bank and the CU count;
+ *   at most 32 and at most one per 128 bank rows are used); partial lists go to `workspace` and a merge pass combines them.  The
+ *   result is bit-identical for every value.  lafs_knn_workspace returns the bytes lafs_knn_search needs for the same four
+ *   arguments (0 when one split runs: the lists are then the output rows and workspace may be NULL); a shorter workspace is refused.
+ * Every refusal (negative code) happens before anything is launched: nothing is written.
+ * lafs_knn_vote: for every query and every ks[i] (HOST array of n_ks <= 8 values, ascending, each in [1, k]) each of the first
+ *   ks[i] list entries with 0 <= idx < n_label gives exp(score / temperature) to class bank_label[idx] (bank_label i32 [n_label] on
+ *   the device, indexed by position; any non-negative int32).  A class's vote is the float32 sum of its entries in list order.
+ *   Classes are ordered by larger vote first, then smaller label; pred i32 / vote f32 [n_ks, n_query, 5] hold the first five,
+ *   unused slots -1 and 0.  Only the at most k retrieved labels are touched: the cost does not depend on the number of classes. */
+int64_t lafs_knn_workspace(int n_query, int64_t n_bank, int k, int splits);
+int lafs_knn_search(const float* bank, int ldb, int64_t n_bank, int64_t bank_pos0, const float* query, int ldq, int n_query, int D, int k,
+                    const int32_t* exclude, int merge, int splits, float* top_score, int32_t* top_idx, void* workspace,
+                    size_t workspace_bytes, hipStream_t stream);
+int lafs_knn_vote(const float* top_score, const int32_t* top_idx, int n_query, int k, const int32_t* bank_label, int64_t n_label,
+                  const int32_t* ks, int n_ks, float temperature, int32_t* pred, float* vote, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------
  * TRAINABLE landmark CNN of the fine-tune step (csrc/landmark_train.hip; reference face_pre_pro/mobilenet.py:224-313 trained through
  * ViT_face.py:679-711 by train_largescale.py:785-891).  Activations are NHWC bf16 [N H W, ld] matrices, ld = channel count padded

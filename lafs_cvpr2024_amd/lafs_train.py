@@ -111,6 +111,14 @@ def get_args_parser():
     p.add_argument('--sync_bn', default=False, type=utils.bool_flag,
                    help="--arch fvit: BatchNorm1d statistics over the cls rows of all ranks (the reference's SyncBatchNorm conversion, "
                         "lafs_train.py:362-364); required for --arch fvit on more than one rank")
+    p.add_argument('--knn_freq', default=0, type=int,
+                   help="every N-th epoch, after the checkpoint is written, rank 0 runs the weighted k-NN evaluation (knn.py) on the live "
+                        "teacher backbone and adds knn_top1_k{K} / knn_top5_k{K} to that epoch's log.txt line; 0: off, nothing is built or read")
+    p.add_argument('--knn_data_path', default='', type=str, help="--knn_freq: directory with the labelled train.rec / train.idx to evaluate on")
+    p.add_argument('--knn_nb', default='10,20,100,200', type=str)
+    p.add_argument('--knn_temperature', default=0.07, type=float)
+    p.add_argument('--knn_holdout', default=1, type=int)
+    p.add_argument('--knn_max_images', default=0, type=int)
     p.add_argument("--dist_url", default="env://", type=str)
     p.add_argument("--local_rank", default=0, type=int)
     return p
@@ -215,17 +223,22 @@ class RecordIOViews:
             yield self.aug(u8), None
 
 
-def build_landmark_frontend(args, device):
-    """Frozen landmark CNN (reference lafs_train.py:241-269: face_landmark_4simmin_glo_loc, eval mode) + the fused front-end."""
+def build_landmark_cnn(landmark_ckpt):
+    """The landmark CNN of the reference (lafs_train.py:241-269: face_landmark_4simmin_glo_loc) with `landmark_ckpt` loaded when given."""
     from .face_pre_pro.ViT_face import face_landmark_4simmin_glo_loc
-    from .landmark_frontend import LandmarkFrontEnd
     cnn = face_landmark_4simmin_glo_loc(loss_type='None', GPU_ID=None, num_class=10, image_size=112, patch_size=8, dim=768,
                                         depth=12, heads=11, mlp_dim=2048)
-    if args.landmark_ckpt:
-        sd = torch.load(args.landmark_ckpt, map_location="cpu", weights_only=False)
+    if landmark_ckpt:
+        sd = torch.load(landmark_ckpt, map_location="cpu", weights_only=False)
         sd = {k[len("module."):] if k.startswith("module.") else k: v for k, v in sd.items()}
         print("=> landmark CNN:", cnn.load_state_dict(sd, strict=False))
-    return LandmarkFrontEnd(cnn, args.batch_size_per_gpu, n_local=args.local_crops_number, device=device)
+    return cnn
+
+
+def build_landmark_frontend(args, device):
+    """Frozen landmark CNN (eval mode) + the fused front-end."""
+    from .landmark_frontend import LandmarkFrontEnd
+    return LandmarkFrontEnd(build_landmark_cnn(args.landmark_ckpt), args.batch_size_per_gpu, n_local=args.local_crops_number, device=device)
 
 
 def check_views(args):
@@ -255,6 +268,56 @@ def build_dino_views(args, device):
     return DeviceDinoAugmenter(args.batch_size_per_gpu, n_local=args.local_crops_number, global_scale=args.global_crops_scale,
                                local_scale=args.local_crops_scale, mean=mean, std=std, device=device,
                                seed=args.seed + utils.get_rank())
+
+
+class KnnProbe:
+    """--knn_freq: the k-NN evaluation of knn.py on the live teacher backbone.  Built only when the flag is set; the record file is
+    opened at the first evaluation.  The evaluation leaves the run as it found it: the teacher's training flag and the random
+    generators of the host and the device are put back, the arena's 16-bit copies are re-derived from the fp32 master before it
+    (the values the engine itself keeps), and nothing else the step reads is written."""
+
+    def __init__(self, args, engine, teacher_backbone, frontend, device):
+        if not args.knn_data_path:
+            raise SystemExit("--knn_freq needs --knn_data_path")
+        self.landmark_teacher = getattr(frontend, "cnn", None)       # the frozen CNN of the landmark front-end (--views lafs)
+        if args.arch == 'mynet' and self.landmark_teacher is None:
+            raise SystemExit("--knn_freq with --arch mynet needs the landmark front-end (--data recordio, synthetic_u8 or synthetic_views)")
+        from . import knn
+        self.knn, self.args, self.engine, self.model, self.device = knn, args, engine, teacher_backbone, device
+        self.ks = knn.parse_ks(args.knn_nb)
+        self.records = None
+
+    def due(self, epoch):
+        return (epoch + 1) % self.args.knn_freq == 0
+
+    def __call__(self):
+        """-> {knn_top1_k{K}, knn_top5_k{K}} (rank 0; the other ranks wait at the caller's barrier)."""
+        a = self.args
+        if self.records is None:
+            self.records = self.knn.load_records(a.knn_data_path, a.knn_max_images)
+        cpu_rng, dev_rng = torch.get_rng_state(), torch.cuda.get_rng_state(self.device)
+        was_training = self.model.training
+        try:
+            self.engine.ta.refresh_shadows()
+            res, _, _ = self.knn.evaluate_backbone(self.model, self.records, args=a, ks=self.ks, temperature=a.knn_temperature,
+                                                   holdout=a.knn_holdout, batch_size=a.batch_size_per_gpu, decode=a.decode, num_workers=0,
+                                                   landmark_teacher=self.landmark_teacher, device=self.device)
+        finally:
+            self.model.train(was_training)
+            torch.set_rng_state(cpu_rng)
+            torch.cuda.set_rng_state(dev_rng, self.device)
+        out = {}
+        for k, (t1, t5) in res.items():
+            print(f"{k}-NN classifier result: Top1: {t1:.4f}, Top5: {t5:.4f}")
+            out[f'knn_top1_k{k}'], out[f'knn_top5_k{k}'] = t1, t5
+        return out
+
+
+def build_knn_probe(args, engine, teacher_backbone, frontend, device):
+    """The run's KnnProbe, or None with --knn_freq 0: then nothing of the evaluation is imported, built or read."""
+    if getattr(args, 'knn_freq', 0) <= 0:
+        return None
+    return KnnProbe(args, engine, teacher_backbone, frontend, device)
 
 
 def build_backbones(args):
@@ -341,6 +404,7 @@ def train_lafs(args, dataset=None):
     else:
         data_loader = SyntheticCrops(args.steps_per_epoch, args.batch_size_per_gpu, args.local_crops_number, device,
                                      args.seed + utils.get_rank())
+    knn_probe = build_knn_probe(args, engine, teacher_b, frontend, device)
     n_it = len(data_loader)
     # ---- schedules (reference :411-424) ----
     lr_schedule = utils.cosine_scheduler(args.lr * (args.batch_size_per_gpu * world) / 256., args.min_lr, args.epochs, n_it,
@@ -377,9 +441,15 @@ def train_lafs(args, dataset=None):
         utils.save_on_master(save_dict, ckpt)
         if args.saveckp_freq and epoch % args.saveckp_freq == 0:
             utils.save_on_master(save_dict, os.path.join(args.output_dir, f'checkpoint{epoch:04}.pth'))
+        knn_stats = {}
+        if knn_probe is not None and knn_probe.due(epoch):
+            if utils.is_main_process():
+                knn_stats = knn_probe()
+            if dist.is_initialized():
+                dist.barrier()
         if utils.is_main_process():
             with (Path(args.output_dir) / "log.txt").open("a") as f:
-                f.write(json.dumps({**{f'train_{k}': v for k, v in stats.items()}, 'epoch': epoch}) + "\n")
+                f.write(json.dumps({**{f'train_{k}': v for k, v in stats.items()}, **knn_stats, 'epoch': epoch}) + "\n")
     print('Training time {}'.format(str(datetime.timedelta(seconds=int(time.time() - start)))))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -626,3 +626,47 @@ def jpeg_decode(stream, images, tables, B, H, W, out=None, status=None, workspac
         raise _lib.LafsHipError("jpeg_decode: out must be contiguous [B,3,H,W], status [B], workspace lafs_jpeg_workspace_bytes(B,H,W)")
     call("lafs_jpeg_decode", _p(stream), stream.numel(), _p(images), _p(tables), tables.numel(), B, H, W, _p(out), _p(status), _p(workspace))
     return status
+
+
+def knn_search(bank, query, k, bank_pos0=0, exclude=None, merge=False, splits=0, top_score=None, top_idx=None):
+    """lafs_knn_search: bank f32 [N, D] and query f32 [Q, D] (row strides multiples of 4, 16-byte aligned) -> (top_score f32 [Q, k],
+    top_idx i32 [Q, k]): per query the first k bank positions bank_pos0 + row of the ranking order of include/lafs_hip.h.  exclude:
+    i32 [Q], the position left out per query (-1: none).  merge: top_score / top_idx hold an earlier result over other positions."""
+    _chk(bank, torch.float32, "bank"); _chk(query, torch.float32, "query"); _chk(exclude, torch.int32, "exclude")
+    _chk(top_score, torch.float32, "top_score"); _chk(top_idx, torch.int32, "top_idx")
+    if bank.dim() != 2 or query.dim() != 2 or bank.shape[1] != query.shape[1]:
+        raise _lib.LafsHipError("knn_search: bank [N, D] and query [Q, D] expected")
+    (N, D), Q, k = bank.shape, query.shape[0], int(k)
+    if exclude is not None and (exclude.dim() != 1 or exclude.numel() != Q or not exclude.is_contiguous()):
+        raise _lib.LafsHipError("knn_search: exclude must be a contiguous int32 [Q]")
+    if merge and (top_score is None or top_idx is None):
+        raise _lib.LafsHipError("knn_search: merge needs the earlier top_score and top_idx")
+    if top_score is None:
+        top_score = torch.empty(Q, k, device=bank.device, dtype=torch.float32)
+    if top_idx is None:
+        top_idx = torch.empty(Q, k, device=bank.device, dtype=torch.int32)
+    for t in (top_score, top_idx):
+        if tuple(t.shape) != (Q, k) or not t.is_contiguous():
+            raise _lib.LafsHipError("knn_search: top_score and top_idx must be contiguous [Q, k]")
+    need = int(_lib.lib().lafs_knn_workspace(Q, N, k, int(splits)))
+    ws = torch.empty(need, device=bank.device, dtype=torch.uint8) if need else None
+    call("lafs_knn_search", _p(bank), _ld(bank), N, int(bank_pos0), _p(query), _ld(query), Q, D, k, _p(exclude), 1 if merge else 0,
+         int(splits), _p(top_score), _p(top_idx), _p(ws), need)
+    return top_score, top_idx
+
+
+def knn_vote(top_score, top_idx, bank_label, ks, temperature=0.07):
+    """lafs_knn_vote: a list of knn_search + bank_label i32 [n_label] (by position) -> (pred i32, vote f32) [len(ks), Q, 5]: the five
+    best classes of the exp(score / temperature)-weighted vote over the first ks[i] entries; unused slots -1 and 0."""
+    _chk(top_score, torch.float32, "top_score"); _chk(top_idx, torch.int32, "top_idx"); _chk(bank_label, torch.int32, "bank_label")
+    if top_score.dim() != 2 or top_idx.shape != top_score.shape or not (top_score.is_contiguous() and top_idx.is_contiguous()):
+        raise _lib.LafsHipError("knn_vote: top_score and top_idx must be contiguous [Q, k]")
+    if bank_label.dim() != 1 or not bank_label.is_contiguous():
+        raise _lib.LafsHipError("knn_vote: bank_label must be a contiguous int32 vector")
+    ks = [int(v) for v in ks]
+    Q, k = top_score.shape
+    pred = torch.empty(len(ks), Q, 5, device=top_score.device, dtype=torch.int32)
+    vote = torch.empty(len(ks), Q, 5, device=top_score.device, dtype=torch.float32)
+    call("lafs_knn_vote", _p(top_score), _p(top_idx), Q, k, _p(bank_label), bank_label.numel(), (C.c_int32 * len(ks))(*ks), len(ks),
+         float(temperature), _p(pred), _p(vote))
+    return pred, vote

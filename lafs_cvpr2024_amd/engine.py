@@ -5,10 +5,13 @@
     per-tensor clip + AdamW + teacher EMA + bf16 shadow refresh (one launch) -> center EMA
 
 Everything between the brackets is captured once into hipGraphs (static buffers, hyper-parameters in a device
-buffer that is refreshed by one async H2D copy per step), so a step costs three graph launches instead of ~1500
-kernel launches from Python.  Collectives stay outside the graphs and run through torch.distributed ("nccl" = RCCL).
+buffer that is refreshed by one async H2D copy per step), so a step costs one graph launch on a single rank, and one per
+stretch between two collectives on several, instead of ~1500 kernel launches from Python.  The step is written once, as a
+generator that yields where a collective sits (_step); collectives stay outside the graphs and run through torch.distributed
+("nccl" = RCCL).
 """
 import math
+from functools import partial
 
 import numpy as np
 import os
@@ -20,7 +23,7 @@ from . import _lib, functional as Fn, ops
 from .arena import ParamArena
 from .distributed import BnStatExchange, FlatReducer
 from .ops import _p, call
-from .utils import PinnedRing
+from .utils import PinnedRing, capture_stretches
 from .vision_transformer import VisionTransformer, attach_arena, _is_matrix_for_dgrad
 
 
@@ -94,13 +97,18 @@ class LafsPretrainEngine:
             raise _lib.LafsHipError("student and teacher heads must both be built with, or both without, use_bn")
         if self.head_bn and self.world > 1:
             raise _lib.LafsHipError(HEAD_BN_MULTI_RANK)
+        # The step (_step) is written once and yields wherever a collective has to sit between its kernels: captured, every stretch
+        # between two yields is one hipGraph.  A single rank has no collective to place: it never yields, and the whole step is ONE
+        # graph (five replay boundaries less); LAFS_ONE_GRAPH=0 gives it the multi-rank launch structure.
+        self._one_graph = self.world == 1 and os.environ.get("LAFS_ONE_GRAPH", "1") != "0"
         # sync_bn (fViT pairs only): the head normalises every crop group with the statistics of the cls rows of ALL ranks.  The forward
-        # segment is cut twice around the exchange of the partial statistics, the head backward once around the all-reduce of its two
-        # sums (_seg_forward_a / _seg_forward_b / _seg_trunk_backward).  One rank has nobody to exchange with: it takes this segmented
-        # form only where it runs the multi-rank launch structure anyway (LAFS_ONE_GRAPH=0), else the plain kernels -- the same bits.
-        self.sync_bn = bool(sync_bn) and self.fvit and (self.world > 1 or os.environ.get("LAFS_ONE_GRAPH", "1") == "0")
+        # is cut once more, around the exchange of the partial statistics (_forward), the head backward around the all-reduce of its two
+        # sums (_seg_trunk_backward).  One rank has nobody to exchange with: it takes this form only where it runs the multi-rank
+        # launch structure anyway, else the plain kernels -- the same bits.
+        self.sync_bn = bool(sync_bn) and self.fvit and not self._one_graph
         self.n_fwd = 2 if self.sync_bn else 1                # graph segments of the forward
         self._bn_sums_live = False
+        self._drop_fixed = {}
         if self.fvit and (vit_s.ac_patch_size, vit_s.patch_size, vit_s.pad) != (vit_t.ac_patch_size, vit_t.patch_size, vit_t.pad):
             raise _lib.LafsHipError("student and teacher fViT must embed with the same window")
         if self.partfvit and (vit_s.with_land or vit_t.with_land):
@@ -220,8 +228,6 @@ class LafsPretrainEngine:
         self.head_start = min(o for n, o in self.sa.offsets.items() if n.startswith(self.head_prefix_s))
         self.depth = vit_s.depth
         self.pos_name = self.spec_s.pos
-        # the trunk backward is cut in two graph segments so that the upper blocks' gradients are already on the wire
-        # (RCCL) while the lower blocks are still being computed
         # the trunk backward is cut into `grad_slices` graph segments (blocks depth-1 .. 0 in equal runs) so that each run's
         # gradients are already on the wire (RCCL) while the next run is computed; only the last run's all-reduce is exposed
         ns = max(1, min(int(grad_slices), self.depth))
@@ -259,7 +265,8 @@ class LafsPretrainEngine:
         slack = 1 if self.world > 1 else 0
         serial = os.environ.get("LAFS_OPT_OVERLAP", "1") == "0"          # A/B knob: every piece in the final segment
         self.piece_runs_at = [n_segments - 1 if serial else min(p + self.n_fwd + slack, n_segments - 1) for p in range(len(self.pieces))]
-        self._piece_tokens = [[] for _ in self.pieces]
+        self._piece_tokens = [[] for _ in self.pieces]       # the reducer's tokens of the step in flight
+        self._center_tok = None
         self.opt_stream = None if os.environ.get("LAFS_SINGLE_STREAM") == "1" else torch.cuda.Stream(device=self.device)
         # large frozen tensors (Part-fViT's 30000 x 768 CosFace table: 92 MB of zeros per step on the wire otherwise) are cut out
         # of the all-reduced ranges; small frozen ones (weight_g) ride along rather than splitting a collective
@@ -309,7 +316,7 @@ class LafsPretrainEngine:
         self._drop_fixed = {0: dev(student, self.drop_s), 1: dev(teacher, self.drop_t)}
 
     def _drop_scales(self, keep, out, salt):
-        fixed = getattr(self, "_drop_fixed", {}).get(salt)
+        fixed = self._drop_fixed.get(salt)
         if fixed is not None:
             out.copy_(fixed)
             return out
@@ -325,39 +332,72 @@ class LafsPretrainEngine:
             return None
         return (vit.dropout_rate, vit.emb_dropout_rate, seed, self.hyper[_lib.HP_STEP:])
 
-    def _seg_forward(self):
-        sa, ta, B = self.sa, self.ta, self.B
-        call("lafs_zero_chunks", _p(sa.grad), _p(sa.chunk_seg), _p(sa.seg_flags), sa.n_chunks, _lib.SEG_OVERWRITTEN)
-        # teacher (two global views, no activations kept) runs on the side stream, concurrently with the student
+    def _fork_side(self):
+        """(main stream, side stream), the side stream waiting for the main one: the teacher runs there beside the student."""
         cur = torch.cuda.current_stream()
-        side = self.side_stream if self.side_stream is not None else cur
-        if os.environ.get("LAFS_TEACHER_SERIAL") == "1":       # lab knob: teacher forward in front of the student on the main stream
-            side = cur
+        # LAFS_TEACHER_SERIAL=1: lab knob, the teacher in front of the student on the main stream
+        serial = self.side_stream is None or os.environ.get("LAFS_TEACHER_SERIAL") == "1"
+        side = cur if serial else self.side_stream
         side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            pos_t = self._pos_tokens(ta, self.spec_t, self.pos_t)[:1]
-            vit_t = self.teacher.backbone
-            drop_t = self._drop_scales(self.keep_t, self.drop_t, 1) if vit_t.training else None   # rate 0 for the DINO ViT teacher
-            dd_t = self._dropout_cfg(vit_t, self.dropout_seed_t)
-            feat_t, _, _ = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False, dropout=dd_t,
-                                          bn_training=vit_t.training, cls_only_last=self.cls_only_last)
-            if self.fvit and vit_t.training:           # one forward of one group (device add: no host sync, capturable)
-                self.bn_t.num_batches_tracked.add_(1)
-            _, st_ht = Fn.head_forward(ta, self.head_prefix_t, feat_t, self.K, save=False, logits=self._logits_t, skip_logits=self.fused_head)
-        # student: all views in one packed pass
-        vit = self.student.backbone
-        drop = self._drop_scales(self.keep_s, self.drop_s, 0) if vit.training else None
-        imgs = [self.in_global_all] + ([self.in_local_all] if self.n_local else [])
-        dd_s = self._dropout_cfg(vit, self.dropout_seed_s)
-        feat_s, st_v, _ = Fn.vit_forward(sa, self.spec_s, self.geom_s, imgs, self._pos_tokens(sa, self.spec_s, self.pos_s), drop,
-                                         save=True, dropout=dd_s, wgrad_overwrite=True,
-                                         wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0,
-                                         bn_training=vit.training, cls_only_last=self.cls_only_last)
-        if self.fvit and vit.training:                 # the reference's forward runs the head once per crop group (:1556-1569)
+        return cur, side
+
+    def _teacher_head(self, feat_t, st_t):
+        if feat_t is None:                             # BatchNorm with the statistics of all ranks: the exchange buffer holds them now
+            feat_t = Fn.vit_forward_sync_bn(self.ta, self.spec_t, st_t, self.bn_x.all(1), self.bn_total_t)
+        if self.fvit and self.teacher.backbone.training:   # one forward of one group (device add: no host sync, capturable)
+            self.bn_t.num_batches_tracked.add_(1)
+        return Fn.head_forward(self.ta, self.head_prefix_t, feat_t, self.K, save=False, logits=self._logits_t, skip_logits=self.fused_head)[1]
+
+    def _student_head(self, feat_s, st_v):
+        self._bn_sums_live = feat_s is None            # (then the head backward too goes through sums of all ranks)
+        if feat_s is None:
+            feat_s = Fn.vit_forward_sync_bn(self.sa, self.spec_s, st_v, self.bn_x.all(0), self.bn_total_s)
+        if self.fvit and self.student.backbone.training:   # the reference's forward runs the head once per crop group (:1556-1569)
             self.bn_s.num_batches_tracked.add_(len(self.geom_s.groups))
-        _, st_h = Fn.head_forward(sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)
+        return Fn.head_forward(self.sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)[1]
+
+    def _forward(self):
+        """The forward, up to the student's head backward (a generator, see _step): both trunks, both heads, loss.  With sync_bn it
+        yields once, between the trunks and the BatchNorm of their cls rows, where the partial statistics of the ranks have to meet."""
+        sa, ta, vit, vit_t = self.sa, self.ta, self.student.backbone, self.teacher.backbone
+        call("lafs_zero_chunks", _p(sa.grad), _p(sa.chunk_seg), _p(sa.seg_flags), sa.n_chunks, _lib.SEG_OVERWRITTEN)
+        if self.sync_bn:
+            self.bn_x.clear()
+        # with sync_bn a network in training mode stops at the partial statistics of its cls rows (feat None), written into this rank's
+        # slot of the zeroed exchange buffer; one in eval mode needs no exchange and runs through
+        slot = lambda i, v: self.bn_x.slot(i) if self.sync_bn and v.training else None
+        cur, side = self._fork_side()
+        with torch.cuda.stream(side):                  # teacher: two global views, no activations kept
+            pos_t = self._pos_tokens(ta, self.spec_t, self.pos_t)[:1]
+            drop_t = self._drop_scales(self.keep_t, self.drop_t, 1) if vit_t.training else None   # rate 0 for the DINO ViT teacher
+            feat_t, st_t = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False,
+                                          dropout=self._dropout_cfg(vit_t, self.dropout_seed_t), bn_training=vit_t.training,
+                                          bn_partial=slot(1, vit_t), cls_only_last=self.cls_only_last)[:2]
+            if not self.sync_bn:                       # uncut: trunk -> head on the side stream, which never waits for the student
+                st_ht = self._teacher_head(feat_t, st_t)
+        drop = self._drop_scales(self.keep_s, self.drop_s, 0) if vit.training else None
+        imgs = [self.in_global_all] + ([self.in_local_all] if self.n_local else [])      # student: all views in one packed pass
+        feat_s, st_v = Fn.vit_forward(sa, self.spec_s, self.geom_s, imgs, self._pos_tokens(sa, self.spec_s, self.pos_s), drop, save=True,
+                                      dropout=self._dropout_cfg(vit, self.dropout_seed_s), wgrad_overwrite=True,
+                                      wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0,
+                                      bn_training=vit.training, bn_partial=slot(0, vit), cls_only_last=self.cls_only_last)[:2]
+        if self.sync_bn:
+            cur.wait_stream(side)
+            yield lambda: self.reducer.wait([self.bn_x.gather()])      # one collective on the step's critical path
+            cur, side = self._fork_side()
+            with torch.cuda.stream(side):
+                st_ht = self._teacher_head(feat_t, st_t)
+        st_h = self._student_head(feat_s, st_v)
         cur.wait_stream(side)
-        self._st = dict(vit=st_v, dfeat=self._head_loss_backward(st_h, st_ht))
+        dfeat = self._head_loss_backward(st_h, st_ht)
+        if self._bn_sums_live:                         # this rank's two sums of the BatchNorm backward
+            Fn.vit_backward_bn_sums(sa, self.spec_s, st_v, dfeat, self.bn_x.sums)
+        self._st = dict(vit=st_v, dfeat=dfeat)
+
+    def _seg_forward(self):
+        """The forward run eagerly (tests)."""
+        for act in self._forward():
+            act()
 
     def _head_loss_backward(self, st_h, st_ht):
         """Last layer of both heads, DINO loss forward + backward, center column sums, student head backward.  Returns dfeat."""
@@ -376,59 +416,6 @@ class LafsPretrainEngine:
         train_g = self.student.head.last_layer.weight_g.requires_grad
         self._head_states = (st_h, st_ht)
         return Fn.head_backward(sa, self.head_prefix_s, st_h, self.dlogits, train_g=train_g, overwrite_last=True)
-
-    def _seg_forward_a(self):
-        """sync_bn, first forward segment: both trunks to their cls rows and this rank's partial statistics of every crop group, written
-        into this rank's slots of the (zeroed) exchange buffer.  A network in eval mode needs no exchange and runs its head here."""
-        sa, ta = self.sa, self.ta
-        call("lafs_zero_chunks", _p(sa.grad), _p(sa.chunk_seg), _p(sa.seg_flags), sa.n_chunks, _lib.SEG_OVERWRITTEN)
-        self.bn_x.clear()
-        cur = torch.cuda.current_stream()
-        side = self.side_stream if self.side_stream is not None else cur
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            pos_t = self._pos_tokens(ta, self.spec_t, self.pos_t)[:1]
-            vit_t = self.teacher.backbone
-            drop_t = self._drop_scales(self.keep_t, self.drop_t, 1) if vit_t.training else None
-            feat_t, st_t, _ = Fn.vit_forward(ta, self.spec_t, self.geom_t, [self.in_global_all], pos_t, drop_t, save=False,
-                                             dropout=self._dropout_cfg(vit_t, self.dropout_seed_t), bn_training=vit_t.training,
-                                             bn_partial=self.bn_x.slot(1) if vit_t.training else None, cls_only_last=self.cls_only_last)
-        vit = self.student.backbone
-        drop = self._drop_scales(self.keep_s, self.drop_s, 0) if vit.training else None
-        imgs = [self.in_global_all] + ([self.in_local_all] if self.n_local else [])
-        feat_s, st_v, _ = Fn.vit_forward(sa, self.spec_s, self.geom_s, imgs, self._pos_tokens(sa, self.spec_s, self.pos_s), drop,
-                                         save=True, dropout=self._dropout_cfg(vit, self.dropout_seed_s), wgrad_overwrite=True,
-                                         wgrad_workgroups=int(os.environ.get("LAFS_WGRAD_WG", 200)) if self.side_stream is not None else 0,
-                                         bn_training=vit.training, bn_partial=self.bn_x.slot(0) if vit.training else None,
-                                         cls_only_last=self.cls_only_last)
-        cur.wait_stream(side)
-        self._st = dict(vit=st_v, vit_t=st_t, feat_s=feat_s, feat_t=feat_t)
-
-    def _seg_forward_b(self):
-        """sync_bn, second forward segment (the exchange buffer now holds the partials of all ranks): BatchNorm of both networks with
-        the combined statistics (running buffers and num_batches_tracked as in the one-rank forward), heads, loss, head backward and
-        this rank's two sums of the BatchNorm backward."""
-        sa, ta, st = self.sa, self.ta, self._st
-        cur = torch.cuda.current_stream()
-        side = self.side_stream if self.side_stream is not None else cur
-        side.wait_stream(cur)
-        with torch.cuda.stream(side):
-            feat_t = st["feat_t"]
-            if feat_t is None:
-                feat_t = Fn.vit_forward_sync_bn(ta, self.spec_t, st["vit_t"], self.bn_x.all(1), self.bn_total_t)
-                self.bn_t.num_batches_tracked.add_(1)
-            _, st_ht = Fn.head_forward(ta, self.head_prefix_t, feat_t, self.K, save=False, logits=self._logits_t, skip_logits=self.fused_head)
-        feat_s = st["feat_s"]
-        self._bn_sums_live = feat_s is None
-        if feat_s is None:
-            feat_s = Fn.vit_forward_sync_bn(sa, self.spec_s, st["vit"], self.bn_x.all(0), self.bn_total_s)
-            self.bn_s.num_batches_tracked.add_(len(self.geom_s.groups))
-        _, st_h = Fn.head_forward(sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)
-        cur.wait_stream(side)
-        dfeat = self._head_loss_backward(st_h, st_ht)
-        if self._bn_sums_live:
-            Fn.vit_backward_bn_sums(sa, self.spec_s, st["vit"], dfeat, self.bn_x.sums)
-        self._st = dict(vit=st["vit"], dfeat=dfeat)
 
     def _seg_trunk_backward(self, k):
         """Run k of the trunk backward: blocks cuts[k]-1 .. cuts[k+1]; run 0 starts with the final norm, the last run ends with
@@ -485,39 +472,55 @@ class LafsPretrainEngine:
             self.sa.refresh_transposed()
 
     # ------------------------------------------------------------------ step
-    def _segments(self):
-        forward = [self._seg_forward_a, self._seg_forward_b] if self.sync_bn else [self._seg_forward]
-        bodies = forward + [(lambda k=k: self._seg_trunk_backward(k)) for k in range(len(self.cuts) - 1)] + [self._seg_update]
-        return [(lambda k=k, b=b: self._with_pieces(k, b)) for k, b in enumerate(bodies)]
+    def _step(self):
+        """The device side of the step, once, in execution order.  A generator: on an engine with collectives to place (not _one_graph)
+        it yields wherever the host has work between two kernels, and what it yields is that work, a callable -- all-reduces to launch,
+        then the stream-side waits for what the next stretch reads.  _capture makes one hipGraph of every stretch between two yields
+        (n_segments of them); without graphs step() drives the generator itself."""
+        cut = not self._one_graph
+        yield from self._forward()
+        if cut:
+            yield self._after_forward
+        for k in range(len(self.cuts) - 1):
+            self._with_pieces(self.n_fwd + k, lambda: self._seg_trunk_backward(k))
+            if cut:
+                yield partial(self._after_backward_run, k)
+        self._with_pieces(self.n_segments - 1, self._seg_update)
+
+    def _after_forward(self):
+        # the BatchNorm backward's sums go out FIRST, the trunk backward waits for them alone; head gradients + center sums follow and
+        # are on the wire (RCCL) while the trunk backward runs (arena order: [embed | blocks 0..depth-1 | norm | head])
+        bn_tok = self.bn_x.reduce_sums() if self._bn_sums_live else None
+        self._piece_tokens[0] = self._reduce_range(*self.pieces[0])
+        self._center_tok = self.reducer.launch(self.colsum)
+        self.reducer.wait([bn_tok])
+        self._await(self.n_fwd)
+
+    def _after_backward_run(self, k):
+        if 1 + k < len(self.pieces):                     # this run's gradients go out as soon as its stretch has been enqueued
+            self._piece_tokens[1 + k] = self._reduce_range(*self.pieces[1 + k])
+        self._await(self.n_fwd + k + 1)
+
+    def _await(self, k):
+        """In front of stretch k the stream waits for what it reads: the update stretch for the center sums, an update piece for its
+        reduced gradients."""
+        if k == self.n_segments - 1:
+            self.reducer.wait([self._center_tok])
+        for p, at in enumerate(self.piece_runs_at):
+            if at == k:
+                self.reducer.wait(self._piece_tokens[p])
 
     def _capture(self):
-        segs = self._segments()
         s = torch.cuda.Stream(device=self.device)
         s.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(s):                       # warm-up outside capture (lazy inits, caches)
-            for f in segs:
-                f()
+        with torch.cuda.stream(s):                       # warm-up outside capture (lazy inits, caches): the whole step, no host work
+            for _ in self._step():
+                pass
         torch.cuda.current_stream().wait_stream(s)
         torch.cuda.synchronize()
-        graphs, pool = [], None
-        # a single rank has no collective to place between the segments: the whole step is ONE graph (five replay boundaries less)
-        self._one_graph = (self.world == 1) and os.environ.get("LAFS_ONE_GRAPH", "1") != "0"
-        if self._one_graph:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                for f in segs:
-                    f()
-            self._graphs = [g]
-            return
-        # world > 1: the process group's watchdog thread polls its events while this thread captures -- thread-local capture mode
-        # keeps another thread's (legal) runtime calls from invalidating the capture
-        for f in segs:
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g, pool=pool, capture_error_mode="thread_local"):
-                f()
-            pool = g.pool()
-            graphs.append(g)
-        self._graphs = graphs
+        # (collectives between the graphs mean a process group, whose watchdog thread is alive during the capture)
+        self._stretches, _ = capture_stretches(self._step(), thread_local=not self._one_graph)
+        self._graphs = [g for g, _ in self._stretches]
 
     def set_inputs(self, crops):
         """crops: list of 2 global + n_local local crops (any device), copied into the static NCHW input buffers.  Each is an
@@ -549,39 +552,14 @@ class LafsPretrainEngine:
             self._capture()
             self._restore(saved)
             self.hyper_ring.upload(self.hyper, fill_hyper)
-        if self.use_graph and getattr(self, "_one_graph", False):
-            self._graphs[0].replay()
-            self.step_count += 1
-            return self.loss
-        segs = self._segments()
-        replay = (lambda i: self._graphs[i].replay()) if self.use_graph else (lambda i: segs[i]())
-
-        def run(i):                              # a segment's update pieces need their gradients reduced: wait (stream-side) first
-            for p, at in enumerate(self.piece_runs_at):
-                if at == i:
-                    self.reducer.wait(self._piece_tokens[p])
-            replay(i)
-        run(0)
-        nf = self.n_fwd
-        bn_tok = None
-        if self.sync_bn:
-            # the partial statistics of both networks meet (one collective on the step's critical path), the second forward segment
-            # runs, and the BatchNorm backward's sums go out FIRST: the trunk backward waits for them alone
-            self.reducer.wait([self.bn_x.gather()])
-            run(1)
-            bn_tok = self.bn_x.reduce_sums()
-        # head gradients + center sums go out over RCCL while the trunk backward runs; each run of blocks follows as soon as
-        # its graph segment has been enqueued (arena order: [embed | blocks 0..depth-1 | norm | head])
-        self._piece_tokens[0] = self._reduce_range(*self.pieces[0])
-        center_tok = self.reducer.launch(self.colsum)
-        for k in range(len(self.cuts) - 1):
-            if k == 0:
-                self.reducer.wait([bn_tok])
-            run(nf + k)
-            if 1 + k < len(self.pieces):
-                self._piece_tokens[1 + k] = self._reduce_range(*self.pieces[1 + k])
-        self.reducer.wait([center_tok])
-        run(len(segs) - 1)
+        if self.use_graph:                       # the host's work (collectives) sits between the graphs
+            for g, act in self._stretches:
+                g.replay()
+                if act is not None:
+                    act()
+        else:
+            for act in self._step():
+                act()
         self.reducer.wait_all()
         self.step_count += 1
         return self.loss

@@ -39,7 +39,7 @@ from . import _lib, functional as Fn, ops
 from .face_pre_pro.ViT_face import ViT_face_landmark_patch8, ViTs_face_overlap
 from .distributed import FlatReducer
 from .ops import _p, call
-from .utils import PinnedRing
+from .utils import PinnedRing, capture_stretches
 from .vision_transformer import attach_arena
 
 f32, bf16 = torch.float32, torch.bfloat16
@@ -455,21 +455,8 @@ class FinetuneEngine:
         if self.cnn is not None:
             self.cnn.mark_stale()                        # the operand refresh becomes part of the graph: every replay sees fresh weights
         # The body is a generator that yields the gradient range to all-reduce wherever a collective has to sit between kernels (only on
-        # the last micro-step of a data-parallel window): every stretch between two yields becomes one hipGraph.  With a process group
-        # alive its watchdog thread polls events while this thread captures -- thread-local capture mode keeps its (legal) runtime
-        # calls from invalidating the capture (as in LafsPretrainEngine._capture).
-        segs, gen, done = [], self._body_gen(first), False
-        mode = dict(capture_error_mode="thread_local") if self.world > 1 else {}
-        while not done:
-            g, out = torch.cuda.CUDAGraph(), None
-            with torch.cuda.graph(g, pool=self._pool, **mode):
-                try:
-                    out = next(gen)
-                except StopIteration:
-                    done = True
-            if self._pool is None:
-                self._pool = g.pool()
-            segs.append((g, out))
+        # the last micro-step of a data-parallel window): every stretch between two yields becomes one hipGraph.
+        segs, self._pool = capture_stretches(self._body_gen(first), self._pool, thread_local=self.world > 1)
         return segs
 
     # ------------------------------------------------------------------ the device side (capturable: lafs_* launches only)

@@ -311,3 +311,26 @@ class PinnedRing:
         ev.record()
         self.events[k] = ev
         return self.bufs[k]
+
+
+# --------------------------------------------------------------------------------------------- hipGraph capture
+def capture_stretches(gen, pool=None, thread_local=False):
+    """Captures a step that is written as a generator: every stretch of `gen` up to its next yield, or to its end, becomes one
+    hipGraph on the shared memory `pool` (None: the first graph's).  A step yields wherever host work -- a collective -- has to sit
+    between kernels, so a step that never yields is ONE graph.  What was yielded is handed back beside the graph that ends there
+    (None behind the last one) and is the caller's to interpret.  Returns ([(graph, yielded)], pool).
+    thread_local: with a process group alive its watchdog thread polls events while this thread captures -- thread-local capture
+    mode keeps another thread's (legal) runtime calls from invalidating the capture."""
+    mode = dict(capture_error_mode="thread_local") if thread_local else {}
+    stretches, done = [], False
+    while not done:
+        g, out = torch.cuda.CUDAGraph(), None
+        with torch.cuda.graph(g, pool=pool, **mode):
+            try:
+                out = next(gen)
+            except StopIteration:
+                done = True
+        if pool is None:
+            pool = g.pool()
+        stretches.append((g, out))
+    return stretches, pool

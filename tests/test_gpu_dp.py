@@ -92,7 +92,7 @@ def _rccl_worker(rank, world, port, out):
     torch.cuda.set_device(0)
     dist.init_process_group("nccl", rank=0, world_size=1, device_id=torch.device("cuda", 0))
     eng = _build(4, True)
-    assert len(eng._segments()) > 1 and eng.reducer.active
+    assert eng.n_segments > 1 and eng.reducer.active
     full = [c.cuda() for c in _crops(4)]
     losses = [float(eng.step(full, lr=1e-3, wd=0.04, momentum=0.9, teacher_temp=0.05, epoch=1).item()) for _ in range(3)]
     assert not eng._one_graph and len(eng._graphs) > 1

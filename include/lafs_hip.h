@@ -574,6 +574,9 @@ enum { LAFS_HP_LR = 0, LAFS_HP_WD, LAFS_HP_BETA1, LAFS_HP_BETA2, LAFS_HP_EPS, LA
        LAFS_HP_STEP /* optimisation step count (as a float): seeds the per-step DropPath masks of a replayed graph */,
        LAFS_HP_MIX_LAM /* mixup lambda of this fine-tune micro-step (lam_dev of lafs_mixup_normalize / lafs_margin_softmax_ce_bf16) */,
        LAFS_HP_LAND_W /* weight of the landmark-supervision term of this fine-tune micro-step (`weight` of lafs_landmark_mse) */,
+       LAFS_HP_MOMENTUM = 13 /* momentum of the SGD / LARS buffer: 0.9, torch.optim.SGD(..., momentum=0.9) at lafs_train.py:402 and the
+                                default of utils.LARS (utils.py:557) */,
+       LAFS_HP_LARS_ETA = 14 /* LARS trust coefficient eta: 0.001, the default of utils.LARS (utils.py:557) */,
        LAFS_HP_COUNT = 16 };
 /* seg_sumsq(f32)[n_seg] = sum of (grad_scale*g)^2 per segment -- the per-tensor norms of utils.clip_gradients
  * (utils.py:132-141).  Two passes through chunk_sumsq(f32)[n_chunks] scratch, fixed summation order: no atomics, nothing
@@ -595,6 +598,32 @@ int lafs_clip_adamw_ema_range(float* param, const float* grad, float* exp_avg, f
                               void* param_bf16, void* teacher_bf16, const int32_t* chunk_seg, int64_t n_chunks, int64_t chunk_lo,
                               int64_t chunk_hi, const int32_t* seg_flags, int32_t* seg_step, int n_seg, int seg_lo, int seg_hi,
                               const float* seg_sumsq, const float* hyper, hipStream_t stream);
+/* The update rules behind --optimizer sgd / lars (lafs_train.py:401-404).  Both keep ONE state buffer, `mom` (torch's momentum_buffer,
+ * LARS's mu), and couple the decay into the gradient: with g^ the scaled and clipped gradient of lafs_clip_adamw_ema,
+ *   SGD  (torch.optim.SGD, momentum = hyper[LAFS_HP_MOMENTUM], dampening 0, no Nesterov; lafs_train.py:402)
+ *        d = g^ + wd_t p        wd_t: hyper[LAFS_HP_WD] / hyper[LAFS_HP_WD_LOW] / 0 by the tensor's LAFS_SEG_DECAY / LAFS_SEG_LOW_DECAY bits
+ *   LARS (utils.py:553-591)  LAFS_SEG_DECAY set (ndim != 1, utils.py:573-583):  d = q (g^ + wd_t p),
+ *        q = eta ||p|| / ||g^ + wd_t p|| where both norms are > 0, else 1;  LAFS_SEG_DECAY clear (ndim == 1):  d = g^
+ *   both (utils.py:585-591):  mom = momentum * mom + d;  p -= lr * mom
+ * A zero `mom` gives the first step's buf = d of torch, so neither rule reads seg_step -- which still counts the steps a tensor
+ * has taken (checkpoints, the DropPath seed). */
+enum { LAFS_UPDATE_SGD = 1, LAFS_UPDATE_LARS = 2 };
+/* lafs_grad_sumsq_range for a LARS step: seg_sumsq exactly as there (same order, same bits), and seg_trust(f32)[n_seg] = q of the
+ * tensors [seg_lo, seg_hi) (1 where LAFS_SEG_DECAY is clear), from ONE read of grad and param: per chunk sum g^2, sum p^2, sum g p
+ * into chunk_part(f32)[3 * n_chunks] (three planes of n_chunks), per tensor
+ *   ||g^ + wd p||^2 = gsc^2 sum g^2 + 2 gsc wd sum g p + wd^2 sum p^2,   gsc = grad_scale * min(1, clip coefficient)
+ * replacing torch.norm(p), torch.norm(dp) of utils.py:577-578.  No atomics, nothing to pre-zero, fixed summation order. */
+int lafs_grad_sumsq_trust_range(const float* param, const float* grad, const int32_t* chunk_seg, int64_t n_chunks, int n_seg,
+                                int64_t chunk_lo, int64_t chunk_hi, int seg_lo, int seg_hi, const int32_t* seg_flags, const float* hyper,
+                                float* chunk_part, float* seg_sumsq, float* seg_trust, hipStream_t stream);
+/* Fused per-tensor clip + SGD-with-momentum or LARS (kind: LAFS_UPDATE_*) + teacher EMA + bf16 shadow refresh on the tensors
+ * [seg_lo, seg_hi): optimizer.step() of lafs_train.py:598,606 for the optimizers of :402 / :404 with the clip, freeze, EMA and shadow
+ * handling of lafs_clip_adamw_ema_range.  seg_trust: what lafs_grad_sumsq_trust_range wrote (LARS; NULL for SGD).  teacher / shadow
+ * pointers may be NULL.  An unknown kind, LARS without seg_trust, or a range that leaves the arena is refused (LAFS_ESHAPE). */
+int lafs_clip_momentum_ema_range(int kind, float* param, const float* grad, float* mom, float* teacher, void* param_bf16,
+                                 void* teacher_bf16, const int32_t* chunk_seg, int64_t n_chunks, int64_t chunk_lo, int64_t chunk_hi,
+                                 const int32_t* seg_flags, int32_t* seg_step, int n_seg, int seg_lo, int seg_hi, const float* seg_sumsq,
+                                 const float* seg_trust, const float* hyper, hipStream_t stream);
 /* dst(bf16)[i] = src(f32)[i] */
 int lafs_cast_bf16(const float* src, void* dst, int64_t n, hipStream_t stream);
 /* dst(f32)[i] = src(bf16)[i]   (gradients that travelled over the wire as bf16: LAFS_GRAD_WIRE=bf16, distributed.py) */

@@ -94,7 +94,9 @@ PATCH_ORDER_CHW, PATCH_ORDER_HWC = 0, 1
 CHUNK = 1024
 SEG_DECAY, SEG_LAST_LAYER, SEG_TRAINABLE, SEG_LOW_DECAY, SEG_OVERWRITTEN = 1, 2, 4, 8, 16
 HP_LR, HP_WD, HP_BETA1, HP_BETA2, HP_EPS, HP_CLIP, HP_EMA_M, HP_FREEZE_LAST, HP_GRAD_SCALE, HP_WD_LOW, HP_STEP, HP_MIX_LAM, HP_LAND_W = range(13)
+HP_MOMENTUM, HP_LARS_ETA = 13, 14         # SGD / LARS momentum and LARS's eta: constants of the reference (lafs_train.py:402, utils.py:557)
 HP_COUNT = 16
+UPDATE_SGD, UPDATE_LARS = 1, 2            # enum LAFS_UPDATE_* (lafs_clip_momentum_ema_range)
 # parameter row of lafs_mix_normalize / lafs_margin_softmax_ce_mix_bf16 (enum LAFS_MIX_* of lafs_hip.h)
 MIX_LAM, MIX_CUT, MIX_YL, MIX_YH, MIX_XL, MIX_XH, MIX_WORDS = range(7)
 OPT_SIDE_STREAMS, OPT_ROW_CHAINS, OPT_KRES_MASK, OPT_KRES_MIN_ITEMS, OPT_NT_WIDE, OPT_NT_TALL, OPT_COMM_CUS, OPT_NT_BIG, OPT_MLP_FUSED = range(9)
@@ -146,6 +148,8 @@ _PROTOS = {
     "lafs_clip_adamw_ema": [vp, vp, vp, vp, vp, vp, vp, vp, i64, vp, vp, i32, vp, vp],
     "lafs_grad_sumsq_range": [vp, vp, i64, i32, i64, i64, i32, i32, vp, vp, vp],
     "lafs_clip_adamw_ema_range": [vp, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, vp, vp],
+    "lafs_grad_sumsq_trust_range": [vp, vp, vp, i64, i32, i64, i64, i32, i32, vp, vp, vp, vp, vp],
+    "lafs_clip_momentum_ema_range": [i32, vp, vp, vp, vp, vp, vp, vp, i64, i64, i64, vp, vp, i32, i32, i32, vp, vp, vp],
     "lafs_cast_bf16": [vp, vp, i64],
     "lafs_cast_f32": [vp, vp, i64],
     "lafs_droppath_scales": [vp, i32, i32, u32, vp, vp],

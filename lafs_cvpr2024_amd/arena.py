@@ -19,9 +19,10 @@ def _round_up(n, m):
 
 
 class ParamArena:
-    """Owns the flat buffers of one nn.Module.  `with_grad` adds grad + AdamW moments."""
+    """Owns the flat buffers of one nn.Module.  `with_grad` adds grad + AdamW moments; `second_moment=False` leaves exp_avg_sq out
+    (SGD and LARS keep one state buffer, exp_avg, as their momentum: 4 bytes per parameter less)."""
 
-    def __init__(self, module: torch.nn.Module, device, with_grad=True, transposed=None):
+    def __init__(self, module: torch.nn.Module, device, with_grad=True, transposed=None, second_moment=True):
         self.module = module
         self.device = torch.device(device)
         self.names, self.params, self.offsets, self.numels = [], [], {}, {}
@@ -40,7 +41,7 @@ class ParamArena:
         self.shadow = torch.zeros(off, device=dev, dtype=torch.bfloat16)
         self.grad = torch.zeros(off, device=dev, dtype=torch.float32) if with_grad else None
         self.exp_avg = torch.zeros(off, device=dev, dtype=torch.float32) if with_grad else None
-        self.exp_avg_sq = torch.zeros(off, device=dev, dtype=torch.float32) if with_grad else None
+        self.exp_avg_sq = torch.zeros(off, device=dev, dtype=torch.float32) if with_grad and second_moment else None
         chunk_seg, flags = [], []
         for i, (name, p) in enumerate(zip(self.names, self.params)):
             chunk_seg += [i] * (_round_up(p.numel(), CHUNK) // CHUNK)

@@ -52,6 +52,13 @@ HEAD_BN_MULTI_RANK = ("a DINO head with BatchNorm (use_bn_in_head) on more than 
 
 f32, bf16 = torch.float32, torch.bfloat16
 
+# --optimizer (reference lafs_train.py:92-93, 399-404).  momentum and eta are constants of the reference, not flags:
+# torch.optim.SGD(params_groups, lr=0, momentum=0.9) and the defaults of utils.LARS (utils.py:557)
+OPTIMIZERS = ('adamw', 'sgd', 'lars')
+SGD_MOMENTUM, LARS_ETA = 0.9, 0.001
+# the per-tensor state key each optimizer's state_dict holds, by which a state_dict's kind is told
+_STATE_KEY = {'adamw': 'exp_avg', 'sgd': 'momentum_buffer', 'lars': 'mu'}
+
 
 def _interp_matrix(grid_src, grid_dst, device):
     """Dense matrix of torch's bicubic F.interpolate from a g x g grid to an r x r grid with the reference's
@@ -67,7 +74,8 @@ def _interp_matrix(grid_src, grid_dst, device):
 
 class LafsPretrainEngine:
     def __init__(self, student, teacher, dino_loss, batch_size, n_local=8, global_size=112, local_size=48,
-                 clip_grad=3.0, freeze_last_layer=1, use_graph=True, device=None, grad_slices=4, sync_bn=False):
+                 clip_grad=3.0, freeze_last_layer=1, use_graph=True, device=None, grad_slices=4, sync_bn=False,
+                 optimizer='adamw'):
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
         self.student, self.teacher, self.dino_loss = student, teacher, dino_loss
         self.B, self.n_local, self.ncrops = batch_size, n_local, 2 + n_local
@@ -113,7 +121,24 @@ class LafsPretrainEngine:
             raise _lib.LafsHipError("student and teacher fViT must embed with the same window")
         if self.partfvit and (vit_s.with_land or vit_t.with_land):
             raise _lib.LafsHipError("LAFS pre-training uses with_land=False backbones (the landmark CNN is the frozen front-end)")
-        self.sa = attach_arena(student, self.device)
+        # --optimizer of the reference (lafs_train.py:399-404).  The choice is fixed here: it picks the kernel pair of _update_piece once
+        # and which state buffers exist (sgd / lars keep exp_avg alone, as their momentum); nothing reads it during a step.
+        if optimizer not in OPTIMIZERS:
+            raise _lib.LafsHipError(f"optimizer {optimizer!r}: one of {', '.join(OPTIMIZERS)}")
+        self.optimizer = optimizer
+        self.sa = attach_arena(student, self.device, second_moment=optimizer == 'adamw')
+        if optimizer == 'adamw' and self.sa.exp_avg_sq is None:
+            raise _lib.LafsHipError("the student's arena was built without a second-moment buffer: it cannot run AdamW")
+        if optimizer == 'lars':
+            # utils.LARS decays and adapts the tensors with ndim != 1 (utils.py:573-576); the kernels key both on LAFS_SEG_DECAY,
+            # which utils.get_params_groups' rule sets for exactly those tensors
+            flags = self.sa.seg_flags.cpu().tolist()
+            for name, p, f in zip(self.sa.names, self.sa.params, flags):
+                if p.requires_grad and bool(f & _lib.SEG_DECAY) != (p.dim() != 1):
+                    raise _lib.LafsHipError(f"optimizer 'lars': {name} has {p.dim()} dimensions but its weight-decay flag is "
+                                            f"{'set' if f & _lib.SEG_DECAY else 'clear'}; LARS decays and adapts exactly the tensors with ndim != 1")
+            self.seg_trust = torch.ones(self.sa.n_seg, device=self.device, dtype=f32)
+            self.chunk_part = self.sa.scratch("lars_chunk_part", 3 * self.sa.n_chunks)
         # the library's side streams / events / kernel options of THIS engine (created now: nothing is created inside a capture;
         # two engines share no stream or event).  The environment's A/B switches are read by _lib.Ctx, not by the library.
         self.ctx = _lib.Ctx(self.device)
@@ -274,6 +299,7 @@ class LafsPretrainEngine:
                              for n, p in zip(self.sa.names, self.sa.params) if not p.requires_grad and p.numel() >= (1 << 20)]
         # teacher forward / weight-gradient GEMMs run on a second stream; LAFS_SINGLE_STREAM=1 serialises everything (profiling)
         self.side_stream = None if os.environ.get("LAFS_SINGLE_STREAM") == "1" else torch.cuda.Stream(device=self.device)
+        self._update_range = {'adamw': self._update_adamw, 'sgd': self._update_sgd, 'lars': self._update_lars}[optimizer]
         self.use_graph = use_graph
         self._graphs = None
         self._st = {}
@@ -437,15 +463,35 @@ class LafsPretrainEngine:
                     call("lafs_pos_interp_bwd", _p(dp), _p(M), _p(gpe), M.shape[0], M.shape[1], self.spec_s.trunk.dim)
 
     def _update_piece(self, p):
-        """Per-tensor gradient norms, clip + AdamW + teacher EMA + bf16 shadows for the tensors of update piece p."""
-        sa, ta = self.sa, self.ta
+        """Per-tensor gradient norms, clip + update rule + teacher EMA + bf16 shadows for the tensors of update piece p."""
         (lo, hi), (s_lo, s_hi) = self.pieces[p], self.piece_segs[p]
-        c_lo, c_hi = lo // _lib.CHUNK, hi // _lib.CHUNK
+        self._update_range(lo // _lib.CHUNK, hi // _lib.CHUNK, s_lo, s_hi)
+
+    def _update_adamw(self, c_lo, c_hi, s_lo, s_hi):
+        sa, ta = self.sa, self.ta
         call("lafs_grad_sumsq_range", _p(sa.grad), _p(sa.chunk_seg), sa.n_chunks, sa.n_seg, c_lo, c_hi, s_lo, s_hi, _p(self.hyper),
              _p(sa.chunk_sumsq), _p(sa.seg_sumsq))
         call("lafs_clip_adamw_ema_range", _p(sa.master), _p(sa.grad), _p(sa.exp_avg), _p(sa.exp_avg_sq), _p(ta.master),
              _p(sa.shadow), _p(ta.shadow), _p(sa.chunk_seg), sa.n_chunks, c_lo, c_hi, _p(sa.seg_flags), _p(sa.seg_step), sa.n_seg,
              s_lo, s_hi, _p(sa.seg_sumsq), _p(self.hyper))
+
+    def _update_sgd(self, c_lo, c_hi, s_lo, s_hi):
+        sa = self.sa
+        call("lafs_grad_sumsq_range", _p(sa.grad), _p(sa.chunk_seg), sa.n_chunks, sa.n_seg, c_lo, c_hi, s_lo, s_hi, _p(self.hyper),
+             _p(sa.chunk_sumsq), _p(sa.seg_sumsq))
+        self._momentum_step(_lib.UPDATE_SGD, None, c_lo, c_hi, s_lo, s_hi)
+
+    def _update_lars(self, c_lo, c_hi, s_lo, s_hi):
+        sa = self.sa
+        call("lafs_grad_sumsq_trust_range", _p(sa.master), _p(sa.grad), _p(sa.chunk_seg), sa.n_chunks, sa.n_seg, c_lo, c_hi, s_lo, s_hi,
+             _p(sa.seg_flags), _p(self.hyper), _p(self.chunk_part), _p(sa.seg_sumsq), _p(self.seg_trust))
+        self._momentum_step(_lib.UPDATE_LARS, self.seg_trust, c_lo, c_hi, s_lo, s_hi)
+
+    def _momentum_step(self, kind, trust, c_lo, c_hi, s_lo, s_hi):
+        sa, ta = self.sa, self.ta
+        call("lafs_clip_momentum_ema_range", kind, _p(sa.master), _p(sa.grad), _p(sa.exp_avg), _p(ta.master), _p(sa.shadow), _p(ta.shadow),
+             _p(sa.chunk_seg), sa.n_chunks, c_lo, c_hi, _p(sa.seg_flags), _p(sa.seg_step), sa.n_seg, s_lo, s_hi, _p(sa.seg_sumsq),
+             _p(trust), _p(self.hyper))
 
     def _seg_update(self):
         call("lafs_center_ema", _p(self.dino_loss.center), _p(self.colsum), self.K, 1.0 / (2 * self.B * self.world),
@@ -541,6 +587,7 @@ class LafsPretrainEngine:
             h[_lib.HP_FREEZE_LAST] = 1.0 if epoch < self.freeze_last_layer else 0.0
             h[_lib.HP_GRAD_SCALE] = 1.0 / self.world        # DDP mean of the summed gradients
             h[_lib.HP_STEP] = float(self.step_count % (1 << 24))
+            h[_lib.HP_MOMENTUM], h[_lib.HP_LARS_ETA] = SGD_MOMENTUM, LARS_ETA
 
         def fill_temps(t):
             t[0], t[1] = float(self.dino_loss.student_temp), teacher_temp
@@ -588,7 +635,8 @@ class LafsPretrainEngine:
         bn = [b for m in ((self.bn_s, self.bn_t) if self.fvit else ()) for b in (m.running_mean, m.running_var, m.num_batches_tracked)]
         if self.head_bn:                             # the four BatchNorm1d of the two heads (mlp.1 / mlp.4)
             bn += [b for net in (self.student, self.teacher) for b in net.head.buffers()]
-        return [sa.master, sa.exp_avg, sa.exp_avg_sq, sa.seg_step, ta.master, self.dino_loss.center] + bn
+        moments = [sa.exp_avg] + ([sa.exp_avg_sq] if sa.exp_avg_sq is not None else [])        # (sgd / lars: one state buffer)
+        return [sa.master] + moments + [sa.seg_step, ta.master, self.dino_loss.center] + bn
 
     def _snapshot(self):
         return [t.clone() for t in self._state_tensors()], torch.cuda.get_rng_state(self.device)
@@ -616,11 +664,24 @@ class LafsPretrainEngine:
                 (noreg if (name.endswith(".bias") or p.dim() == 1) else reg).append(name)
         return reg, noreg
 
+    def _kind_of_state_dict(self, sd):
+        """'adamw' | 'sgd' | 'lars' | None (cannot tell: no state entries and unknown group keys)."""
+        for st in sd["state"].values():
+            for kind, key in _STATE_KEY.items():
+                if key in st:
+                    return kind
+        keys = set().union(*[set(g) for g in sd["param_groups"]]) if sd["param_groups"] else set()
+        return 'adamw' if 'betas' in keys else 'lars' if 'eta' in keys else 'sgd' if 'nesterov' in keys else None
+
     def optimizer_state_dict(self):
-        """The state_dict torch.optim.AdamW(get_params_groups(student)) would have at this point -- the format the reference
-        stores under checkpoint['optimizer'] and restores with optimizer.load_state_dict (lafs_train.py:428-463,
-        utils.py:152-184): per-parameter {step, exp_avg, exp_avg_sq} (only for tensors that have been stepped, like torch:
-        the last layer has none while it is frozen) and the two param_groups."""
+        """The state_dict the reference's optimizer would have at this point -- the format the reference stores under
+        checkpoint['optimizer'] and restores with optimizer.load_state_dict (lafs_train.py:428-463, utils.py:152-184).
+          adamw  torch.optim.AdamW(get_params_groups(student)): per-parameter {step, exp_avg, exp_avg_sq}
+          sgd    torch.optim.SGD(..., lr=0, momentum=0.9):       per-parameter {momentum_buffer, step}
+          lars   utils.LARS(...):                                per-parameter {mu, step}
+        An entry exists only for a tensor that has been stepped, like torch: the last layer has none while it is frozen.  `step`
+        (the tensor's seg_step) is no key of torch's SGD or the reference's LARS, which both ignore it; with it a resume here
+        continues the DropPath sequence exactly."""
         sa = self.sa
         reg, noreg = self._adamw_order()
         steps = sa.seg_step.cpu().tolist()
@@ -630,18 +691,35 @@ class LafsPretrainEngine:
             t = steps[sa.names.index(name)]
             if t > 0:
                 shape = sa.params[sa.names.index(name)].shape
-                state[idx] = {"step": torch.tensor(float(t)), "exp_avg": sa.view(sa.exp_avg, name, shape).detach().cpu().clone(),
-                              "exp_avg_sq": sa.view(sa.exp_avg_sq, name, shape).detach().cpu().clone()}
-        common = {"lr": h[_lib.HP_LR], "betas": (h[_lib.HP_BETA1] or 0.9, h[_lib.HP_BETA2] or 0.999), "eps": h[_lib.HP_EPS] or 1e-8,
-                  "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None}
+                if self.optimizer == 'adamw':
+                    state[idx] = {"step": torch.tensor(float(t)), "exp_avg": sa.view(sa.exp_avg, name, shape).detach().cpu().clone(),
+                                  "exp_avg_sq": sa.view(sa.exp_avg_sq, name, shape).detach().cpu().clone()}
+                else:
+                    state[idx] = {_STATE_KEY[self.optimizer]: sa.view(sa.exp_avg, name, shape).detach().cpu().clone(),
+                                  "step": torch.tensor(float(t))}
+        if self.optimizer == 'adamw':
+            common = {"lr": h[_lib.HP_LR], "betas": (h[_lib.HP_BETA1] or 0.9, h[_lib.HP_BETA2] or 0.999), "eps": h[_lib.HP_EPS] or 1e-8,
+                      "amsgrad": False, "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None}
+        elif self.optimizer == 'sgd':
+            # lr, momentum, dampening, weight_decay, nesterov + whatever keys the installed torch adds (maximize, foreach, ...)
+            common = dict(torch.optim.SGD([torch.nn.Parameter(torch.zeros(1))], lr=0, momentum=SGD_MOMENTUM).defaults, lr=h[_lib.HP_LR])
+        else:
+            common = {"lr": h[_lib.HP_LR], "weight_decay": 0.0, "momentum": SGD_MOMENTUM, "eta": LARS_ETA, "weight_decay_filter": None,
+                      "lars_adaptation_filter": None}
         groups = [dict(common, weight_decay=h[_lib.HP_WD], params=list(range(len(reg)))),
                   dict(common, weight_decay=0.0, params=list(range(len(reg), len(reg) + len(noreg))))]
         return {"state": state, "param_groups": groups}
 
     def load_optimizer_state_dict(self, sd):
-        """Inverse of optimizer_state_dict; also accepts a checkpoint written by the reference itself (same format)."""
+        """Inverse of optimizer_state_dict; also accepts a checkpoint written by the reference itself (same format).  The reference's
+        SGD / LARS entries carry no step count: their tensors get seg_step = 1 (stepped at least once) and the caller sets
+        step_count from the epoch (lafs_train.py here)."""
         if "state" not in sd or "param_groups" not in sd:
             raise _lib.LafsHipError("checkpoint['optimizer'] is not a torch.optim.AdamW state_dict (keys: %s)" % sorted(sd))
+        kind = self._kind_of_state_dict(sd)
+        if kind is not None and kind != self.optimizer:
+            raise _lib.LafsHipError(f"checkpoint['optimizer'] is the state of optimizer '{kind}', this engine was built with "
+                                    f"optimizer '{self.optimizer}'")
         sa = self.sa
         reg, noreg = self._adamw_order()
         names = reg + noreg
@@ -649,17 +727,22 @@ class LafsPretrainEngine:
         if sizes != [len(reg), len(noreg)]:
             raise _lib.LafsHipError(f"optimizer param_groups of sizes {sizes} do not fit this model ({len(reg)} regularised + "
                                     f"{len(noreg)} other tensors)")
-        sa.exp_avg.zero_(); sa.exp_avg_sq.zero_(); sa.seg_step.zero_()
+        sa.exp_avg.zero_(); sa.seg_step.zero_()
+        if sa.exp_avg_sq is not None:
+            sa.exp_avg_sq.zero_()
         steps = sa.seg_step.cpu()
         flat = [i for g in sd["param_groups"] for i in g["params"]]
+        key = _STATE_KEY[self.optimizer]
         for pos, idx in enumerate(flat):
             st = sd["state"].get(idx)
-            if st is None:
+            if st is None or st.get(key) is None:            # (torch's SGD stores momentum_buffer = None for a tensor it never stepped)
                 continue
             name = names[pos]
             shape = sa.params[sa.names.index(name)].shape
-            sa.view(sa.exp_avg, name, shape).copy_(st["exp_avg"]); sa.view(sa.exp_avg_sq, name, shape).copy_(st["exp_avg_sq"])
-            steps[sa.names.index(name)] = int(float(st["step"]))
+            sa.view(sa.exp_avg, name, shape).copy_(st[key])
+            if self.optimizer == 'adamw':
+                sa.view(sa.exp_avg_sq, name, shape).copy_(st["exp_avg_sq"])
+            steps[sa.names.index(name)] = int(float(st["step"])) if "step" in st else 1
         sa.seg_step.copy_(steps)
         # the per-step DropPath masks are seeded with the step count: continue the sequence of the interrupted run
         self.step_count = int(steps.max()) if steps.numel() else 0

@@ -18,7 +18,8 @@ Differences from the reference, all forced by its own breakage or by scope (SURV
   * --arch fvit pre-trains ViTs_face_overlap (the overlapping-patch fViT with its BatchNorm1d head; --fvit_dims, --fvit_window,
     --fvit_dropout); on more than one rank it needs --sync_bn true, the counterpart of the reference's SyncBatchNorm conversion
     (:362-364): the BatchNorm1d head then normalises every crop group with the statistics of all ranks' cls rows;
-  * the optimizer is the engine's fused per-tensor-clip + AdamW (the reference's default and only used one).
+  * --optimizer picks the update rule of the engine's fused per-tensor-clip + update + EMA kernel: adamw (the reference's default),
+    sgd (torch.optim.SGD(lr=0, momentum=0.9), :402) or lars (utils.LARS, :404); momentum and LARS's eta are the reference's constants.
 """
 import argparse
 import datetime
@@ -68,7 +69,8 @@ def get_args_parser():
     p.add_argument("--lr", default=0.0005, type=float)
     p.add_argument("--warmup_epochs", default=10, type=int)
     p.add_argument('--min_lr', type=float, default=1e-6)
-    p.add_argument('--optimizer', default='adamw', type=str, choices=['adamw'])
+    p.add_argument('--optimizer', default='adamw', type=str, choices=['adamw', 'sgd', 'lars'],
+                   help="Type of optimizer (reference :92-93): adamw for ViTs, sgd, or lars for convnets and large batches.")
     p.add_argument('--drop_path_rate', type=float, default=0.1)
     p.add_argument('--mynet_dims', default='768,12,11,2048', type=str, help="dim,depth,heads,mlp_dim of --arch mynet (reference :300-335)")
     p.add_argument('--mynet_dropout', default=0.1, type=float, help="dropout = emb_dropout of --arch mynet (reference: 0.1)")
@@ -382,7 +384,7 @@ def train_lafs(args, dataset=None):
                          args.warmup_teacher_temp_epochs, args.epochs)
     engine = LafsPretrainEngine(student, teacher, dino_loss, args.batch_size_per_gpu, n_local=args.local_crops_number,
                                 clip_grad=args.clip_grad, freeze_last_layer=args.freeze_last_layer, use_graph=args.use_graph,
-                                device=device, sync_bn=args.sync_bn)
+                                device=device, sync_bn=args.sync_bn, optimizer=args.optimizer)
     print(f"Student and Teacher are built: they are both {args.arch} networks.")
 
     frontend = None
@@ -417,6 +419,9 @@ def train_lafs(args, dataset=None):
     ckpt = os.path.join(args.output_dir, "checkpoint.pth")
     if os.path.isfile(ckpt):
         _load_checkpoint(ckpt, student, teacher, dino_loss, engine, to_restore)
+        # a reference-written sgd / lars state carries no step counts (engine.load_optimizer_state_dict): the steps its run took
+        if args.optimizer != 'adamw':
+            engine.step_count = max(engine.step_count, to_restore["epoch"] * n_it)
     start_epoch = to_restore["epoch"]
 
     start = time.time()

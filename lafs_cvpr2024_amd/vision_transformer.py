@@ -23,15 +23,18 @@ def _is_matrix_for_dgrad(name, p):
     return p.dim() == 2 and any(k in name for k in ("attn.", "mlp.", "transformer.layers."))
 
 
-def attach_arena(module, device=None):
+def attach_arena(module, device=None, second_moment=True):
     """Move every parameter of ``module`` (e.g. a MultiCropWrapper) into one ParamArena and tell the kernel-driving
-    sub-modules where they live.  Idempotent."""
+    sub-modules where they live.  Idempotent.  second_moment=False: no exp_avg_sq buffer (ParamArena), dropped from an arena
+    that already has one."""
     arena = getattr(module, "_lafs_arena", None)
     if arena is not None:
+        if not second_moment:
+            arena.exp_avg_sq = None
         return arena
     if device is None:
         device = torch.device("cuda", torch.cuda.current_device())
-    arena = ParamArena(module, device, with_grad=True, transposed=_is_matrix_for_dgrad)
+    arena = ParamArena(module, device, with_grad=True, transposed=_is_matrix_for_dgrad, second_moment=second_moment)
     object.__setattr__(module, "_lafs_arena", arena)
     for mod_name, m in module.named_modules():
         if hasattr(m, "_bind_arena"):

@@ -515,7 +515,8 @@ int lafs_l2norm_fwd(const float* x, int ldx, void* y_bf16, int ldy, float* inv_n
 int lafs_l2norm_bwd(const float* x, int ldx, const float* dy, int lddy, const float* inv_norm, float* dx, int lddx,
                     int rows, int D, hipStream_t stream);
 /* weight_norm (dim=0): w(bf16)[k,:] = g[k] * v[k,:] / ||v[k,:]|| ; also w_t(bf16) [D, ldwt] transposed copy
- * (NULL to skip); rows k in [K, Kpad) of w and columns of w_t are zero-filled.  inv_norm f32 [K]. */
+ * (NULL to skip); rows k in [K, Kpad) of w and columns of w_t are zero-filled.  inv_norm f32 [K].  An all-zero row of v gives
+ * inv_norm = inf and a NaN row of w, as in torch: there is no clamp. */
 int lafs_weightnorm_fwd(const float* v, const float* g, int K, int Kpad, int D, void* w, void* w_t, int ldwt,
                         float* inv_norm, hipStream_t stream);
 /* dv(f32)[k,:] (+)= g/||v|| * (dw - vhat * <dw, vhat>) ; dg(f32)[k] (+)= <dw, vhat>  (dg may be NULL). */

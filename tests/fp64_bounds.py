@@ -1,13 +1,14 @@
-"""The fp64 oracle of the kernel tests: plain fp64 restatements of the GEMM family's, the LayerNorm family's and the arena step's
-operations that carry, next to every value, a
+"""The fp64 oracle of the kernel tests: plain fp64 restatements of the GEMM family's, the LayerNorm family's, the arena step's and the
+DINO head's and loss's operations that carry, next to every value, a
 bound on how far the kernel's value may lie from it, element by element (never normalised by a tensor's maximum).
 
 The reference rounds to 16 bits exactly where include/lafs_hip.h says the kernel stores 16 bits, and nowhere else.  Where the kernel
 stores a 16-bit value the bound is the distance to the neighbouring 16-bit values its unrounded value can reach (`flip`): 0 where no
 rounding boundary lies within reach, so most 16-bit outputs must match the reference exactly.
 
-Shared by tests/test_gpu_mlp_fused.py, tests/test_gpu_gemm.py, tests/test_gpu_wgrad.py, tests/test_gpu_layernorm.py, tests/test_gpu_optim.py
-and the two CPU modules tests/test_oracle_gemm_host.py and tests/test_oracle_rowops_host.py (which show that the bounds are tight
+Shared by tests/test_gpu_mlp_fused.py, tests/test_gpu_gemm.py, tests/test_gpu_wgrad.py, tests/test_gpu_layernorm.py, tests/test_gpu_optim.py,
+tests/test_gpu_dino_head.py and the three CPU modules tests/test_oracle_gemm_host.py, tests/test_oracle_rowops_host.py and
+tests/test_oracle_dino_host.py (which show that the bounds are tight
 enough to mean something and that seeded faults fail them).  Everything here runs on whatever
 device its arguments live on.  The case grids, input distributions and guarded buffers of the GEMM modules are in tests/gemm_cases.py."""
 import math
@@ -385,6 +386,251 @@ def adamw_ema(p, g, m, v, t, chunk_seg, flags, step, ss, sse, hp):
         out["teacher"] = (tn, tne)
         out["teacher16"] = flip(tn, tne)
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the DINO head and loss (head.hip,
+# dino_loss.hip, dino_head_loss.hip)
+# v_exp_f32 / v_log_f32: 1 ulp, 2x margin (the allowance of tests/test_gpu_attention_cls.py); a flushed denormal result adds TINY
+EXP_REL = 4 * U
+LOG_REL = 4 * U
+ULP1 = 2 * U            # sqrtf and `/` under the project's default flags: 1 ulp
+TINY = 2.0 ** -126
+LOG2E, LN2 = 1.4426950408889634, 0.6931471805599453
+HEAD_DEPTH = 16 + 6     # head.hip row sums: a lane adds its 4 float4 (16 terms) in sequence, a 6-step butterfly follows
+
+
+def inv32(t):
+    """fl(1.0f / t) for the fp32 value of t, widened: the reciprocal temperature a kernel holds."""
+    return float(torch.tensor(1.0, dtype=f32) / torch.tensor(t, dtype=f32))
+
+
+def dino_coef(ncrops, B, student_temp, grad_scale, dev_student_temp=None):
+    """coef = grad_scale / ((2 ncrops - 2) B tau_s) as the host forms it in fp32 and, where device temperatures are given, the
+    kernels' correction coef / (fl(1 / tau_s) dev_tau_s), which swaps the host's tau_s for the device's.  The correction's division
+    runs on the device (1 ulp); the caller allows ULP1 relative for it."""
+    t = lambda v: torch.tensor(v, dtype=f32)
+    coef = t(grad_scale) / (t(float(2 * ncrops - 2)) * t(float(B)) * t(student_temp))
+    if dev_student_temp is not None:
+        coef = coef / ((t(1.0) / t(student_temp)) * t(dev_student_temp))
+    return float(coef)
+
+
+def _sumsq_row(x):
+    """Row sums of squares as head.hip forms them: same-sign terms, each square rounds (1), then HEAD_DEPTH additions."""
+    ss = (x * x).sum(1, keepdim=True)
+    return ss, (HEAD_DEPTH + 1) * U * ss
+
+
+def _row_dot(y, ye, d):
+    """s = sum_c y d over a row of head.hip's backward kernels (y known to within ye, d exact): every product rounds, the sum has
+    depth HEAD_DEPTH."""
+    t = y * d
+    s = t.sum(1, keepdim=True)
+    return s, (ye * d.abs() + U * t.abs()).sum(1, keepdim=True) + HEAD_DEPTH * U * t.abs().sum(1, keepdim=True)
+
+
+def _proj(f, fe, d, y, ye, s, se):
+    """f (d - y s), the tangent projection both backward kernels end with: y s and the difference round (or once as an fma), the
+    product with f rounds."""
+    ys = y * s
+    inner = d - ys
+    ie = ye * s.abs() + (y.abs() + ye) * se + U * ys.abs() + U * (d.abs() + ys.abs())
+    o = f * inner
+    return o, f.abs() * ie + fe * (inner.abs() + ie) + U * o.abs()
+
+
+def l2norm_fwd(x):
+    """lafs_l2norm_fwd on exact fp32 rows x [R, D]: {"inv": 1 / max(sqrtf(sum x^2), 1e-12f) [R, 1], "y": x inv, "y16": its bf16 store}, each
+    (reference, bound).  The sum of squares is carried as an interval through the root (1 ulp), the clamp (both ends clamped: a row
+    wholly below it has inv = fl(1 / 1e-12f) up to the division's ulp) and the division (1 ulp); y = x inv rounds once."""
+    ss, sse = _sumsq_row(x)
+    n = ss.sqrt()
+    ne = torch.maximum((ss + sse).sqrt() - n, n - (ss - sse).clamp_min(0).sqrt()) + ULP1 * n
+    c = f32c(1e-12)
+    d, lo, hi = n.clamp_min(c), (n - ne).clamp_min(c), (n + ne).clamp_min(c)
+    inv = 1 / d
+    inve = torch.maximum(1 / lo - inv, inv - 1 / hi) + ULP1 * inv
+    y = x * inv
+    ye = x.abs() * inve + U * y.abs()
+    return {"inv": (inv, inve), "y": (y, ye), "y16": flip(y, ye)}
+
+
+def l2norm_bwd(x, dy, inv):
+    """lafs_l2norm_bwd: dx = inv (dy - y <y, dy>) with y = x inv recomputed in fp32 (one rounding), on the inv_norm [R, 1] the kernel is
+    handed."""
+    y = x * inv
+    ye = U * y.abs()
+    s, se = _row_dot(y, ye, dy)
+    return _proj(inv, torch.zeros_like(inv), dy, y, ye, s, se)
+
+
+def weightnorm_fwd(v, g):
+    """lafs_weightnorm_fwd on the K live rows: {"inv": rsqrtf(sum v^2) [K, 1], "w": v (g inv), "w16": its bf16 store}; g [K, 1].  (Pad rows are exactly
+    0 and w_t is a bitwise transpose: neither needs a bound.)"""
+    ss, sse = _sumsq_row(v)
+    inv, inve = rsqrt_iv(ss, sse)
+    sc = g * inv
+    sce = g.abs() * inve + U * sc.abs()
+    w = v * sc
+    we = v.abs() * sce + U * w.abs()
+    return {"inv": (inv, inve), "w": (w, we), "w16": flip(w, we)}
+
+
+def weightnorm_bwd(dw, v, g, inv, dv_old=None, dg_old=None):
+    """lafs_weightnorm_bwd on the inv_norm [K, 1] it is handed: vhat = v inv (one rounding), s = <dw, vhat>, dg = (dg_old +) s,
+    dv = (dv_old +) (g inv) (dw - vhat s).  Returns {"dv", "dg"}."""
+    vh = v * inv
+    vhe = U * vh.abs()
+    s, se = _row_dot(vh, vhe, dw)
+    f = g * inv
+    dv, dve = _proj(f, U * f.abs(), dw, vh, vhe, s, se)
+    dg, dge = s, se
+    if dg_old is not None:
+        dg = dg_old + s
+        dge = se + U * dg.abs()
+    if dv_old is not None:
+        dv = dv_old + dv
+        dve = dve + U * dv.abs()
+    return {"dv": (dv, dve), "dg": (dg, dge)}
+
+
+def scaled_logits(z, ze, it, center=None, dev=False):
+    """a = (z - center) it, the argument of every exponential of the loss kernels, and the bound on the kernel's fp32 value of it: z
+    known to within ze; the subtraction rounds; the product rounds (1) and the constant it runs with is itself rounded (1: the
+    fp32 product it log2(e) of the log2-domain kernels, or the log2(e) inside __expf); with device temperatures 1.0f / temp is
+    a device division (ULP1)."""
+    d = z if center is None else z - center
+    a = d * it
+    sub = 0 if center is None else U * d.abs()
+    return a, it * (ze + sub) + (2 * U + (ULP1 if dev else 0)) * a.abs()
+
+
+def lse_rows(z, ze, inv_temp, center=None, n_exp=1, n_round=1, dev=False, ln2_product=True, parts=False):
+    """Natural log-sum-exp of the rows of (z - center) inv_temp, logits known to within ze: (lse [R, 1], bound, A = the row's largest
+    |argument|).  lse is 1-Lipschitz in the maximum norm of its arguments, so the arguments' worst error passes through unscaled.
+    parts: also the bound without the logits' own error inv_temp ze (see `dino_loss`: what is left when that error is common to the
+    log-sum-exp and to an argument it is subtracted from), which includes the second-order term 2 (inv_temp max ze)^2.
+    On top: a term exp(a_k - M) reaches the sum through at most n_exp exponentials (its own and the rescalings exp2(m - m') of the
+    running sum), EXP_REL each, whose arguments are differences of running maxima that telescope to M - a_k, each rounded once: u (M -
+    a_k) in all, weighted by the term's share of the sum; n_round fp32 roundings of the positive sum; v_log_f32 LOG_REL of max(1,
+    |log2 S|); M + log2 S rounds; ln2_product: the product with the fp32 constant ln 2 rounds and the constant is rounded."""
+    a, ae = scaled_logits(z, ze, inv_temp, center, dev)
+    A = a.abs().max(1, keepdim=True).values
+    M = a.max(1, keepdim=True).values
+    x = M - a
+    ex = torch.exp(-x)
+    S = ex.sum(1, keepdim=True)
+    L = M + torch.log(S)
+    srel = U * (ex * x).sum(1, keepdim=True) / S + n_exp * EXP_REL + n_round * U
+    c = (inv_temp * ze).expand_as(a)
+    cmax = c.max(1, keepdim=True).values
+    Lr = (ae - c).max(1, keepdim=True).values + 1.01 * srel + LOG_REL * torch.log(S).clamp_min(LN2) + U * L.abs()
+    if ln2_product:
+        Lr = Lr + 2 * U * L.abs()
+    return (L, Lr + cmax, A, Lr + 2 * cmax * cmax) if parts else (L, Lr + cmax, A)
+
+
+def _exp_minus(a, ae, L, Le):
+    """exp(a - L) as the kernels form it (v_exp_f32 of a rounded difference, arguments off by ae and Le): (value, bound).  v_exp_f32
+    flushes a denormal result: where the kernel's value can fall below TINY it may be 0, off by the value itself (<= TINY)."""
+    arg = a - L
+    v = torch.exp(arg)
+    e = v * (torch.expm1(ae + Le + 2 * U * arg.abs()) + EXP_REL)
+    return v, e + torch.where(v - e < TINY, v, torch.zeros_like(v))
+
+
+def dino_loss(s, se, t, te, center, ncrops, B, temps, coef, grad16, dev=False, fused=False):
+    """lafs_dino_loss_fwd_bwd (fused: lafs_dino_head_loss) on student logits s [ncrops B, K] and teacher logits t [2 B, K] known to
+    within se, te (0 for the unfused kernel, whose logits are operands; `gemm`'s bound for the fused one), centre [K], temps = the
+    fp32 (tau_s, tau_t) in force, coef = `dino_coef`.  Returns {"q" [2 B, K], "p", "grad" [ncrops B, K] (through `flip` where
+    grad16), "dots" [ncrops B, 1] = <sum_{i != v} q_i, s / tau_s>, "loss", "lse_s", "lse_t"} as (reference, bound) and "A" [ncrops B, 1],
+    the row's largest |logit / tau| over the student row and its two teacher rows.
+    p, q: `_exp_minus` -- the argument's error grows with |a| and |lse| and multiplies the value.  A logit's own error (se, te) is
+    common to the argument and to the log-sum-exp it is subtracted from, and is carried as such (`centred` below, and `common` for the
+    loss); every rounding of the kernels' own arithmetic is counted independently on both sides.
+    grad: coef (n_v p - sum q): the errors of both sides add (the cancellation is carried, not divided out); the sum q_0 + q_1, the
+    difference and the product with coef round; with device temperatures coef carries a device division.
+    dots, loss: sums of any order over terms that carry the errors above; depth = the longest chain of fp32 additions a term can
+    pass through in either kernel (written out below)."""
+    K = s.shape[1]
+    its, itt = inv32(temps[0]), inv32(temps[1])
+    if fused:
+        nblk = -(-K // 64)
+        trips = -(-nblk // 64)
+        # row_part: 16 values in sequence + 2 shuffles; row_lse: `trips` in sequence + 6 butterfly steps, one rescaling each
+        ne, nr = 1 + trips + 6, 18 + 2 * (trips + 6)
+    else:
+        trips = -(-K // 4096) + 1
+        # row_stats: 16 values per trip, then the butterfly (6) and the four waves (4), one rescaling each
+        ne, nr = 1 + trips + 10, 16 + 2 * (trips + 10)
+    Ls, Lse, As, Lsr = lse_rows(s, se, its, None, ne, nr, dev, not fused, parts=True)
+    Lt, Lte, At, Ltr = lse_rows(t, te, itt, center, ne, nr, dev, not fused, parts=True)
+    a_s, ase = scaled_logits(s, se, its, None, dev)
+    a_t, ate = scaled_logits(t, te, itt, center, dev)
+
+    def centred(a, ae, ze, it, L):
+        """The argument error of exp(a_k - lse) with the logits' own error eta (|eta_j| <= c_j = ze_j / tau) taken as what it is in
+        the fused kernel: the same in both passes (they form a logit with the same MFMA sequence, bit for bit), hence common to a_k
+        and to the log-sum-exp, which moves by sum_j w_j eta_j (w = the softmax; second order in `lse_rows`).  What is left of it in
+        a_k - lse is eta_k - sum_j w_j eta_j, at most (1 - w_k) c_k + sum_{j != k} w_j c_j -- 0 for a single class, ~2 c for a
+        flat row.  Every other part of ae (the roundings of the kernel's own arithmetic) stays as it is."""
+        c = (it * ze).expand_as(a)
+        w = torch.exp(a - L)
+        return ae + (w * c).sum(1, keepdim=True) - 2 * w * c
+
+    p, pe = _exp_minus(a_s, centred(a_s, ase, se, its, Ls), Ls, Lsr)
+    q, qe = _exp_minus(a_t, centred(a_t, ate, te, itt, Lt), Lt, Ltr)
+    q0, q1, q0e, q1e = q[:B], q[B:], qe[:B], qe[B:]
+    v = torch.arange(ncrops * B, device=s.device) // B
+    sel0, sel1 = (v != 0).double()[:, None], (v != 1).double()[:, None]           # crop v meets q_i for i != v
+    rep = lambda x: x.repeat(ncrops, 1)
+    qs = sel0 * rep(q0) + sel1 * rep(q1)
+    qse = sel0 * rep(q0e) + sel1 * rep(q1e) + U * qs
+    nv = sel0 + sel1
+    diff = nv * p - qs
+    g = coef * diff
+    ge = coef * (nv * pe + qse + U * diff.abs()) + (U + (ULP1 if dev else 0)) * g.abs()
+    ge = ge + torch.where(g.abs() - ge < TINY, g.abs(), torch.zeros_like(g))       # (a denormal product may be flushed as well)
+    out = {"q": (q, qe), "p": (p, pe), "lse_s": (Ls, Lse), "lse_t": (Lt, Lte), "grad": flip(g, ge) if grad16 else (g, ge)}
+    At2 = torch.maximum(At[:B], At[B:])
+    out["A"] = torch.maximum(As, rep(At2))
+    term = qs * a_s
+    dots, dabs = term.sum(1, keepdim=True), term.abs().sum(1, keepdim=True)
+    terme = (qse * a_s.abs() + qs * ase + U * term.abs()).sum(1, keepdim=True)
+    rows_s = ncrops * B
+    if fused:
+        # a thread's 32 values per 32-row tile over <= ceil(rows_s / 128) tiles, the wave (6) and the four waves (2); the finalize
+        # kernel: a thread's rows and blocks in sequence, then 256 partial sums in sequence
+        d_dot = 32 * -(-rows_s // 128) + 8
+        d_fin = -(-rows_s // 256) + -(-nblk // 256) + min(256, max(rows_s, nblk))          # (the other partial sums are exact zeros)
+    else:
+        # a thread's 4 values, the wave (6), the four waves (3), the 1024-class chunks in sequence; the finalize kernel: a thread's
+        # <= 2 rows, the wave (6), 16 waves in sequence
+        d_dot = 4 + 6 + 3 + -(-K // 1024)
+        d_fin = 2 + 6 + 16
+    out["dots"] = (dots, terme + d_dot * U * dabs)
+    N = (2 * ncrops - 2) * B
+    loss = (nv * Ls - dots).sum() / N
+    lmag = (nv * Ls.abs() + dabs).sum()
+    # A student logit's own error eta_j is common to n_v lse (which it moves by n_v p_j eta_j) and to the dot (by sum q_j eta_j): to
+    # first order the loss moves by the gradient, (n_v p_j - sum q_j) eta_j; the second order is in `lse_rows`' part without it.
+    c_s = (its * se).expand_as(a_s)
+    common = (diff.abs() * c_s).sum()
+    terme_r = (qse * a_s.abs() + qs * (ase - c_s) + U * term.abs()).sum()
+    le = ((nv * Lsr).sum() + terme_r + common + (d_dot + d_fin + 2) * U * lmag) / N + ULP1 * loss.abs()
+    if fused:
+        le = le + 2 * U * (nv * Ls.abs()).sum() / N              # the product with the fp32 constant ln 2, here in the finalize kernel
+    out["loss"] = (loss.reshape(1), le.reshape(1))
+    return out
+
+
+def center_ema(center, colsum, inv_rows, m):
+    """lafs_center_ema: center m + colsum inv_rows (1 - m) on the fp32 values of inv_rows and m (1.0f - m is exact for m in [0.5, 1]):
+    two products on the right, one on the left, one sum."""
+    ir, mm = f32c(inv_rows), f32c(m)
+    new = colsum * ir * (f32c(1.0) - mm)
+    ref = center * mm + new
+    return ref, U * ((center * mm).abs() + 2 * new.abs() + ref.abs())
 
 
 # ------------------------------------------------------------------------------------------------ checks

@@ -832,6 +832,26 @@ int lafs_mix_normalize(const uint8_t* src_u8, float* dst, int B, int S, const in
 int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, const float* lam_rows,
                                     int lam_stride, float eps, float s, float m, int margin_type, float loss_scale, void* dcos, int lddc,
                                     float* loss_out, float* row_ws, float* part_ws, hipStream_t stream);
+/* AdaFace head (Kim, Jain, Liu, CVPR 2022; PARITY UNPINNED: the reference names it, train_largescale.py:820, util/utils.py:398, and
+ * ships no class): a margin pair per row from the embedding's norm, the image-quality proxy.  inv_norm f32 [B] as lafs_l2norm_fwd
+ * writes it; state f32 [2] = (batch_mean, batch_std) in DEVICE memory (initially 20, 100), read and written when the kernel runs.
+ *   n_b = clip(1 / inv_norm[b], 1e-3, 100);  mean = sum n_b / B;  std = sqrt(sum (n_b - mean)^2 / (B - 1))  (unbiased, two passes);
+ *   update = 1: state <- t_alpha (mean, std) + (1 - t_alpha) state, BEFORE it is used;  update = 0: the state is read, not written;
+ *   k_b = clip((n_b - batch_mean) / (batch_std + 1e-3) h, -1, 1);  row_margin f32 [B, 2] = (g_ang, g_add) = (-m k_b, m + m k_b).
+ * One workgroup, a fixed reduction order (the same bits run to run), no atomics.  B >= 2. */
+int lafs_adaface_margins(const float* inv_norm, int B, float* state, float t_alpha, float h, float m, int update, float* row_margin,
+                         hipStream_t stream);
+/* The (row, chunk) launches of lafs_margin_softmax_ce_mix_bf16 with AdaFace's per-row margins in place of (m, margin_type, eps):
+ *   c^ = clamp(c, -1 + 1e-3, 1 - 1e-3) on every class;  on the classes whose target weight is > 0 (both spikes of a mixed row):
+ *   z = s (cos(clip(acos c^ + g_ang[b], 1e-3, pi - 1e-3)) - g_add[b]);  elsewhere z = s c^;  loss_b = lse(z) - sum_k y_k z_k;
+ *   dcos_k = loss_scale/B (softmax_k - y_k) dz_k/dc_k,  dz/dc = s sin(theta_m) / sin(theta) on a target, s elsewhere, and exactly 0 where
+ *   c was clamped or theta_m clipped (the thresholds are the fp32 constants).  No gradient flows into the margins.
+ * lambda of row b = lam_rows[b * lam_stride] (device memory; stride 0: one lambda for the batch, 1: an array, LAFS_MIX_WORDS: the
+ * table); y2 == NULL: the partner of row b is row B-1-b.  cos is read-only; bf16 dcos [B, lddc], pad columns [C, lddc) zeroed;
+ * row_ws f32 [B]; part_ws f32 [B * 32]. */
+int lafs_margin_softmax_ce_ada_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, const float* lam_rows,
+                                    int lam_stride, const float* row_margin, float s, float loss_scale, void* dcos, int lddc,
+                                    float* loss_out, float* row_ws, float* part_ws, hipStream_t stream);
 /* dst(i32)[n] = src(i64)[n]: the loader's int64 labels (train_largescale.py:842) into the kernels' index type without an ATen cast */
 int lafs_cast_i64_i32(const int64_t* src, int32_t* dst, int n, hipStream_t stream);
 /* Patch-vector gradient f32 [B, (S/8)^2, 192] -> image gradient f32 [B, 3, S, S]: the inverse re-indexing of lafs_patchify (the

@@ -214,6 +214,8 @@ _PROTOS = {
     "lafs_margin_softmax_ce_bf16": [vp, i32, i32, i32, vp, vp, f32, vp, f32, f32, i32, f32, vp, i32, vp, vp, vp],
     "lafs_mix_normalize": [vp, vp, i32, i32, vp],
     "lafs_margin_softmax_ce_mix_bf16": [vp, i32, i32, i32, vp, vp, vp, i32, f32, f32, f32, i32, f32, vp, i32, vp, vp, vp],
+    "lafs_adaface_margins": [vp, i32, vp, f32, f32, f32, i32, vp],
+    "lafs_margin_softmax_ce_ada_bf16": [vp, i32, i32, i32, vp, vp, vp, i32, vp, f32, f32, vp, i32, vp, vp, vp],
     "lafs_cast_i64_i32": [vp, vp, i32],
     "lafs_dino_head_loss": [vp, vp, vp, vp, i32, vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32, f32, vp, vp],
     "lafs_transpose_bf16": [vp, i32, i32, i32, vp, i32],

@@ -27,6 +27,40 @@ __device__ __forceinline__ float margin_dlogit(float c, float y, float s, float 
   return s * __sinf(th + m) / __sinf(th);
 }
 
+// The margin of a launch, behind one pair of calls: logit(c, y) = z and dlogit(c, y) = dz/dcos of a class with cosine c and target
+// weight y.  FixedMargin: CosFace / ArcFace, one (m, type) for the batch -- the two functions above.  AdaMargin: AdaFace (Kim, Jain,
+// Liu, CVPR 2022; PARITY UNPINNED), a pair per ROW formed by lafs_adaface_margins from the embedding's norm:
+//     c^ = clamp(c, -1 + eps, 1 - eps) on every class;   target (y > 0): z = s (cos(clip(acos c^ + g_ang, eps, pi - eps)) - g_add);
+//     elsewhere z = s c^;   dz/dc = s sin(theta_m) / sin(theta) on a target, s elsewhere, and exactly 0 where c was clamped or theta_m
+//     clipped.
+// A row's pair is the same in every lane of its workgroup (blockIdx.y indexes it): it is loaded once, into scalar registers.  The
+// target's acosf / cosf / sinf are the full-precision library functions: at most two classes per row take that branch.
+struct FixedMargin {
+  float s, m; int type;
+  __device__ __forceinline__ float logit(float c, float y) const { return margin_logit(c, y, s, m, type); }
+  __device__ __forceinline__ float dlogit(float c, float y) const { return margin_dlogit(c, y, s, m, type); }
+  __device__ __forceinline__ const FixedMargin& row(int) const { return *this; }
+};
+constexpr float ADA_EPS = 1e-3f, ADA_LO = -1.f + 1e-3f, ADA_HI = 1.f - 1e-3f, ADA_PI_HI = 3.14159265358979323846f - 1e-3f;
+struct AdaMargin {
+  float s, g_ang, g_add;
+  __device__ __forceinline__ float logit(float c, float y) const {
+    const float cc = fminf(fmaxf(c, ADA_LO), ADA_HI);
+    if (y > 0.f) return s * (cosf(fminf(fmaxf(acosf(cc) + g_ang, ADA_EPS), ADA_PI_HI)) - g_add);
+    return s * cc;
+  }
+  __device__ __forceinline__ float dlogit(float c, float y) const {
+    if (c < ADA_LO || c > ADA_HI) return 0.f;
+    if (y <= 0.f) return s;
+    const float th = acosf(c), tm = th + g_ang;
+    return (tm < ADA_EPS || tm > ADA_PI_HI) ? 0.f : s * sinf(tm) / sinf(th);
+  }
+};
+struct AdaMargins {
+  float s; const float* row_margin;                   // f32 [B, 2] = (g_ang, g_add)
+  __device__ __forceinline__ AdaMargin row(int b) const { return {s, row_margin[2 * (size_t)b], row_margin[2 * (size_t)b + 1]}; }
+};
+
 // ---- the dense head's loss: margin + softmax + soft-target CE, one implementation behind three entry points ----
 // Target of row b, never materialised (util/mixup_my.py:18-24 label smoothing; :152-200 batch / pair / elem modes; :71-81 CutMix's
 // area-corrected lambda):
@@ -91,15 +125,23 @@ struct OnlineLse {
 
 // gscale * (exp(z - shift) * pscale - y) * dz/dcos: the dense head has shift = lse, pscale = 1; the class-sharded head the global
 // max and 1/Z
+template <class MG>
+__device__ __forceinline__ float margin_grad(float c, float y, float shift, float pscale, const MG& mg, float gscale) {
+  return gscale * (__expf(mg.logit(c, y) - shift) * pscale - y) * mg.dlogit(c, y);
+}
 __device__ __forceinline__ float margin_grad(float c, float y, float shift, float pscale, float s, float m, int type, float gscale) {
-  return gscale * (__expf(margin_logit(c, y, s, m, type) - shift) * pscale - y) * margin_dlogit(c, y, s, m, type);
+  return margin_grad(c, y, shift, pscale, FixedMargin{s, m, type}, gscale);
 }
 // the spikes' share of sum_k y_k z_k: (y_k - off) z_k at a1 and a2 (a1 == a2: the summed weight, once)
-__device__ __forceinline__ float spike_dot(const float* row, const MixLabel& label, float s, float m, int type) {
+template <class MG>
+__device__ __forceinline__ float spike_dot(const float* row, const MixLabel& label, const MG& mg) {
   const int a1 = label.a1, a2 = label.a2;
-  float dot = (label(a1) - label.off) * margin_logit(row[a1], label(a1), s, m, type);
-  if (a2 != a1) dot += (label(a2) - label.off) * margin_logit(row[a2], label(a2), s, m, type);
+  float dot = (label(a1) - label.off) * mg.logit(row[a1], label(a1));
+  if (a2 != a1) dot += (label(a2) - label.off) * mg.logit(row[a2], label(a2));
   return dot;
+}
+__device__ __forceinline__ float spike_dot(const float* row, const MixLabel& label, float s, float m, int type) {
+  return spike_dot(row, label, FixedMargin{s, m, type});
 }
 
 // One workgroup per sample row, in place, one launch: cos -> d loss / d cos (f32).  The row loss is formed before the barrier
@@ -149,8 +191,9 @@ __device__ __forceinline__ float mce_fold_lse(const float* prow) {
   return r.lse();
 }
 // bf16 gradient of classes [k0, k1) of one row (k0 a multiple of 4); `pads`: also zero the pad columns [C, lddc) of the gradient operand
-__device__ __forceinline__ void mce_write_chunk(const float* row, bf16_t* drow, MceChunk ck, const MixLabel& label, float lse, float s, float m,
-                                                int type, float gscale, bool pads, int C, int lddc) {
+template <class MG>
+__device__ __forceinline__ void mce_write_chunk(const float* row, bf16_t* drow, MceChunk ck, const MixLabel& label, float lse, const MG& mg,
+                                                float gscale, bool pads, int C, int lddc) {
   const int k1 = ck.k1;
   for (int k = ck.k0 + 4 * threadIdx.x; k < k1; k += 1024) {        // 4 consecutive classes per thread: 16-byte loads, 8-byte stores
     if (k + 3 < k1) {
@@ -158,30 +201,32 @@ __device__ __forceinline__ void mce_write_chunk(const float* row, bf16_t* drow, 
       const float cv[4] = {c4.x, c4.y, c4.z, c4.w};
       float g[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) g[e] = margin_grad(cv[e], label(k + e), lse, 1.f, s, m, type, gscale);
+      for (int e = 0; e < 4; ++e) g[e] = margin_grad(cv[e], label(k + e), lse, 1.f, mg, gscale);
       *reinterpret_cast<uint2*>(drow + k) = make_uint2(pack_bf2(g[0], g[1]), pack_bf2(g[2], g[3]));
     } else {
-      for (int e = 0; e < 4 && k + e < k1; ++e) drow[k + e] = f2bf(margin_grad(row[k + e], label(k + e), lse, 1.f, s, m, type, gscale));
+      for (int e = 0; e < 4 && k + e < k1; ++e) drow[k + e] = f2bf(margin_grad(row[k + e], label(k + e), lse, 1.f, mg, gscale));
     }
   }
   if (pads)
     for (int k = C + threadIdx.x; k < lddc; k += 256) drow[k] = 0;
 }
 
-template <bool SMOOTH>
+// MGS: the launch's margins (FixedMargin itself, or AdaMargins: the table a row's AdaMargin is taken from)
+template <bool SMOOTH, class MGS>
 __global__ __launch_bounds__(256) void margin_ce_part_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
                                                             const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
-                                                            float lam, float eps, float s, float m, int type, float* __restrict__ part) {
+                                                            float lam, float eps, MGS margins, float* __restrict__ part) {
   constexpr int NP = SMOOTH ? 3 : 2;
   __shared__ float sz[4];
   const int b = blockIdx.y, ch = blockIdx.x;
   const float* row = cosv + (size_t)b * ld;
+  const auto mg = margins.row(b);
   const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, lam, eps, b, B, C);
   const MceChunk ck = mce_chunk(C, ch);
   OnlineLse acc;
   float zs = 0.f;
   for (int k = ck.k0 + threadIdx.x; k < ck.k1; k += 256) {
-    const float z = margin_logit(row[k], label(k), s, m, type);
+    const float z = mg.logit(row[k], label(k));
     if constexpr (SMOOTH) zs += z;
     acc.add(z);
   }
@@ -196,20 +241,21 @@ __global__ __launch_bounds__(256) void margin_ce_part_kernel(const float* __rest
     if constexpr (SMOOTH) p[2] = (sz[0] + sz[1]) + (sz[2] + sz[3]);
   }
 }
-template <bool SMOOTH>
+template <bool SMOOTH, class MGS>
 __global__ __launch_bounds__(256) void margin_ce_grad_kernel(const float* __restrict__ cosv, int ld, int B, int C, const int* __restrict__ y1,
                                                             const int* __restrict__ y2, const float* __restrict__ lam_rows, int lam_stride,
-                                                            float lam, float eps, float s, float m, int type, float gscale,
+                                                            float lam, float eps, MGS margins, float gscale,
                                                             const float* __restrict__ part, bf16_t* __restrict__ dcos, int lddc,
                                                             float* __restrict__ row_loss) {
   constexpr int NP = SMOOTH ? 3 : 2;
   const int b = blockIdx.y, ch = blockIdx.x;
   const float* row = cosv + (size_t)b * ld;
+  const auto mg = margins.row(b);
   const MixLabel label = mix_label(y1, y2, lam_rows, lam_stride, lam, eps, b, B, C);
   const float* prow = part + (size_t)b * MCE_NCH * NP;
   const float lse = mce_fold_lse<NP>(prow);
   if (ch == 0 && threadIdx.x == 0) {
-    float loss = lse - spike_dot(row, label, s, m, type);   // sum_k y_k = 1
+    float loss = lse - spike_dot(row, label, mg);   // sum_k y_k = 1
     if constexpr (SMOOTH) {
       float Zs = 0.f;
       for (int c = 0; c < MCE_NCH; ++c) Zs += prow[c * NP + 2];
@@ -217,7 +263,7 @@ __global__ __launch_bounds__(256) void margin_ce_grad_kernel(const float* __rest
     }
     row_loss[b] = loss;
   }
-  mce_write_chunk(row, dcos + (size_t)b * lddc, mce_chunk(C, ch), label, lse, s, m, type, gscale, ch == MCE_NCH - 1, C, lddc);
+  mce_write_chunk(row, dcos + (size_t)b * lddc, mce_chunk(C, ch), label, lse, mg, gscale, ch == MCE_NCH - 1, C, lddc);
 }
 
 __global__ __launch_bounds__(256) void cast_i64_i32_kernel(const long long* __restrict__ src, int* __restrict__ dst, int n) {
@@ -478,16 +524,56 @@ __global__ __launch_bounds__(LMSE_THREADS) void landmark_mse_kernel(const float2
   }
 }
 
+// ---- AdaFace: the batch's norm statistics, the running state and every row's margin pair, ONE workgroup ----
+// n_b = clip(1 / inv_norm[b], 1e-3, 100);  mean = sum n_b / B;  std = sqrt(sum (n_b - mean)^2 / (B - 1)), two passes (a sum of squares
+// cancels at norms near 20 +- 0.2);  update: state <- t (mean, std) + (1 - t) state, FIRST;  k_b = clip((n_b - batch_mean) /
+// (batch_std + 1e-3) h, -1, 1);  row_margin[b] = (-m k_b, m + m k_b).  Fixed order, no atomics: a thread adds its rows in index order,
+// a 64-lane butterfly follows, every thread adds the four wave sums as (0 + 1) + (2 + 3).  The state lives in device memory and is
+// read and written when the kernel runs: a replayed graph moves it once per replay.
+__device__ __forceinline__ float ada_block_sum(float v, float* red) {
+  v = wave_sum(v);
+  __syncthreads();                                     // (red may still be read from the sum before)
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ float ada_norm(float inv) { return fminf(fmaxf(1.f / inv, 1e-3f), 100.f); }
+__global__ __launch_bounds__(256) void adaface_margins_kernel(const float* __restrict__ inv_norm, int B, float* __restrict__ state, float t_alpha,
+                                                             float h, float m, int update, float* __restrict__ row_margin) {
+  __shared__ float red[4], st[2];
+  float a = 0.f;
+  for (int i = threadIdx.x; i < B; i += 256) a += ada_norm(inv_norm[i]);
+  const float mean = ada_block_sum(a, red) / (float)B;
+  float q = 0.f;
+  for (int i = threadIdx.x; i < B; i += 256) { const float d = ada_norm(inv_norm[i]) - mean; q = __builtin_fmaf(d, d, q); }
+  const float sd = sqrtf(ada_block_sum(q, red) / (float)(B - 1));
+  if (threadIdx.x == 0) {
+    float bm = state[0], bs = state[1];
+    if (update) {
+      bm = __builtin_fmaf(t_alpha, mean, (1.f - t_alpha) * bm);
+      bs = __builtin_fmaf(t_alpha, sd, (1.f - t_alpha) * bs);
+      state[0] = bm; state[1] = bs;
+    }
+    st[0] = bm; st[1] = bs;
+  }
+  __syncthreads();
+  const float bm = st[0], den = st[1] + 1e-3f;
+  for (int i = threadIdx.x; i < B; i += 256) {
+    const float k = fminf(fmaxf((ada_norm(inv_norm[i]) - bm) / den * h, -1.f), 1.f), mk = m * k;
+    *reinterpret_cast<float2*>(row_margin + 2 * (size_t)i) = make_float2(-mk, m + mk);
+  }
+}
+
 // the chunked form's three launches: partials, gradient + row losses, mean loss
-template <bool SMOOTH>
+template <bool SMOOTH, class MGS>
 int launch_margin_ce(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2, const float* lam_rows, int lam_stride, float lam,
-                     float eps, float s, float m, int margin_type, float loss_scale, void* dcos, int lddc, float* loss_out, float* row_ws,
-                     float* part_ws, hipStream_t stream) {
-  hipLaunchKernelGGL(margin_ce_part_kernel<SMOOTH>, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, lam, eps,
-                     s, m, margin_type, part_ws);
+                     float eps, MGS margins, float loss_scale, void* dcos, int lddc, float* loss_out, float* row_ws, float* part_ws,
+                     hipStream_t stream) {
+  hipLaunchKernelGGL((margin_ce_part_kernel<SMOOTH, MGS>), dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride,
+                     lam, eps, margins, part_ws);
   LAFS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(margin_ce_grad_kernel<SMOOTH>, dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride, lam, eps,
-                     s, m, margin_type, loss_scale / (float)B, part_ws, (bf16_t*)dcos, lddc, row_ws);
+  hipLaunchKernelGGL((margin_ce_grad_kernel<SMOOTH, MGS>), dim3(MCE_NCH, B), dim3(256), 0, stream, cos, ld, B, C, y1, y2, lam_rows, lam_stride,
+                     lam, eps, margins, loss_scale / (float)B, part_ws, (bf16_t*)dcos, lddc, row_ws);
   LAFS_LAUNCH_CHECK();
   hipLaunchKernelGGL(mean_kernel, dim3(1), dim3(256), 0, stream, row_ws, B, 1.0f / (float)B, loss_out);
   LAFS_LAUNCH_CHECK();
@@ -522,8 +608,8 @@ extern "C" int lafs_margin_softmax_ce_bf16(const float* cos, int ld, int B, int 
   LAFS_CHECK_ARG(cos && y1 && dcos && loss_out && row_ws && part_ws && B > 0 && C > 0 && ld >= C && lddc >= C, "bad operand");
   LAFS_CHECK_ARG(ld % 4 == 0 && lddc % 4 == 0, "row strides must be multiples of 4 elements");
   LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
-  return launch_margin_ce<false>(cos, ld, B, C, y1, y2, lam_dev, 0, lam, 0.f, s, m, margin_type, loss_scale, dcos, lddc, loss_out, row_ws, part_ws,
-                                 stream);
+  return launch_margin_ce<false>(cos, ld, B, C, y1, y2, lam_dev, 0, lam, 0.f, FixedMargin{s, m, margin_type}, loss_scale, dcos, lddc, loss_out,
+                                 row_ws, part_ws, stream);
 }
 
 extern "C" int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2,
@@ -537,8 +623,34 @@ extern "C" int lafs_margin_softmax_ce_mix_bf16(const float* cos, int ld, int B, 
   LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
   LAFS_CHECK_ARG(eps >= 0.f && eps < 1.f, "label smoothing must lie in [0, 1)");
   LAFS_CHECK_ARG(eps == 0.f || margin_type == 0, "label smoothing needs the CosFace margin (ArcFace has no margin for a dense target)");
-  const auto launch = eps > 0.f ? launch_margin_ce<true> : launch_margin_ce<false>;        // eps == 0: off = 0, nothing to smooth
-  return launch(cos, ld, B, C, y1, y2, lam_rows, lam_stride, 0.f, eps, s, m, margin_type, loss_scale, dcos, lddc, loss_out, row_ws, part_ws, stream);
+  const auto launch = eps > 0.f ? launch_margin_ce<true, FixedMargin> : launch_margin_ce<false, FixedMargin>;        // eps == 0: off = 0, nothing to smooth
+  return launch(cos, ld, B, C, y1, y2, lam_rows, lam_stride, 0.f, eps, FixedMargin{s, m, margin_type}, loss_scale, dcos, lddc, loss_out, row_ws,
+                part_ws, stream);
+}
+
+extern "C" int lafs_adaface_margins(const float* inv_norm, int B, float* state, float t_alpha, float h, float m, int update, float* row_margin,
+                                    hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(inv_norm && state && row_margin, "bad operand");
+  LAFS_CHECK_ARG((uintptr_t)row_margin % 8 == 0, "row_margin pairs must be 8-byte aligned");
+  LAFS_CHECK_ARG(B >= 2, "the unbiased standard deviation of the batch's norms needs at least two rows");
+  LAFS_CHECK_ARG(t_alpha >= 0.f && t_alpha <= 1.f, "t_alpha must lie in [0, 1]");
+  LAFS_CHECK_ARG(update == 0 || update == 1, "update must be 0 (read the state) or 1 (update it first)");
+  hipLaunchKernelGGL(adaface_margins_kernel, dim3(1), dim3(256), 0, stream, inv_norm, B, state, t_alpha, h, m, update, row_margin);
+  LAFS_LAUNCH_CHECK();
+  return LAFS_OK;
+}
+
+extern "C" int lafs_margin_softmax_ce_ada_bf16(const float* cos, int ld, int B, int C, const int32_t* y1, const int32_t* y2,
+                                               const float* lam_rows, int lam_stride, const float* row_margin, float s, float loss_scale,
+                                               void* dcos, int lddc, float* loss_out, float* row_ws, float* part_ws, hipStream_t stream) {
+  LAFS_CLEAR_ERROR();
+  LAFS_CHECK_ARG(cos && y1 && lam_rows && row_margin && dcos && loss_out && row_ws && part_ws && B > 0 && C > 0 && ld >= C && lddc >= C,
+                 "bad operand");
+  LAFS_CHECK_ARG(ld % 4 == 0 && lddc % 4 == 0, "row strides must be multiples of 4 elements");
+  LAFS_CHECK_ARG(lam_stride >= 0, "lam_stride counts 32-bit words between two rows' lambdas (0: one lambda for the batch)");
+  return launch_margin_ce<false>(cos, ld, B, C, y1, y2, lam_rows, lam_stride, 0.f, 0.f, AdaMargins{s, row_margin}, loss_scale, dcos, lddc, loss_out,
+                                 row_ws, part_ws, stream);
 }
 
 extern "C" int lafs_cast_i64_i32(const int64_t* src, int32_t* dst, int n, hipStream_t stream) {
@@ -618,6 +730,7 @@ extern "C" int lafs_shard_margin_rowmax(const float* cos, int ld, int B, int S, 
                                         const float* lam, float s, float m, int margin_type, float* rowmax, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(cos && y_local && rowmax && B > 0 && S > 0 && ld >= S, "bad operand");
+  LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
   LAFS_CHECK_ARG(y2_local == nullptr || margin_type == 0, "soft (mixup) targets: CosFace margin only (ArcFace takes hard labels)");
   hipLaunchKernelGGL(shard_rowmax_kernel, dim3(B), dim3(256), 0, stream, cos, ld, S, y_local, y2_local, lam, s, m, margin_type, rowmax);
   LAFS_LAUNCH_CHECK();
@@ -629,6 +742,7 @@ extern "C" int lafs_shard_margin_rowsum(const float* cos, int ld, int B, int S, 
                                         float* target_logit, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(cos && y_local && gmax && rowsum && target_logit && B > 0 && S > 0 && ld >= S, "bad operand");
+  LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
   LAFS_CHECK_ARG(y2_local == nullptr || margin_type == 0, "soft (mixup) targets: CosFace margin only (ArcFace takes hard labels)");
   hipLaunchKernelGGL(shard_rowsum_kernel, dim3(B), dim3(256), 0, stream, cos, ld, S, y_local, y2_local, lam, s, m, margin_type, gmax,
                      rowsum, target_logit);
@@ -641,6 +755,7 @@ extern "C" int lafs_shard_margin_grad(float* cos, int ld, int B, int S, const in
                                       float grad_scale, hipStream_t stream) {
   LAFS_CLEAR_ERROR();
   LAFS_CHECK_ARG(cos && y_local && gmax && Z && B > 0 && S > 0 && ld >= S, "bad operand");
+  LAFS_CHECK_ARG(margin_type == 0 || margin_type == 1, "margin_type must be 0 (CosFace) or 1 (ArcFace)");
   LAFS_CHECK_ARG(y2_local == nullptr || margin_type == 0, "soft (mixup) targets: CosFace margin only (ArcFace takes hard labels)");
   hipLaunchKernelGGL(shard_grad_kernel, dim3(B), dim3(256), 0, stream, cos, ld, S, y_local, y2_local, lam, s, m, margin_type, gmax, Z,
                      grad_scale);

@@ -1,5 +1,5 @@
 """Drop-in surface of the reference's ``face_pre_pro/ViT_face.py`` for the symbols on the hot path
-(SURVEY.md section 8b): ``CosFace``, ``ViT_face_landmark_patch8`` (Part-fViT) and
+(SURVEY.md section 8b): ``CosFace``, ``AdaFace`` (named by the reference, restated from the paper), ``ViT_face_landmark_patch8`` (Part-fViT) and
 ``extract_patches_pytorch_gridsample`` -- same constructor / forward signatures and state_dict keys, running on the
 gfx950 HIP kernels -- and for fViT, ``ViTs_face_overlap`` (the plain face transformer with released weights).  The other experiment
 variants the entry points never instantiate are not provided.
@@ -56,49 +56,64 @@ def extract_patches_pytorch_gridsample(imgs, landmarks, patch_shape=None, num_la
 
 
 # ------------------------------------------------------------------------------------------------- margin head
+def _cosine_fwd(x, weight):
+    """cos(x, W) f32 [B, C]: an MFMA GEMM over row-normalised bf16 operands; the normalisations are HIP row kernels.  Returns the
+    cosines and what `_cosine_bwd` needs (inv_x: 1 / ||x_b|| as lafs_l2norm_fwd writes it)."""
+    B, D = x.shape
+    C = weight.shape[0]
+    Cpad = (C + 127) // 128 * 128
+    dev = x.device
+    xn = torch.empty(B, D, device=dev, dtype=bf16); inv_x = torch.empty(B, device=dev, dtype=f32)
+    x32 = x.contiguous().float()
+    call("lafs_l2norm_fwd", _p(x32), D, _p(xn), D, _p(inv_x), B, D)
+    wn = torch.empty(Cpad, D, device=dev, dtype=bf16); inv_w = torch.empty(C, device=dev, dtype=f32)
+    ones = torch.ones(C, device=dev, dtype=f32)
+    w32 = weight.contiguous().float()
+    call("lafs_weightnorm_fwd", _p(w32), _p(ones), C, Cpad, D, _p(wn), None, Cpad, _p(inv_w))
+    cos = ops.gemm_nt(xn, wn, _lib.EPI_F32, n_cols=Cpad)[:, :C]
+    return cos, (x32, w32, xn, wn, inv_x, inv_w, ones)
+
+
+def _cosine_bwd(saved, dcos_f32):
+    """(d x, d W) from d cos f32 [B, C] (rounded to bf16, the operand format of the two gradient GEMMs)."""
+    x32, w32, xn, wn, inv_x, inv_w, ones = saved
+    B, D = x32.shape
+    C, Cpad = w32.shape[0], wn.shape[0]
+    dev = x32.device
+    dcos = torch.zeros(B, Cpad, device=dev, dtype=bf16)
+    dcos[:, :C] = dcos_f32.to(bf16)
+    # d(xn) = dcos @ wn  (contraction over classes -> split-K), d(wn) = dcos^T @ xn
+    wn_t = wn.t().contiguous()
+    dxn = ops.gemm_nt(dcos, wn_t, _lib.EPI_ATOMIC_F32, splits=max(1, min(64, Cpad // 1024)))
+    dwn = torch.zeros(Cpad, D, device=dev, dtype=f32)
+    ops.gemm_tn_acc(dcos, xn, dwn, splits=1)
+    dx = torch.empty(B, D, device=dev, dtype=f32)
+    call("lafs_l2norm_bwd", _p(x32), D, _p(dxn), D, _p(inv_x), _p(dx), D, B, D)
+    dw = torch.empty(C, D, device=dev, dtype=f32)
+    call("lafs_weightnorm_bwd", _p(dwn), _p(w32), _p(ones), _p(inv_w), C, D, _p(dw), None, 0)
+    return dx, dw
+
+
+def _dense_label(label, B, C, dev):
+    if label.dim() > 1:
+        return label.to(f32)
+    return torch.zeros(B, C, device=dev, dtype=f32).scatter_(1, label.view(-1, 1).long(), 1.0)
+
+
 class _CosFaceFunction(torch.autograd.Function):
-    """s * (cos(x, W) - m * y).  cos is an MFMA GEMM over row-normalised bf16 operands; the normalisations are HIP
-    row kernels.  (The training engine fuses margin + softmax + CE instead: lafs_margin_softmax_ce_bf16 / _mix_bf16.)"""
+    """s * (cos(x, W) - m * y).  (The training engine fuses margin + softmax + CE instead: lafs_margin_softmax_ce_bf16 / _mix_bf16.)"""
 
     @staticmethod
     def forward(ctx, x, weight, label, s, m):
-        B, D = x.shape
-        C = weight.shape[0]
-        Cpad = (C + 127) // 128 * 128
-        dev = x.device
-        xn = torch.empty(B, D, device=dev, dtype=bf16); inv_x = torch.empty(B, device=dev, dtype=f32)
-        x32 = x.contiguous().float()
-        call("lafs_l2norm_fwd", _p(x32), D, _p(xn), D, _p(inv_x), B, D)
-        wn = torch.empty(Cpad, D, device=dev, dtype=bf16); inv_w = torch.empty(C, device=dev, dtype=f32)
-        ones = torch.ones(C, device=dev, dtype=f32)
-        w32 = weight.contiguous().float()
-        call("lafs_weightnorm_fwd", _p(w32), _p(ones), C, Cpad, D, _p(wn), None, Cpad, _p(inv_w))
-        cos = ops.gemm_nt(xn, wn, _lib.EPI_F32, n_cols=Cpad)[:, :C]
-        if label.dim() > 1:
-            y = label.to(f32)
-        else:
-            y = torch.zeros(B, C, device=dev, dtype=f32).scatter_(1, label.view(-1, 1).long(), 1.0)
-        ctx.save_for_backward(x32, w32, xn, wn, inv_x, inv_w, ones)
-        ctx.s, ctx.C, ctx.Cpad = s, C, Cpad
+        cos, saved = _cosine_fwd(x, weight)
+        y = _dense_label(label, x.shape[0], weight.shape[0], x.device)
+        ctx.save_for_backward(*saved)
+        ctx.s = s
         return s * (cos - m * y)
 
     @staticmethod
     def backward(ctx, dout):
-        x32, w32, xn, wn, inv_x, inv_w, ones = ctx.saved_tensors
-        B, D = x32.shape
-        C, Cpad = ctx.C, ctx.Cpad
-        dev = x32.device
-        dcos = torch.zeros(B, Cpad, device=dev, dtype=bf16)
-        dcos[:, :C] = (dout * ctx.s).to(bf16)
-        # d(xn) = dcos @ wn  (contraction over classes -> split-K), d(wn) = dcos^T @ xn
-        wn_t = wn.t().contiguous()
-        dxn = ops.gemm_nt(dcos, wn_t, _lib.EPI_ATOMIC_F32, splits=max(1, min(64, Cpad // 1024)))
-        dwn = torch.zeros(Cpad, D, device=dev, dtype=f32)
-        ops.gemm_tn_acc(dcos, xn, dwn, splits=1)
-        dx = torch.empty(B, D, device=dev, dtype=f32)
-        call("lafs_l2norm_bwd", _p(x32), D, _p(dxn), D, _p(inv_x), _p(dx), D, B, D)
-        dw = torch.empty(C, D, device=dev, dtype=f32)
-        call("lafs_weightnorm_bwd", _p(dwn), _p(w32), _p(ones), _p(inv_w), C, D, _p(dw), None, 0)
+        dx, dw = _cosine_bwd(ctx.saved_tensors, dout * ctx.s)
         return dx, dw, None, None, None
 
 
@@ -122,6 +137,77 @@ class CosFace(nn.Module):
 
     def __repr__(self):
         return f"{self.__class__.__name__}(in_features = {self.in_features}, out_features = {self.out_features}, s = {self.s}, m = {self.m})"
+
+
+class _AdaFaceFunction(torch.autograd.Function):
+    """AdaFace logits (lafs_hip.h, lafs_margin_softmax_ce_ada_bf16) on the eager module path: the margins come from
+    lafs_adaface_margins, torch element-wise operations form the logits, as _CosFaceFunction does.  The margins are detached: no
+    gradient flows through the norm statistics.  (The training engine fuses margin + softmax + CE: lafs_margin_softmax_ce_ada_bf16.)"""
+
+    @staticmethod
+    def forward(ctx, x, weight, label, state, s, m, h, t_alpha, update):
+        B, C = x.shape[0], weight.shape[0]
+        cos, saved = _cosine_fwd(x, weight)
+        rm = torch.empty(B, 2, device=x.device, dtype=f32)
+        call("lafs_adaface_margins", _p(saved[4]), B, _p(state), t_alpha, h, m, int(update), _p(rm))
+        tgt = _dense_label(label, B, C, x.device) > 0
+        one, eps = torch.tensor(1.0, dtype=f32), torch.tensor(1e-3, dtype=f32)        # the kernels' fp32 thresholds
+        lo, hi, pi_hi = float(eps - one), float(one - eps), float(torch.tensor(math.pi, dtype=f32) - eps)
+        cc = cos.clamp(lo, hi)
+        th = torch.acos(cc)
+        tm = th + rm[:, :1]
+        z = s * torch.where(tgt, torch.cos(tm.clamp(float(eps), pi_hi)) - rm[:, 1:], cc)
+        live = (cos >= lo) & (cos <= hi)
+        dz = torch.where(tgt, torch.where((tm >= float(eps)) & (tm <= pi_hi), torch.sin(tm) / torch.sin(th), torch.zeros_like(cos)),
+                         torch.ones_like(cos))
+        ctx.save_for_backward(*saved, s * dz * live)
+        return z
+
+    @staticmethod
+    def backward(ctx, dout):
+        dx, dw = _cosine_bwd(ctx.saved_tensors[:-1], dout * ctx.saved_tensors[-1])
+        return dx, dw, None, None, None, None, None, None, None
+
+
+class AdaFace(nn.Module):
+    """AdaFace margin head (Kim, Jain, Liu, CVPR 2022; PARITY UNPINNED: the reference names the head, train_largescale.py:820, and ships
+    no class): the margin adapts per sample to the embedding's norm, the image-quality proxy.  `weight` has CosFace's name, layout and
+    initialisation; `batch_mean` / `batch_std` (f32 [1] buffers, initially 20 and 100) are the running norm statistics, updated in
+    training mode only.  ``forward(input, label)``: label is a class-index vector or a dense soft target (every class of positive
+    weight carries the full margin)."""
+
+    def __init__(self, in_features, out_features, device_id, s=64.0, m=0.4, h=0.333, t_alpha=0.01):
+        super().__init__()
+        if device_id is not None:
+            raise NotImplementedError("device_id model parallelism is not part of the hot path (always None in the reference)")
+        if in_features % 64:
+            raise NotImplementedError("in_features must be a multiple of 64 for the MFMA GEMM")
+        self.in_features, self.out_features, self.device_id = in_features, out_features, device_id
+        self.s, self.m, self.h, self.t_alpha, self.eps = s, m, h, t_alpha, 1e-3
+        self.weight = nn.Parameter(torch.empty(out_features, in_features))
+        nn.init.xavier_uniform_(self.weight)
+        self.register_buffer("batch_mean", torch.full((1,), 20.0))
+        self.register_buffer("batch_std", torch.full((1,), 100.0))
+
+    def state_storage(self):
+        """f32 [2] = (batch_mean, batch_std) on the weight's device, the `state` operand of lafs_adaface_margins.  The two buffers
+        are made views of it (once per device move), so state_dict() always holds the values the kernel wrote last."""
+        st = getattr(self, "_state", None)
+        dev = self.weight.device
+        if (st is None or st.device != dev or self.batch_mean.data_ptr() != st.data_ptr()
+                or self.batch_std.data_ptr() != st.data_ptr() + 4):
+            st = torch.cat([self.batch_mean.detach().to(dev, f32), self.batch_std.detach().to(dev, f32)])
+            self.batch_mean, self.batch_std = st[0:1], st[1:2]
+            object.__setattr__(self, "_state", st)
+        return st
+
+    def forward(self, input, label):
+        return _AdaFaceFunction.apply(input, self.weight, label, self.state_storage(), float(self.s), float(self.m), float(self.h),
+                                      float(self.t_alpha), self.training)
+
+    def __repr__(self):
+        return (f"{self.__class__.__name__}(in_features = {self.in_features}, out_features = {self.out_features}, s = {self.s}, "
+                f"m = {self.m}, h = {self.h}, t_alpha = {self.t_alpha})")
 
 
 # ------------------------------------------------------------------------------------------------- Part-fViT
@@ -214,6 +300,8 @@ class ViT_face_landmark_patch8(nn.Module):
             pass
         elif loss_type == 'CosFace':
             self.loss = CosFace(in_features=dim, out_features=num_class, device_id=GPU_ID, m=0.4)
+        elif loss_type == 'AdaFace':
+            self.loss = AdaFace(in_features=dim, out_features=num_class, device_id=GPU_ID, m=0.4)
         else:
             raise NotImplementedError(f"loss_type {loss_type!r}: only 'CosFace' and 'None' exist in the reference")
         self.theta = 0
@@ -505,6 +593,8 @@ class ViTs_face_overlap(nn.Module):
             pass
         elif loss_type == 'CosFace':
             self.loss = CosFace(in_features=dim, out_features=num_class, device_id=GPU_ID)
+        elif loss_type == 'AdaFace':
+            self.loss = AdaFace(in_features=dim, out_features=num_class, device_id=GPU_ID)
         else:
             raise NotImplementedError(f"loss_type {loss_type!r}: only 'CosFace' and 'None' exist in the reference")
         self._arena, self._spec, self._hook = None, None, None

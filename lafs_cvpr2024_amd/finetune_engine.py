@@ -36,7 +36,7 @@ import torch
 import torch.distributed as dist
 
 from . import _lib, functional as Fn, ops
-from .face_pre_pro.ViT_face import ViT_face_landmark_patch8, ViTs_face_overlap
+from .face_pre_pro.ViT_face import AdaFace, ViT_face_landmark_patch8, ViTs_face_overlap
 from .distributed import FlatReducer
 from .ops import _p, call
 from .utils import PinnedRing, capture_stretches
@@ -61,8 +61,11 @@ class FinetuneEngine:
     def __init__(self, backbone: ViT_face_landmark_patch8, batch_size, acc_step=3, mixup_alpha=0.2, mixup_prob=0.1,
                  s=64.0, m=0.4, margin_type=0, image_size=112, device=None, sharded_head=None, use_graph=None,
                  cutmix_alpha=0.0, cutmix_minmax=None, switch_prob=0.5, mix_mode="batch", label_smoothing=0.0,
-                 landmark_teacher=None, keep_land=False):
-        """margin_type 0 = CosFace (the reference), 1 = ArcFace (parity unpinned), on the dense `backbone.loss.weight` head;
+                 landmark_teacher=None, keep_land=False, ada_h=0.333, ada_t_alpha=0.01):
+        """margin_type 0 = CosFace (the reference), 1 = ArcFace (parity unpinned), on the dense `backbone.loss.weight` head; 2 = AdaFace
+        (parity unpinned; `backbone.loss` must be an AdaFace, m = 0.4): lafs_adaface_margins forms a margin pair per row from the
+        embedding norms behind lafs_l2norm_fwd and moves the module's `batch_mean` / `batch_std` buffers -- whose storage it is handed --
+        once per training micro-step (ada_h: the norm-to-margin slope, ada_t_alpha: the statistics' EMA rate); dense head only;
         `sharded_head` (a partial_fc.PartialFC) replaces it by the class-sharded head (CosFace: mixup targets as on the dense head).
         use_graph: None = capture the micro-step whenever it is capturable (single rank, dense head; LAFS_FT_GRAPH=0 disables).
         cutmix_alpha / cutmix_minmax / switch_prob / mix_mode / label_smoothing: util.mixup_my.Mixup's arguments of the same meaning
@@ -81,6 +84,12 @@ class FinetuneEngine:
         if label_smoothing > 0.0 and sharded_head is not None:
             raise _lib.LafsHipError("label smoothing on the class-sharded head is not supported (a smoothed target over a sampled class "
                                     "subset is not defined here): use the dense CosFace head")
+        if margin_type not in (0, 1, 2):
+            raise _lib.LafsHipError("margin_type must be 0 (CosFace), 1 (ArcFace) or 2 (AdaFace)")
+        if margin_type == 2 and sharded_head is not None:
+            raise _lib.LafsHipError("AdaFace (margin_type 2) runs on the dense head: its class-sharded form is not built")
+        if label_smoothing > 0.0 and margin_type == 2:
+            raise _lib.LafsHipError("label smoothing needs the CosFace margin: AdaFace has no margin for a dense target")
         if label_smoothing > 0.0 and margin_type != 0:
             raise _lib.LafsHipError("label smoothing needs the CosFace margin: ArcFace has no margin for a dense target")
         if keep_land and landmark_teacher is None:
@@ -100,6 +109,9 @@ class FinetuneEngine:
         if not isinstance(backbone, (ViT_face_landmark_patch8, ViTs_face_overlap)) or (sharded_head is None and not hasattr(backbone, "loss")):
             raise _lib.LafsHipError("FinetuneEngine drives ViT_face_landmark_patch8 or ViTs_face_overlap with loss_type='CosFace', or "
                                     "either of them with a sharded head")
+        if sharded_head is None and (margin_type == 2) != isinstance(backbone.loss, AdaFace):
+            raise _lib.LafsHipError("margin_type 2 and a backbone built with loss_type='AdaFace' go together: the engine updates that "
+                                    f"module's batch_mean / batch_std (margin_type {margin_type}, loss {type(backbone.loss).__name__})")
         if batch_size % 8:
             raise _lib.LafsHipError("FinetuneEngine needs a batch size that is a multiple of 8 (16-byte rows in the class-gradient GEMM)")
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
@@ -133,6 +145,9 @@ class FinetuneEngine:
             self.arena.refresh_shadows()
             self.sync_buffers()
         self.head = sharded_head
+        # AdaFace: the kernel's `state` operand IS the storage of loss.batch_mean / loss.batch_std, so a state_dict holds the live values
+        self.ada_h, self.ada_t_alpha = float(ada_h), float(ada_t_alpha)
+        self.ada_state = backbone.loss.state_storage() if margin_type == 2 else None
         self.C = backbone.loss.out_features if sharded_head is None else 8
         self.Cpad = (self.C + 127) // 128 * 128
         self.D = backbone.dim
@@ -201,6 +216,7 @@ class FinetuneEngine:
             self.xn = torch.empty(B, D, device=dev, dtype=bf16)
             self.xn_t = torch.empty(D, B, device=dev, dtype=bf16)
             self.inv_x = torch.empty(B, device=dev, dtype=f32)
+            self.row_margin = torch.empty(B, 2, device=dev, dtype=f32) if margin_type == 2 else None      # AdaFace (g_ang, g_add)
             self.dxn = torch.empty(B, D, device=dev, dtype=f32)
             self.dxn_ws = ops.wgrad_workspace(self.Cpad, B, D, dev)                 # d(emb_n): reduction over the classes
             self.dwn_ws = None if B % 32 == 0 else ops.wgrad_workspace(B, self.Cpad, D, dev)
@@ -421,8 +437,8 @@ class FinetuneEngine:
         """One eager micro-step body on a side stream BEFORE the first capture (as LafsPretrainEngine._capture does): code objects
         are loaded, kernel attributes set and the per-step workspaces (`_ws`, `dth`) allocated by the ordinary allocator instead of
         from inside a stream capture / the graph's private pool.  The state the body mutates -- gradients, the loss, the landmark
-        CNN's BatchNorm running statistics and loss-scale state, the running statistics of fViT's head -- is snapshotted and put back
-        (a first step counted twice would be a 10 % error of the statistics at momentum 0.1)."""
+        CNN's BatchNorm running statistics and loss-scale state, the running statistics of fViT's head, AdaFace's norm statistics -- is
+        snapshotted and put back (a first step counted twice would be a 10 % error of the statistics at momentum 0.1)."""
         a, cnn = self.arena, self.cnn
         bn = []
         if self.fvit:
@@ -431,6 +447,8 @@ class FinetuneEngine:
         if cnn is not None:
             bn += [t for s in [cnn.stem["bn"]] + [L[k] for L in cnn.blocks for k in ("bn1", "bn2", "bn3")] for t in (s["rm"], s["rv"]) if t is not None]
             bn.append(cnn.gscale)
+        if self.ada_state is not None:
+            bn.append(self.ada_state)
         saved = [t.clone() for t in [a.grad, self.loss] + bn]
         n_fwd = cnn.n_forward if cnn is not None else 0
         cur = torch.cuda.current_stream()
@@ -523,12 +541,19 @@ class FinetuneEngine:
             return
         # ---- margin head (face_pre_pro/ViT_face.py:49-89 + timm SoftTargetCrossEntropy, train_largescale.py:820)
         call("lafs_l2norm_fwd", _p(emb), D, _p(self.xn), D, _p(self.inv_x), B, D)
+        if self.margin_type == 2:                        # AdaFace: this batch's norms -> running statistics (training mode) -> a margin pair per row
+            call("lafs_adaface_margins", _p(self.inv_x), B, _p(self.ada_state), self.ada_t_alpha, self.ada_h, self.m, 1 if m.training else 0,
+                 _p(self.row_margin))
         call("lafs_weightnorm_fwd", _p(a.view(a.master, self.wname)), _p(self.ones), self.C, self.Cpad, D, _p(self.wn), None, self.Cpad,
              _p(self.inv_w))
         ops.gemm_nt(self.xn, self.wn, _lib.EPI_F32, out=self.cos, n_cols=self.Cpad)
         # margin + softmax + soft-target CE; d/dcos leaves as bf16 (the operand of the two class-gradient GEMMs); the mixup partner of
         # row b is row B-1-b, lambda comes from device memory
-        if self.mix_rows:                                # a lambda per row (read from the parameter table) and label smoothing
+        if self.margin_type == 2:                        # one entry for both branches: the batch's lambda at stride 0, or the table's per row
+            lam_rows, stride = (self.mix_tab, _lib.MIX_WORDS) if self.mix_rows else (hp[_lib.HP_MIX_LAM:], 0)
+            call("lafs_margin_softmax_ce_ada_bf16", _p(self.cos), self.Cpad, B, self.C, _p(self.y1), None, _p(lam_rows), stride,
+                 _p(self.row_margin), self.s, 1.0 / self.acc_step, _p(self.dcos), self.Cpad, _p(self.loss), _p(self.row_ws), _p(self.part_ws))
+        elif self.mix_rows:                              # a lambda per row (read from the parameter table) and label smoothing
             call("lafs_margin_softmax_ce_mix_bf16", _p(self.cos), self.Cpad, B, self.C, _p(self.y1), None, _p(self.mix_tab), _lib.MIX_WORDS,
                  self.label_smoothing, self.s, self.m, self.margin_type, 1.0 / self.acc_step, _p(self.dcos), self.Cpad, _p(self.loss),
                  _p(self.row_ws), _p(self.part_ws))

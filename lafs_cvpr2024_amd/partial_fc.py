@@ -102,6 +102,9 @@ class _Centres(torch.nn.Module):
 class PartialFC:
     def __init__(self, embedding_size, num_classes, batch_size, sample_rate=1.0, s=64.0, m=0.4, margin_type=0, device=None,
                  seed=0):
+        if margin_type not in (0, 1):
+            raise _lib.LafsHipError("PartialFC takes margin_type 0 (CosFace) or 1 (ArcFace): AdaFace's per-row margins (margin_type 2) "
+                                    "exist on the dense head only")
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.rank = dist.get_rank() if self.world > 1 else 0

@@ -1,7 +1,9 @@
-"""Supervised Part-fViT + CosFace / ArcFace / PartialFC fine-tuning loop (reference train_largescale.py:317-963) on the HIP
+"""Supervised Part-fViT + CosFace / ArcFace / AdaFace / PartialFC fine-tuning loop (reference train_largescale.py:317-963) on the HIP
 fine-tune engine.  Model configuration as the reference builds it (:432, 542-557): with_land=True (trainable MobileNetV3
 landmark branch), dropout = emb_dropout = 0.1, DropPath 0.1, CosFace(s=64, m=0.4) over all classes on every rank.
 `--head PartialFC` / `--head ArcFace` select the class-sharded head of config C5 (parity unpinned, see partial_fc.py).
+`--head AdaFace` (parity unpinned; Kim, Jain, Liu, CVPR 2022) trains the dense head with a margin per sample from the embedding's norm
+(`--adaface_h`, `--adaface_t_alpha`); the progress line then shows the running norm statistics (`ada_mean`, `ada_std`).
 
 Kept from the reference: flags that define the step (batch size, epochs, the lr rescale of :472
 `acc_step/480 * lr * sqrt(world*bs/336) * 336`, weight decay 0.1 on >= 2-D tensors (:618-627; `--weight-decay` is parsed by the
@@ -60,9 +62,12 @@ def get_args_parser():
     p.add_argument("--epochs", "-e", default=34, type=int)
     p.add_argument("--lr", default=1e-3, type=float, help="base rate before the reference's rescale (train_largescale.py:355,472)")
     p.add_argument("--weight_decay", default=0.1, type=float)
-    p.add_argument("--head", default="CosFace", type=str, choices=["CosFace", "PartialFC", "ArcFace"],
+    p.add_argument("--head", default="CosFace", type=str, choices=["CosFace", "PartialFC", "ArcFace", "AdaFace"],
                    help="CosFace: the reference's dense head; ArcFace: dense head with the additive angular margin (m=0.5); "
+                        "AdaFace: dense head whose margin adapts per sample to the embedding's norm (m=0.4); "
                         "PartialFC: class centres sharded over the ranks (config C5)")
+    p.add_argument("--adaface_h", default=0.333, type=float, help="AdaFace: slope from the normalised embedding norm to the margin")
+    p.add_argument("--adaface_t_alpha", default=0.01, type=float, help="AdaFace: EMA rate of the running norm mean / std")
     p.add_argument("--partial_margin", default="CosFace", type=str, choices=["CosFace", "ArcFace"])
     p.add_argument("--sample_rate", default=1.0, type=float, help="PartialFC negative-class sampling rate")
     p.add_argument("--with_land", default=True, type=utils.bool_flag, help="trainable landmark branch (reference :432)")
@@ -218,13 +223,14 @@ def build_backbone(args):
     """The fine-tune model of the reference (:432, 542-557) for these flags."""
     check_net_args(args)
     sharded = args.head == "PartialFC"
+    loss_type = "None" if sharded else "AdaFace" if args.head == "AdaFace" else "CosFace"
     if args.net == "VITs":              # the released fViT configuration; --with_land is not read
-        return ViTs_face_overlap(loss_type="None" if sharded else "CosFace", GPU_ID=None, num_class=args.num_class, image_size=112,
+        return ViTs_face_overlap(loss_type=loss_type, GPU_ID=None, num_class=args.num_class, image_size=112,
                                  patch_size=8, ac_patch_size=12, pad=4, dim=768, depth=12, heads=11, mlp_dim=2048,
                                  dropout=args.dropout, emb_dropout=args.dropout, drop_path_rate=args.drop_path)
     # the dense ArcFace head lives in the same `loss.weight` tensor as CosFace (the reference names an ArcFace class it never
     # defines, ViT_face.py:654-655); the margin is applied by the fused kernel
-    return ViT_face_landmark_patch8(loss_type="None" if sharded else "CosFace", GPU_ID=None, num_class=args.num_class,
+    return ViT_face_landmark_patch8(loss_type=loss_type, GPU_ID=None, num_class=args.num_class,
                                     image_size=112, patch_size=8, dim=768, depth=12, heads=11, mlp_dim=2048,
                                     dropout=args.dropout, emb_dropout=args.dropout, with_land=args.with_land,
                                     drop_path_rate=args.drop_path)
@@ -403,6 +409,7 @@ def main(args):
     world = utils.get_world_size()
     sharded = args.head == "PartialFC"
     arc = (args.partial_margin if sharded else args.head) == "ArcFace"
+    ada = args.head == "AdaFace"
     backbone = build_backbone(args)
     if args.model_dir:
         load_ssl_teacher(backbone, args.model_dir)
@@ -416,7 +423,8 @@ def main(args):
                          margin_type=1 if arc else 0, device=device, seed=cfg["SEED"])
     engine = FinetuneEngine(backbone, args.batch_size, acc_step=cfg["acc_step"], mixup_alpha=args.mixup,
                             mixup_prob=args.mixup_prob if mixing_active(args) else 0.0,
-                            s=64.0, m=0.5 if arc else 0.4, margin_type=1 if arc else 0, device=device, sharded_head=head,
+                            s=64.0, m=0.5 if arc else 0.4, margin_type=2 if ada else 1 if arc else 0, device=device, sharded_head=head,
+                            ada_h=args.adaface_h, ada_t_alpha=args.adaface_t_alpha,
                             cutmix_alpha=args.cutmix, cutmix_minmax=args.cutmix_minmax, switch_prob=args.mixup_switch_prob,
                             mix_mode=args.mixup_mode, label_smoothing=args.smoothing, landmark_teacher=teacher, keep_land=args.keep_land)
     # train_largescale.py:472:  lr = acc_step / 480 * lr * sqrt(world * BATCH_SIZE / 336) * 336
@@ -477,6 +485,9 @@ def main(args):
             loss = engine.step(x, y, lr=lr, weight_decay=args.weight_decay, land_weight=land_w)
             if it % 50 == 0:
                 land = f" loss_land {float(engine.loss_land.item()):.6f}" if args.keep_land else ""      # (reference :914-915)
+                if ada:                 # the running norm statistics, read where loss.item() synchronises anyway
+                    mean_std = engine.ada_state.tolist()
+                    land += f" ada_mean {mean_std[0]:.4f} ada_std {mean_std[1]:.4f}"
                 print(f"Epoch {epoch} it {it}/{n_it} loss {float(loss.item()):.4f} lr {lr:.3e} "
                       f"{(epoch * n_it + it + 1) * args.batch_size * world / (time.time() - t0):.1f} samples/s{land}")
             if engine.micro % cfg["acc_step"] == 0:      # an optimizer step ran (reference :893)

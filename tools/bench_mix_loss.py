@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
-"""Time lafs_margin_softmax_ce_mix_bf16 (lambda per row, label smoothing) against lafs_margin_softmax_ce_bf16 at the fine-tune
-head's shape (B = 128, C = 205 990): both stream the fp32 logits twice and write the bf16 gradient once.  Interleaved rounds in one
+"""Time lafs_margin_softmax_ce_mix_bf16 (lambda per row, label smoothing) and lafs_margin_softmax_ce_ada_bf16 (AdaFace: a margin pair
+per row, clamped cosines) against lafs_margin_softmax_ce_bf16 at the fine-tune
+head's shape (B = 128, C = 205 990): all stream the fp32 logits twice and write the bf16 gradient once.  Interleaved rounds in one
 process; per variant the median over rounds of the mean launch time, and the existing kernel's own round-to-round spread.  GPU box only.
 usage: python tools/bench_mix_loss.py [--batch 128] [--classes 205990] [--rounds 9] [--iters 40]"""
 import argparse
@@ -41,7 +42,17 @@ def new(eps):
                         Cpad, _p(loss), _p(rows), _p(part))
 
 
-variants = {"margin_softmax_ce_bf16": old, "mix_bf16 eps=0": new(0.0), "mix_bf16 eps=0.1": new(0.1)}
+# AdaFace: margins of rows whose quality proxy k runs over [-1, 1] (g_ang = -m k, g_add = m + m k), the batch's lambda at stride 0
+k = torch.linspace(-1.0, 1.0, B, device=dev)
+row_margin = torch.stack([-0.4 * k, 0.4 + 0.4 * k], 1).contiguous()
+
+
+def ada():
+    call("lafs_margin_softmax_ce_ada_bf16", _p(cos), Cpad, B, C, _p(y1), None, _p(lam1), 0, _p(row_margin), 64.0, 1.0, _p(dcos), Cpad, _p(loss),
+         _p(rows), _p(part))
+
+
+variants = {"margin_softmax_ce_bf16": old, "mix_bf16 eps=0": new(0.0), "mix_bf16 eps=0.1": new(0.1), "ada_bf16": ada}
 times = {k: [] for k in variants}
 for f in variants.values():
     for _ in range(10):

@@ -1098,6 +1098,26 @@ int lafs_knn_search(const float* bank, int ldb, int64_t n_bank, int64_t bank_pos
 int lafs_knn_vote(const float* top_score, const int32_t* top_idx, int n_query, int k, const int32_t* bank_label, int64_t n_label,
                   const int32_t* ks, int n_ks, float temperature, int32_t* pred, float* vote, hipStream_t stream);
 
+/* Softmax cross-entropy of plain logits with the rank of the target and, optionally, the bf16 gradient (csrc/linear_probe.hip): the
+ * loss of the linear probe on frozen features, the trained half of DINO's evaluation pair (eval_linear.py; no counterpart in the
+ * reference).  logits f32 [B, ld], READ-ONLY, of which the first C columns are classes; y i32 [B] on the device.  For a row with
+ * 0 <= y[b] < C, z = logits[b]:
+ *   row_loss[b] = logsumexp_j(z_j) - z_y      the row's maximum subtracted inside every exponential, sums in fp32;
+ *   row_rank[b] = #{ j < C : z_j > z_y or (z_j == z_y and j < y) }: top-1 is rank == 0, top-5 rank < 5, nothing is sorted, and the tie
+ *                 rule makes the rank a function of the logits alone (comparisons of f32 values: the rank is exact);
+ *   dlogits(bf16)[b, j] = bf16(grad_scale (softmax(z)_j - [j == y]))   for j < C, zero for C <= j < lddl: the buffer is the bf16
+ *                 operand of lafs_gemm_tn_acc as it stands.  dlogits_bf16 == NULL: no gradient is formed and nothing of it written.
+ * y[b] == -1: the row has no target (the padding of a short last batch): loss 0, rank -1, a zero gradient row.  Any other label outside
+ * [0, C) cannot be caught on the host: loss NaN, rank -2, a zero gradient row, nothing written outside the row.
+ * 1 <= B <= 65535, 1 <= C <= ld; lddl >= C, lddl % 8 == 0 and dlogits 16-byte aligned.  Rows that start on a 16-byte boundary
+ * (ld % 4 == 0 and an aligned base) are read 16 bytes at a time throughout; others take a scalar head up to the boundary and a scalar
+ * tail.  (row, chunk of 4096 columns) partials, a per-row fold, then the (row, chunk) gradient pass: every sum in a fixed order, no
+ * atomics, the same bits on every call.  Bytes per call: 4 B C without the gradient, 8 B C + 2 B lddl with it (the gradient pass
+ * reads the logits a second time).  ws: lafs_softmax_ce_rank_workspace_bytes(B, C) bytes, 4-byte aligned, contents irrelevant on entry. */
+int64_t lafs_softmax_ce_rank_workspace_bytes(int B, int C);
+int lafs_softmax_ce_rank(const float* logits, int ld, int B, int C, const int32_t* y, float grad_scale, void* dlogits_bf16, int lddl,
+                         float* row_loss, int32_t* row_rank, float* ws, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------
  * TRAINABLE landmark CNN of the fine-tune step (csrc/landmark_train.hip; reference face_pre_pro/mobilenet.py:224-313 trained through
  * ViT_face.py:679-711 by train_largescale.py:785-891).  Activations are NHWC bf16 [N H W, ld] matrices, ld = channel count padded

@@ -670,3 +670,39 @@ def knn_vote(top_score, top_idx, bank_label, ks, temperature=0.07):
     call("lafs_knn_vote", _p(top_score), _p(top_idx), Q, k, _p(bank_label), bank_label.numel(), (C.c_int32 * len(ks))(*ks), len(ks),
          float(temperature), _p(pred), _p(vote))
     return pred, vote
+
+
+def softmax_ce_rank_workspace(B, n_classes, device):
+    n = int(_lib.lib().lafs_softmax_ce_rank_workspace_bytes(int(B), int(n_classes)))
+    if n < 0:
+        raise _lib.LafsHipError("lafs_softmax_ce_rank_workspace_bytes: bad shape")
+    return torch.empty(n // 4, device=device, dtype=torch.float32)
+
+
+def softmax_ce_rank(logits, y, n_classes=None, grad_scale=1.0, dlogits=None, row_loss=None, row_rank=None, ws=None):
+    """lafs_softmax_ce_rank: logits f32 [B, >= C] (read-only) and y i32 [B] -> (row_loss f32 [B], row_rank i32 [B]) and, when
+    dlogits (bf16 [B, lddl], lddl % 8 == 0) is given, dlogits = bf16(grad_scale (softmax - one-hot)) with zero pad columns.  y == -1:
+    no target (loss 0, rank -1, zero gradient row); any other label outside [0, C): loss NaN, rank -2."""
+    _chk(logits, torch.float32, "logits"); _chk(y, torch.int32, "y"); _chk(dlogits, bf16, "dlogits")
+    _chk(row_loss, torch.float32, "row_loss"); _chk(row_rank, torch.int32, "row_rank"); _chk(ws, torch.float32, "ws")
+    if logits.dim() != 2 or y.dim() != 1 or y.numel() != logits.shape[0] or not y.is_contiguous():
+        raise _lib.LafsHipError("softmax_ce_rank: logits [B, C] and a contiguous y [B] expected")
+    B = logits.shape[0]
+    n = logits.shape[1] if n_classes is None else int(n_classes)
+    if dlogits is not None and (dlogits.dim() != 2 or dlogits.shape[0] != B):
+        raise _lib.LafsHipError("softmax_ce_rank: dlogits must be [B, lddl]")
+    if row_loss is None:
+        row_loss = torch.empty(B, device=logits.device, dtype=torch.float32)
+    if row_rank is None:
+        row_rank = torch.empty(B, device=logits.device, dtype=torch.int32)
+    for t in (row_loss, row_rank):
+        if t.dim() != 1 or t.numel() != B or not t.is_contiguous():
+            raise _lib.LafsHipError("softmax_ce_rank: row_loss and row_rank must be contiguous [B]")
+    need = int(_lib.lib().lafs_softmax_ce_rank_workspace_bytes(B, n))
+    if ws is None:
+        ws = softmax_ce_rank_workspace(B, n, logits.device)
+    elif ws.numel() * 4 < need or not ws.is_contiguous():
+        raise _lib.LafsHipError(f"softmax_ce_rank: the workspace holds {ws.numel() * 4} bytes, {need} are needed")
+    call("lafs_softmax_ce_rank", _p(logits), _ld(logits), B, n, _p(y), float(grad_scale), _p(dlogits), 0 if dlogits is None else _ld(dlogits),
+         _p(row_loss), _p(row_rank), _p(ws))
+    return row_loss, row_rank

@@ -1118,6 +1118,31 @@ int64_t lafs_softmax_ce_rank_workspace_bytes(int B, int C);
 int lafs_softmax_ce_rank(const float* logits, int ld, int B, int C, const int32_t* y, float grad_scale, void* dlogits_bf16, int lddl,
                          float* row_loss, int32_t* row_rank, float* ws, hipStream_t stream);
 
+/* KoLeo regulariser (csrc/koleo.hip): the Kozachenko-Leonenko differential-entropy term DINOv2 adds to the DINO loss, which pushes
+ * every row of a batch away from its nearest neighbour on the sphere.  No counterpart in the reference; restated from DINOv2's
+ * published KoLeoLoss (PARITY UNPINNED).  x f32 [n_groups * rows, ldx], READ-ONLY, of which the first D columns are features; group g
+ * owns rows [g rows, (g + 1) rows) of x and of dx, and neighbours are never searched across groups.  For one group of n = rows rows:
+ *   xh_i = x_i / max(||x_i||, eps)                                    F.normalize(x, p=2, dim=-1, eps=eps)
+ *   I(i) = argmax over j != i of <xh_i, xh_j>                         the lowest j among exactly equal values; constant for the gradient
+ *   v_i  = xh_i - xh_I(i) + eps,  d_i = ||v_i||                       nn.PairwiseDistance(2, eps): eps added to every element
+ *   L    = -(1 / n) sum_i log(d_i + eps)
+ *   c_i  = -(1 / n) v_i / (d_i (d_i + eps)),  g_j = c_j - sum over {i : I(i) = j} of c_i, in ascending i
+ *   dL/dx_j = (g_j - xh_j <xh_j, g_j>) / ||x_j|| where ||x_j|| >= eps, g_j / eps below (the gradient of the clamp)
+ * (The search ranks row i's candidates by <x_i, x_j> / max(||x_j||, eps): the cosine times ||x_i||, constant over j.  A row is never its
+ * own candidate.)  Exact duplicates are legal: then v_i = eps in every element, d_i = eps sqrt(D), loss and gradient large but finite.
+ * Outputs: loss[g] = L of group g, unscaled;  nn i32 [n_groups * rows] (may be NULL) = I(i) as a row index INSIDE the group;
+ * dx (may be NULL: forward only) [n_groups * rows, lddx]: dx[r, :D] = (accumulate ? dx[r, :D] : 0) + grad_scale dL_g/dx_r -- columns
+ * >= D and rows outside the call are not touched.  All arithmetic is fp32 and no 16-bit value is stored.  Every sum over D has one
+ * order for every row, nothing is an atomic (the scatter of c_i is a gather over the group's neighbour list): identical rows give
+ * exactly equal scores, and two calls on equal inputs give equal bits.  Two launches.
+ * Accepted: n_groups >= 1, 2 <= rows <= 1024, 4 <= D <= 1024, D % 4 == 0, ldx, lddx >= D and % 4 == 0, eps > 0, x, dx and ws 16-byte
+ * aligned; anything else (rows == 1 included) returns a negative code before any launch.  ws: lafs_koleo_workspace_bytes(n_groups,
+ * rows, D) bytes (-1 for a shape that is not accepted), contents irrelevant on entry. */
+int64_t lafs_koleo_workspace_bytes(int n_groups, int rows, int D);
+int lafs_koleo_fwd_bwd(const float* x, int ldx, int n_groups, int rows, int D, float eps, float grad_scale,
+                       float* loss /* [n_groups], written */, int32_t* nn /* [n_groups*rows], written; may be NULL */,
+                       float* dx /* may be NULL: forward only */, int lddx, int accumulate, void* ws, hipStream_t stream);
+
 /* ------------------------------------------------------------------------------------------------------------------------
  * TRAINABLE landmark CNN of the fine-tune step (csrc/landmark_train.hip; reference face_pre_pro/mobilenet.py:224-313 trained through
  * ViT_face.py:679-711 by train_largescale.py:785-891).  Activations are NHWC bf16 [N H W, ld] matrices, ld = channel count padded

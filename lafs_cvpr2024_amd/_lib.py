@@ -210,6 +210,7 @@ _PROTOS = {
     "lafs_knn_search": [vp, i32, i64, i64, vp, i32, i32, i32, i32, vp, i32, i32, vp, vp, vp, C.c_size_t],
     "lafs_knn_vote": [vp, vp, i32, i32, vp, i64, C.POINTER(C.c_int32), i32, f32, vp, vp],
     "lafs_softmax_ce_rank": [vp, i32, i32, i32, vp, f32, vp, i32, vp, vp, vp],
+    "lafs_koleo_fwd_bwd": [vp, i32, i32, i32, i32, f32, f32, vp, vp, vp, i32, i32, vp],
     "lafs_landmark_theta": [vp, i32, i32, vp, f32, vp, i32, vp],
     "lafs_mixup_normalize": [vp, vp, i32, i32, f32, vp],
     "lafs_margin_softmax_ce_bf16": [vp, i32, i32, i32, vp, vp, f32, vp, f32, f32, i32, f32, vp, i32, vp, vp, vp],
@@ -265,6 +266,7 @@ _NO_STREAM = {
     "lafs_ijb_search_workspace": ([i32, i32, i32], i64),
     "lafs_knn_workspace": ([i32, i64, i32, i32], i64),
     "lafs_softmax_ce_rank_workspace_bytes": ([i32, i32], i64),
+    "lafs_koleo_workspace_bytes": ([i32, i32, i32], i64),
     "lafs_wgrad_workspace_bytes": ([i32, i32, i32], i64),
     "lafs_jpeg_workspace_bytes": ([i32, i32, i32], i64),
     "lafs_wgrad_group_workspace_bytes": ([C.POINTER(WgradItem), i32, i32, i32], i64),

@@ -75,7 +75,7 @@ def _interp_matrix(grid_src, grid_dst, device):
 class LafsPretrainEngine:
     def __init__(self, student, teacher, dino_loss, batch_size, n_local=8, global_size=112, local_size=48,
                  clip_grad=3.0, freeze_last_layer=1, use_graph=True, device=None, grad_slices=4, sync_bn=False,
-                 optimizer='adamw'):
+                 optimizer='adamw', koleo_weight=0.0):
         self.device = torch.device(device if device is not None else ("cuda", torch.cuda.current_device()))
         self.student, self.teacher, self.dino_loss = student, teacher, dino_loss
         self.B, self.n_local, self.ncrops = batch_size, n_local, 2 + n_local
@@ -221,6 +221,21 @@ class LafsPretrainEngine:
                         if self.fused_head else None)
         self.dlogits = torch.zeros(self.ncrops * B, self.Kpad, device=dev, dtype=bf16)
         self.loss = torch.zeros(1, device=dev, dtype=f32)
+        # KoLeo regulariser of DINOv2 (csrc/koleo.hip; nothing of it in the reference, PARITY UNPINNED) on the backbone's cls features of
+        # the student's two global crops, one group of B rows per crop: loss = dino_loss + koleo_weight (L_0 + L_1).  Its gradient is
+        # added to dfeat between the head backward and the trunk backward (_forward).  The neighbours are searched inside this rank's
+        # batch, as DINOv2 searches them, so no collective is added.  Weight 0: no buffer, no launch -- the step of an engine without it.
+        self.koleo_weight = float(koleo_weight)
+        if not self.koleo_weight >= 0.0:
+            raise _lib.LafsHipError(f"koleo_weight {koleo_weight!r}: a weight >= 0 (0 = off; DINOv2 uses 0.1)")
+        self.koleo = None
+        if self.koleo_weight > 0:
+            if B < 2:
+                raise _lib.LafsHipError("koleo_weight > 0 needs batch_size >= 2: every row's nearest neighbour is another row of its crop")
+            self.koleo = torch.zeros(2, device=dev, dtype=f32)
+            self.koleo_nn = torch.zeros(2 * B, device=dev, dtype=torch.int32)
+            self.koleo_ws = ops.koleo_workspace(2, B, D, dev)
+        self._feat_s = None
         self.loss_ws = torch.empty(_lib.lib().lafs_dino_loss_workspace(self.ncrops, B, self.K), device=dev, dtype=f32)
         self.colsum = torch.zeros(self.K, device=dev, dtype=f32)
         self.in_global_all = torch.zeros(2 * B, 3, global_size, global_size, device=dev)
@@ -315,6 +330,13 @@ class LafsPretrainEngine:
         st = self._head_states[which]
         return ops.gemm_nt(st.zn, st.wn, _lib.EPI_F32, n_cols=st.Kpad)
 
+    @property
+    def koleo_value(self):
+        """koleo_weight (L_0 + L_1) of the last step as a device scalar: what the step added to the DINO loss in self.loss."""
+        if self.koleo is None:
+            raise _lib.LafsHipError("koleo_value: the engine was built with koleo_weight 0")
+        return self.koleo_weight * self.koleo.sum()
+
     logits_s = property(lambda self: self._logits(0))
     logits_t = property(lambda self: self._logits(1))
 
@@ -380,6 +402,7 @@ class LafsPretrainEngine:
             feat_s = Fn.vit_forward_sync_bn(self.sa, self.spec_s, st_v, self.bn_x.all(0), self.bn_total_s)
         if self.fvit and self.student.backbone.training:   # the reference's forward runs the head once per crop group (:1556-1569)
             self.bn_s.num_batches_tracked.add_(len(self.geom_s.groups))
+        self._feat_s = feat_s                          # what the head receives: the KoLeo term reads its first 2B rows
         return Fn.head_forward(self.sa, self.head_prefix_s, feat_s, self.K, save=True, logits=self._logits_s, skip_logits=self.fused_head)[1]
 
     def _forward(self):
@@ -416,6 +439,10 @@ class LafsPretrainEngine:
         st_h = self._student_head(feat_s, st_v)
         cur.wait_stream(side)
         dfeat = self._head_loss_backward(st_h, st_ht)
+        if self.koleo is not None:                     # + koleo_weight d(L_0 + L_1)/dfeat on the global crops' rows (packed first)
+            B = self.B
+            ops.koleo(self._feat_s[:2 * B], 2, B, grad_scale=self.koleo_weight, dx=dfeat[:2 * B], accumulate=True, loss=self.koleo,
+                      nn=self.koleo_nn, ws=self.koleo_ws)
         if self._bn_sums_live:                         # this rank's two sums of the BatchNorm backward
             Fn.vit_backward_bn_sums(sa, self.spec_s, st_v, dfeat, self.bn_x.sums)
         self._st = dict(vit=st_v, dfeat=dfeat)

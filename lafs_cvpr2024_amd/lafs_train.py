@@ -19,7 +19,9 @@ Differences from the reference, all forced by its own breakage or by scope (SURV
     --fvit_dropout); on more than one rank it needs --sync_bn true, the counterpart of the reference's SyncBatchNorm conversion
     (:362-364): the BatchNorm1d head then normalises every crop group with the statistics of all ranks' cls rows;
   * --optimizer picks the update rule of the engine's fused per-tensor-clip + update + EMA kernel: adamw (the reference's default),
-    sgd (torch.optim.SGD(lr=0, momentum=0.9), :402) or lars (utils.LARS, :404); momentum and LARS's eta are the reference's constants.
+    sgd (torch.optim.SGD(lr=0, momentum=0.9), :402) or lars (utils.LARS, :404); momentum and LARS's eta are the reference's constants;
+  * --koleo_weight w > 0 adds DINOv2's KoLeo regulariser, w (L_0 + L_1) on the backbone's cls features of the student's two global
+    crops (nothing of it in the reference; csrc/koleo.hip inside the captured step); `train_koleo` joins the epoch's log.txt line.
 """
 import argparse
 import datetime
@@ -71,6 +73,9 @@ def get_args_parser():
     p.add_argument('--min_lr', type=float, default=1e-6)
     p.add_argument('--optimizer', default='adamw', type=str, choices=['adamw', 'sgd', 'lars'],
                    help="Type of optimizer (reference :92-93): adamw for ViTs, sgd, or lars for convnets and large batches.")
+    p.add_argument('--koleo_weight', default=0.0, type=float,
+                   help="Weight of the KoLeo regulariser on the cls features of the student's global crops (0 = off; DINOv2 uses 0.1). "
+                        "Not in the reference.")
     p.add_argument('--drop_path_rate', type=float, default=0.1)
     p.add_argument('--mynet_dims', default='768,12,11,2048', type=str, help="dim,depth,heads,mlp_dim of --arch mynet (reference :300-335)")
     p.add_argument('--mynet_dropout', default=0.1, type=float, help="dropout = emb_dropout of --arch mynet (reference: 0.1)")
@@ -384,7 +389,7 @@ def train_lafs(args, dataset=None):
                          args.warmup_teacher_temp_epochs, args.epochs)
     engine = LafsPretrainEngine(student, teacher, dino_loss, args.batch_size_per_gpu, n_local=args.local_crops_number,
                                 clip_grad=args.clip_grad, freeze_last_layer=args.freeze_last_layer, use_graph=args.use_graph,
-                                device=device, sync_bn=args.sync_bn, optimizer=args.optimizer)
+                                device=device, sync_bn=args.sync_bn, optimizer=args.optimizer, koleo_weight=args.koleo_weight)
     print(f"Student and Teacher are built: they are both {args.arch} networks.")
 
     frontend = None
@@ -528,11 +533,15 @@ def train_one_epoch(engine, dino_loss, data_loader, lr_schedule, wd_schedule, mo
         if callable(after):
             after()                                         # front-end of the next batch, overlapping this step
         loss_acc += loss.view(1)
+        if engine.koleo is not None:                       # (--koleo_weight: the regulariser's share is not part of engine.loss)
+            loss_acc += engine.koleo_value
         if it % 20 == 0:                                   # the only host sync inside the epoch
             lv = float(loss.item())
             stop_if_poisoned(lv)
             stop_if_poisoned(float(loss_acc.item()))
             metric_logger.update(loss=lv)
+            if engine.koleo is not None:
+                metric_logger.update(koleo=float(engine.koleo_value.item()))
         metric_logger.update(lr=float(lr_schedule[it]))
         metric_logger.update(wd=float(wd_schedule[it]))
     stop_if_poisoned(float(loss_acc.item()))                # every step of the epoch was finite: the checkpoint may be written

@@ -706,3 +706,42 @@ def softmax_ce_rank(logits, y, n_classes=None, grad_scale=1.0, dlogits=None, row
     call("lafs_softmax_ce_rank", _p(logits), _ld(logits), B, n, _p(y), float(grad_scale), _p(dlogits), 0 if dlogits is None else _ld(dlogits),
          _p(row_loss), _p(row_rank), _p(ws))
     return row_loss, row_rank
+
+
+def koleo_workspace(n_groups, rows, D, device):
+    n = int(_lib.lib().lafs_koleo_workspace_bytes(int(n_groups), int(rows), int(D)))
+    if n < 0:
+        raise _lib.LafsHipError("lafs_koleo_workspace_bytes: bad shape (n_groups >= 1, 2 <= rows <= 1024, 4 <= D <= 1024, D % 4 == 0)")
+    return torch.empty(n // 4, device=device, dtype=torch.float32)
+
+
+def koleo(x, n_groups, rows, *, eps=1e-8, grad_scale=1.0, dx=None, accumulate=False, loss=None, nn=None, ws=None):
+    """lafs_koleo_fwd_bwd: the KoLeo regulariser of n_groups groups of `rows` rows each, x f32 [n_groups * rows, D] (read-only, row
+    stride % 4 == 0) -> (loss f32 [n_groups], unscaled; nn i32 [n_groups * rows], the neighbour of every row as an index inside its
+    group).  With dx (f32, the shape of x): dx = (dx if accumulate else 0) + grad_scale dL_g/dx.  With loss, nn, ws (and dx) passed
+    nothing is allocated: the call is capturable."""
+    _chk(x, torch.float32, "x"); _chk(dx, torch.float32, "dx"); _chk(loss, torch.float32, "loss"); _chk(nn, torch.int32, "nn")
+    _chk(ws, torch.float32, "ws")
+    n_groups, rows = int(n_groups), int(rows)
+    if x.dim() != 2 or x.shape[0] != n_groups * rows:
+        raise _lib.LafsHipError("koleo: x must be [n_groups * rows, D]")
+    R, D = x.shape
+    if dx is not None and (dx.dim() != 2 or tuple(dx.shape) != (R, D)):
+        raise _lib.LafsHipError("koleo: dx must have the shape of x")
+    need = int(_lib.lib().lafs_koleo_workspace_bytes(n_groups, rows, D))
+    if need < 0:
+        raise _lib.LafsHipError(f"koleo: {n_groups} groups of {rows} rows x {D} columns: n_groups >= 1, 2 <= rows <= 1024, 4 <= D <= 1024 and "
+                                "D % 4 == 0 are needed")
+    if loss is None:
+        loss = torch.empty(n_groups, device=x.device, dtype=torch.float32)
+    if nn is None:
+        nn = torch.empty(R, device=x.device, dtype=torch.int32)
+    if loss.dim() != 1 or loss.numel() != n_groups or not loss.is_contiguous() or nn.dim() != 1 or nn.numel() != R or not nn.is_contiguous():
+        raise _lib.LafsHipError("koleo: loss must be a contiguous [n_groups], nn a contiguous [n_groups * rows]")
+    if ws is None:
+        ws = koleo_workspace(n_groups, rows, D, x.device)
+    elif ws.numel() * 4 < need or not ws.is_contiguous():
+        raise _lib.LafsHipError(f"koleo: the workspace holds {ws.numel() * 4} bytes, {need} are needed")
+    call("lafs_koleo_fwd_bwd", _p(x), _ld(x), n_groups, rows, D, float(eps), float(grad_scale), _p(loss), _p(nn), _p(dx),
+         0 if dx is None else _ld(dx), int(bool(accumulate)), _p(ws))
+    return loss, nn

@@ -870,7 +870,9 @@ int lafs_cnn_stem(const float* x, const float* w, const float* b, int N, int S, 
  * [N,ceil(H/stride),ceil(W/stride),C] = act(conv + b).  C % 8 == 0. */
 int lafs_cnn_dwconv(const void* x, const float* w, const float* b, int N, int H, int W, int C, int k, int stride, int act,
                     void* y, hipStream_t stream);
-/* out(bf16)[n, c] = mean over the HW positions of x bf16 [N,HW,C]  (squeeze; final average pool). */
+/* out(bf16)[n, c] = mean over the HW positions of x bf16 [N,HW,C]  (squeeze; final average pool).  C % 8 == 0, ldo >= C: columns
+ * [C, ldo) of out are not written.  Two kernels (one workgroup per image for HW >= 16 and C <= 2048, else one thread per image and
+ * 8 channels), both with a fixed order of additions: a repeated call is bit-identical. */
 int lafs_cnn_pool(const void* x, int N, int HW, int C, void* out, int ldo, hipStream_t stream);
 /* x(bf16)[n,p,c] = act(x[n,p,c] * s(bf16)[n,c]) in place  (excite + the block's non-linearity). */
 int lafs_cnn_scale_act(void* x, const void* s, int lds, int N, int HW, int C, int act, hipStream_t stream);
@@ -1162,7 +1164,13 @@ int lafs_cnn_im2col_stem(const float* x, int N, int S, void* P, hipStream_t stre
  *                       backward; running_mean / running_var (NULL or both) get the momentum update with the unbiased variance;
  *   lafs_cnn_bn_bwd   : dz = (dy + add_nc[n, c] / HW) act'(z) with z recomputed from x; dx(fp16) = gamma rstd (dz - mean(dz) -
  *                       xhat mean(dz xhat)); dgamma += sum dz xhat / scale, dbeta += sum dz / scale (arena gradients, may be NULL);
- *                       dsums(f64)[2C] = caller-zeroed scratch.  add_nc fp16 [N, ldadd] (the squeeze-excite pooling gradient) or NULL. */
+ *                       dsums(f64)[2C] = caller-zeroed scratch.  add_nc fp16 [N, ldadd] (the squeeze-excite pooling gradient) or NULL.
+ * Contracts the kernel tests hold (tests/test_gpu_cnn_kernels.py): these three entry points accept any C <= ld (C % 8 != 0 included;
+ * only the strides must be multiples of 8); sums / dsums ACCUMULATE (what the buffer held enters the statistics, and dx of the
+ * same call); dgamma / dbeta accumulate; y and dx are written over all ld* columns with the pad channels [C, ld*) exactly zero
+ * (y whatever the inputs hold there, dx given finite x and dy there); columns of x / dy / resid / add_nc at or beyond the output's
+ * row stride are not read.  The fp64 atomics make the sums order-dependent at the 2^-52 level; stat, y and dx are functions of the
+ * sums handed in. */
 int lafs_cnn_bn_stats(const void* x, int ldx, int64_t R, int C, double* sums, hipStream_t stream);
 int lafs_cnn_bn_apply(const void* x, int ldx, int64_t R, int C, const double* sums, const float* gamma, const float* beta, float eps,
                       float momentum, float* running_mean, float* running_var, int act, const void* resid, int ldr, void* y, int ldy,
@@ -1203,7 +1211,8 @@ int lafs_cnn_cast_f16_f32(const void* src, float* dst, int64_t n, hipStream_t st
 /* Depthwise k x k convolution (k in {3,5}, stride in {1,2}, pad (k-1)/2, no bias) on NHWC bf16.  w = tap-major fp32 image [k*k][ld] of
  * the module's [C][1][k][k] tensor (lafs_cnn_dw_layout_table: table[8 e ..] = {src offset, C, k*k, dst offset, ld}, 256 elements per
  * workgroup); forward; backward = dx(bf16) and dw(f32, += into a tap-major image [k*k][ld] that lafs_cnn_unpad_add_table folds,
- * transposed, into the arena). */
+ * transposed, into the arena).  y and dx cover all ld channels (pad channels zero given zero pads in x, dy and w); dw is touched in
+ * columns [0, C) only, by fp32 atomics (one per tap, channel and slab of >= 1024 output pixels): not bitwise repeatable. */
 int lafs_cnn_dw_layout_table(const float* master, float* dst, const int64_t* table, const int32_t* starts, int n_entries, int n_blocks,
                              hipStream_t stream);
 int lafs_cnn_dwconv_train_fwd(const void* x, const float* w, int N, int H, int W, int ld, int C, int k, int stride, void* y,
@@ -1228,7 +1237,9 @@ int lafs_cnn_pad_cast_table(const float* master, void* dst, const int64_t* table
  * transpose, ...}; 256 elements per workgroup.  transpose: the source image is [cols][ld] (tap-major depthwise gradients). */
 int lafs_cnn_unpad_add_table(const float* padded, float* grad, const int64_t* table, const int32_t* starts, int n_entries, int n_blocks,
                              const float* grad_scale, hipStream_t stream);
-/* Backward of theta = (t - min) / (max - min) * 111 per image (ViT_face.py:698-706), incl. the paths through min and max. */
+/* Backward of theta = (t - min) / (max - min) * 111 per image (ViT_face.py:698-706), incl. the paths through min and max: with equal
+ * extrema the FIRST occurrence takes the gradient, as torch.min / torch.max select.  n = 2 n_full > 1; fixed order, bit-identical
+ * on a repeated call. */
 int lafs_landmark_theta_bwd(const float* t, const float* dtheta, int B, int n, float* dt, hipStream_t stream);
 
 /* Landmark post-processing (face_pre_pro/ViT_face.py:1347-1378, 698-706): t f32 [B, 2*n_full] raw regressor output ->

@@ -6,6 +6,8 @@ The reference rounds to 16 bits exactly where include/lafs_hip.h says the kernel
 stores a 16-bit value the bound is the distance to the neighbouring 16-bit values its unrounded value can reach (`flip`): 0 where no
 rounding boundary lies within reach, so most 16-bit outputs must match the reference exactly.
 
+(The landmark CNN's kernels use the building blocks of the last section from tests/cnn_cases.py, judged on the CPU by
+tests/test_oracle_cnn_host.py.)
 Shared by tests/test_gpu_mlp_fused.py, tests/test_gpu_gemm.py, tests/test_gpu_wgrad.py, tests/test_gpu_layernorm.py, tests/test_gpu_optim.py,
 tests/test_gpu_dino_head.py and the three CPU modules tests/test_oracle_gemm_host.py, tests/test_oracle_rowops_host.py and
 tests/test_oracle_dino_host.py (which show that the bounds are tight
@@ -631,6 +633,88 @@ def center_ema(center, colsum, inv_rows, m):
     new = colsum * ir * (f32c(1.0) - mm)
     ref = center * mm + new
     return ref, U * ((center * mm).abs() + 2 * new.abs() + ref.abs())
+
+
+# ------------------------------------------------------------------------------------------------ the landmark CNN (landmark_cnn.hip,
+# landmark_train.hip): activation derivatives, depthwise convolutions, column means
+def act_grad(z, ze, kind):
+    """act_grad_f of landmark_train.hip on a pre-activation z the kernel holds to within ze: (derivative, bound, knife).  relu': z > 0;
+    h-swish': 0 for z <= -3, 1 for z >= 3, (2 z + 3) (1 / 6) between (2 z exact, the sum rounds, the product with the rounded constant
+    rounds twice); h-sigmoid': 1 / 6 for -3 < z < 3 (the rounded constant: u / 6), else 0.  The derivatives jump at the kinks -- relu'
+    by 1 at 0, h-swish' by 0.5 at -3 (0 -> -0.5) and at 3 (1.5 -> 1), h-sigmoid' by 1 / 6 at +-3: an element whose z lies within ze
+    of a kink (`knife`) may take either branch, and its bound admits both.  With ze = 0 nothing is on a knife edge and the side is
+    the source's."""
+    zero = torch.zeros_like(z)
+    if kind == ACT_NONE:
+        return torch.ones_like(z), zero, torch.zeros_like(z, dtype=torch.bool)
+    if kind == ACT_RELU:
+        knife = z.abs() < ze
+        return (z > 0).double(), knife.double(), knife
+    knife = ((z + 3).abs() < ze) | ((z - 3).abs() < ze)
+    if kind == ACT_HSWISH:
+        mid = (z > -3) & (z < 3)
+        d = torch.where(mid, (2 * z + 3) / 6, (z >= 3).double())
+        e = torch.where(mid, ze / 3 + U * ((2 * z + 3).abs() / 6 + 2 * d.abs()), zero)
+        return d, e + 0.5 * knife.double(), knife
+    if kind == ACT_HSIGMOID:
+        mid = (z > -3) & (z < 3)
+        return mid.double() / 6, torch.where(mid, zero + U / 6, zero) + knife.double() / 6, knife
+    raise ValueError(kind)
+
+
+def _dw_geom(H, W, k, stride):
+    return (H + stride - 1) // stride, (W + stride - 1) // stride, (k - 1) // 2
+
+
+def dwconv(x, w, k, stride):
+    """Depthwise k x k convolution, stride 1 or 2, pad (k - 1) / 2, of NHWC x [N, H, W, C] with tap-major weights w [k k, C]: (value,
+    sum |terms|) [N, ceil(H / stride), ceil(W / stride), C] -- nn.Conv2d(C, C, k, stride, (k - 1) // 2, groups=C) without its bias."""
+    N, H, W, C = x.shape
+    Ho, Wo, P = _dw_geom(H, W, k, stride)
+    xp = torch.zeros(N, H + 2 * P, W + 2 * P, C, dtype=x.dtype, device=x.device)
+    xp[:, P:P + H, P:P + W] = x
+    v = torch.zeros(N, Ho, Wo, C, dtype=x.dtype, device=x.device)
+    s = torch.zeros_like(v)
+    for ky in range(k):
+        for kx in range(k):
+            t = xp[:, ky:ky + stride * (Ho - 1) + 1:stride, kx:kx + stride * (Wo - 1) + 1:stride] * w[ky * k + kx]
+            v, s = v + t, s + t.abs()
+    return v, s
+
+
+def dwconv_bwd(x, dy, w, k, stride):
+    """Both gradients of `dwconv`: (dx, sum |terms of dx|) [N, H, W, C] and (dw, sum |terms of dw|) [k k, C]."""
+    N, H, W, C = x.shape
+    Ho, Wo, P = _dw_geom(H, W, k, stride)
+    xp = torch.zeros(N, H + 2 * P, W + 2 * P, C, dtype=x.dtype, device=x.device)
+    xp[:, P:P + H, P:P + W] = x
+    dxp, sxp = torch.zeros_like(xp), torch.zeros_like(xp)
+    dw, sw = torch.zeros_like(w), torch.zeros_like(w)
+    for ky in range(k):
+        for kx in range(k):
+            sl = (slice(None), slice(ky, ky + stride * (Ho - 1) + 1, stride), slice(kx, kx + stride * (Wo - 1) + 1, stride))
+            t = dy * w[ky * k + kx]
+            dxp[sl] += t
+            sxp[sl] += t.abs()
+            u = dy * xp[sl]
+            dw[ky * k + kx] = u.sum((0, 1, 2))
+            sw[ky * k + kx] = u.abs().sum((0, 1, 2))
+    crop = (slice(None), slice(P, P + H), slice(P, P + W))
+    return (dxp[crop], sxp[crop]), (dw, sw)
+
+
+def tree_depth(n, lanes):
+    """Most fp32 additions a term passes through when `lanes` threads each add their share of n terms in sequence and a binary tree
+    over the lanes follows: a sum of any sign is then off by at most depth u sum|terms|."""
+    return -(-n // lanes) + max(1, math.ceil(math.log2(lanes)))
+
+
+def col_mean(x, depth, r16):
+    """mean over dim 1 of x [N, HW, C] as the pooling kernels form it: a sum of the given depth, then the product with the rounded
+    fp32 reciprocal 1.0f / HW (2 u), stored to 16 bits."""
+    HW = x.shape[1]
+    m = x.mean(1)
+    return flip(m, depth * U * x.abs().sum(1) / HW + 2 * U * m.abs(), r16)
 
 
 # ------------------------------------------------------------------------------------------------ checks
